@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmarks of EgoNeRF's volume-rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config render|train|erp]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config render|train|erp] [--full] [--dump-outputs DIR]
 
 `--config render` (default) is the headline: BASELINE configs[1] — OmniBlender-barbershop shape (grid [150,172,516]),
 4096-ray batch, 512 samples/ray, eval, no resampling.  A step = one EgoNeRF.forward over one batch already resident in HBM
@@ -13,6 +13,11 @@ sharded over the ranks, per-image PSNR all-reduced).
 N > 1: one process per GPU over RCCL.  Either the caller launches the ranks (torch.distributed.run sets RANK / WORLD_SIZE /
 LOCAL_RANK / MASTER_*), or — when WORLD_SIZE is absent — this script re-executes itself through torch.distributed.run on
 127.0.0.1.  Rays are independent, so ranks shard work with no data-path collective.  Rank 0 prints ONE JSON line.
+
+A plain `--config render` run sets up, warms up, times the K steps and prints the headline line (its `roofline`, `cpu_baseline`
+and `parity` are null).  `--full` adds everything else the line has carried: the per-kernel split and roofline, the other
+arithmetics, the early-termination variant, the CPU baselines, the parity leg against the oracle and the `secondary` block of
+the other configurations.  `--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -89,8 +94,14 @@ def parse():
     ap.add_argument("--shape", type=int, nargs=3, default=None, metavar=("RAYS", "N_COARSE", "N_FINE"), help="render: another batch shape on the "
                     "headline scene, e.g. 256 64 0 (BASELINE configs[0]) or 4096 256 256 (SURVEY 8(d) Config 2's resampling secondary: the path "
                     "every shipped config uses, configs/EgoNeRF/common.txt:15-23); N_FINE > 0 = inverse-CDF resampling, coarse samples kept")
+    ap.add_argument("--full", action="store_true", help="render: besides the headline timing, the per-kernel split, roofline, other "
+                    "arithmetics, CPU baselines, parity against the oracle and the `secondary` runs of the other configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path returned in its last timed step (rank 0) "
+                    "as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed, seeded row sample of anything larger)")
     ap.add_argument("--cpu-worker", nargs=2, type=int, metavar=("N_RAYS", "THREADS"), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.dump_outputs and a.config == "train":
+        ap.error("--dump-outputs: not available for --config train")
     dflt = dict(render=(200, 10), train=(20, 3), erp=(4, 1), metrics=(10, 2))[a.config]  # render: 0.7 ms steps, amortise the barrier bracket
     a.steps = dflt[0] if a.steps is None else a.steps
     a.warmup = dflt[1] if a.warmup is None else a.warmup
@@ -209,6 +220,32 @@ def timed(rk: Ranks, step, steps: int, warmup: int) -> float:
         step()
     rk.barrier()
     return rk.max_over_ranks(time.perf_counter() - t0)
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+FORWARD_OUTPUTS = ("rgb_map", "depth_map", "bg_map", "env_map", "alpha")   # EgoNeRF.forward's return tuple, in order
+
+
+def forward_arrays(out) -> dict:
+    """EgoNeRF.forward's outputs by name (None entries dropped)."""
+    return {n: t for n, t in zip(FORWARD_OUTPUTS, out) if t is not None}
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array, float64 kept and everything else as float32.  Above DUMP_LIMIT_BYTES in all, each array keeps
+    a fixed row sample (seeded, sorted, the same on every run) of its share of the budget."""
+    os.makedirs(dirpath, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        host[name] = v if v.dtype == np.float64 else v.astype(np.float32)
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_LIMIT_BYTES and v.ndim >= 1 and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * DUMP_LIMIT_BYTES / total))
+            if keep < v.shape[0]:
+                v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(v))
 
 
 # =====================================================================================================
@@ -380,11 +417,35 @@ def run_render(a, rk: Ranks):
     model = synth.build_model(cfg, weights, dev)
     rays = torch.from_numpy(synth.make_rays(N_RAYS, seed=1 + rk.rank)).to(dev)
     kw = dict(n_coarse=N_SAMPLES, exp_sampling=True)
+    last = {}
+    step = (lambda: last.__setitem__("out", model(rays, **kw))) if a.dump_outputs else (lambda: model(rays, **kw))
     with torch.no_grad():
-        dt = timed(rk, lambda: model(rays, **kw), a.steps, a.warmup)
+        dt = timed(rk, step, a.steps, a.warmup)
     headline_spread = rk.rank_step_ms(a.steps)
     if rk.rank != 0:
         return None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, forward_arrays(last["out"]))
+    rays_per_s = rk.world * N_RAYS * a.steps / dt
+    line = dict(metric="rays/sec at 4096-ray batch, 512 samples (EgoNeRF volume-rendering forward)", value=rays_per_s,
+                unit="rays/s", samples_per_s=rays_per_s * N_SAMPLES, n_gpus=rk.world, steps=a.steps, warmup=a.warmup,
+                rank_step_ms=headline_spread,
+                clock_ramp_s=RAMP_SECONDS,  # untimed: the same step repeated before the W warm-up steps (see timed())
+                ms_per_step=dt / a.steps * 1e3, higher_is_better=True, scaling="weak", vs_baseline=None,
+                dtype={"f16x3": "f32 (tables, interpolation, compositing; matrix products as 3x fp16 MFMA with fp32 accumulate)",
+                       "f16f8": "f32 (tables, interpolation, compositing; matrix products: fp16 MFMA main term + block-scaled fp8 MFMA "
+                                "correction terms in the MLP, 3x fp16 MFMA in the basis, fp32 accumulate)",
+                       "f16f6": "f32 (tables, interpolation, compositing; matrix products: fp16 MFMA main term + block-scaled fp6 MFMA "
+                                "correction terms with per-lane dynamic block scales in the MLP, 3x fp16 MFMA in the basis, fp32 accumulate)",
+                       "f32": "f32"}[model.mlp_precision],
+                data="synthetic",
+                config=dict(workload="OmniBlender barbershop shape: grid [150,172,516], 16x3/48x3 comps, MLP_Fea; "
+                                     "4096 rays x 512 samples, eval, no resampling (BASELINE configs[1])"
+                                     + ("" if a.density_shift is None else f"; NON-HEADLINE variant: density_shift {a.density_shift}"),
+                            rays_per_step_per_gpu=N_RAYS, samples_per_ray=N_SAMPLES, parallelism=f"ray-sharded x{rk.world}"),
+                roofline=None, cpu_baseline=None, parity=None, speedup_vs_cpu=None)
+    if not a.full:   # a plain run: the headline figure only
+        return line
     # ---- per-kernel durations, measured live with events on the launch stream (same work as a step) ----
     lib, st = _lib.load(), _lib.stream_handle()
     sc = model.scene()
@@ -564,25 +625,9 @@ def run_render(a, rk: Ranks):
             cpu = cpu_baseline_all_cores()
         except Exception as e:  # the single-process figure still stands
             cpu = dict(cpu_single, note=f"all-cores run failed: {e!r}")
-    rays_per_s = rk.world * N_RAYS * a.steps / dt
-    return dict(metric="rays/sec at 4096-ray batch, 512 samples (EgoNeRF volume-rendering forward)", value=rays_per_s,
-                unit="rays/s", samples_per_s=rays_per_s * N_SAMPLES, n_gpus=rk.world, steps=a.steps, warmup=a.warmup,
-                rank_step_ms=headline_spread,
-                clock_ramp_s=RAMP_SECONDS,  # untimed: the same step repeated before the W warm-up steps (see timed())
-                ms_per_step=dt / a.steps * 1e3, higher_is_better=True, scaling="weak", vs_baseline=None,
-                dtype={"f16x3": "f32 (tables, interpolation, compositing; matrix products as 3x fp16 MFMA with fp32 accumulate)",
-                       "f16f8": "f32 (tables, interpolation, compositing; matrix products: fp16 MFMA main term + block-scaled fp8 MFMA "
-                                "correction terms in the MLP, 3x fp16 MFMA in the basis, fp32 accumulate)",
-                       "f16f6": "f32 (tables, interpolation, compositing; matrix products: fp16 MFMA main term + block-scaled fp6 MFMA "
-                                "correction terms with per-lane dynamic block scales in the MLP, 3x fp16 MFMA in the basis, fp32 accumulate)",
-                       "f32": "f32"}[model.mlp_precision],
-                data="synthetic",
-                config=dict(workload="OmniBlender barbershop shape: grid [150,172,516], 16x3/48x3 comps, MLP_Fea; "
-                                     "4096 rays x 512 samples, eval, no resampling (BASELINE configs[1])"
-                                     + ("" if a.density_shift is None else f"; NON-HEADLINE variant: density_shift {a.density_shift}"),
-                            rays_per_step_per_gpu=N_RAYS, samples_per_ray=N_SAMPLES, parallelism=f"ray-sharded x{rk.world}"),
-                roofline=roofline, cpu_baseline=cpu, cpu_baseline_single_process=cpu_single, parity=parity,
+    line.update(roofline=roofline, cpu_baseline=cpu, cpu_baseline_single_process=cpu_single, parity=parity,
                 speedup_vs_cpu=None if cpu is None else rays_per_s / cpu["value"])
+    return line
 
 
 
@@ -607,13 +652,15 @@ def run_render_variant(a, rk: Ranks):
     state = dict(i=0)
 
     def step():
-        model(batches[state["i"] % B], **kw)
+        state["out"] = model(batches[state["i"] % B], **kw)
         state["i"] += 1
     with torch.no_grad():
         dt = timed(rk, step, a.steps, a.warmup)
     spread = rk.rank_step_ms(a.steps)
     if rk.rank != 0:
         return None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, forward_arrays(state["out"]))
     lib, st = _lib.load(), _lib.stream_handle()
     sc = model.scene()
     M = N_RAYS * N_SAMPLES
@@ -697,11 +744,15 @@ def run_render_shape(a, rk: Ranks):
     model = synth.build_model(cfg, weights, dev)
     rays = torch.from_numpy(synth.make_rays(N, seed=1 + rk.rank)).to(dev)
     kw = dict(n_coarse=nc, exp_sampling=True) if nf == 0 else dict(n_coarse=nc, n_fine=nf, resampling=True, use_coarse_sample=True, exp_sampling=True)
+    last = {}
+    step = (lambda: last.__setitem__("out", model(rays, **kw))) if a.dump_outputs else (lambda: model(rays, **kw))
     with torch.no_grad():
-        dt = timed(rk, lambda: model(rays, **kw), a.steps, a.warmup)
+        dt = timed(rk, step, a.steps, a.warmup)
     spread = rk.rank_step_ms(a.steps)
     if rk.rank != 0:
         return None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, forward_arrays(last["out"]))
     S = nc + nf
     if nf:
         split, skipped = erp_chunk_split(model, rays, reps=24, ERP_NC=nc, ERP_NF=nf)
@@ -789,6 +840,8 @@ def run_eval_metrics(a, rk: Ranks):
     spread = rk.rank_step_ms(a.steps)
     if rk.rank != 0:
         return None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {k: np.float64(v) for k, v in out.items()})
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(12)]
     for i in range(14):
         e = evs[max(i - 2, 0)]
@@ -1184,6 +1237,8 @@ def run_erp(a, rk: Ranks):
         model.early_termination_eps = a.term_eps
         dt = timed(rk, step, a.steps, a.warmup)
         spread = rk.rank_step_ms(a.steps)
+        if a.dump_outputs and rk.rank == 0:
+            dump_outputs(a.dump_outputs, dict(rgb_map=state["last"]))
         psnrs = []
         imgs_on = []
         for k, ref in enumerate(refs):
@@ -1320,6 +1375,7 @@ def run_secondary(a, rk: Ranks):
 
     def sub(**over):
         b = copy.copy(a)
+        b.dump_outputs = None   # what --dump-outputs writes is the headline's
         for k, v in over.items():
             setattr(b, k, v)
         return b
@@ -1493,11 +1549,11 @@ def main():
     variant = a.config == "render" and (a.n_voxel or a.fresh_rays or a.shape)
     line = (run_render_shape if (a.config == "render" and a.shape) else run_render_variant if variant
             else dict(render=run_render, train=run_train, erp=run_erp, metrics=run_eval_metrics)[a.config])(a, rk)
-    if a.config == "render" and not variant and rk.world == 1 and not a.no_secondary and a.density_shift is None:
+    if a.full and a.config == "render" and not variant and rk.world == 1 and not a.no_secondary and a.density_shift is None:
         line["secondary"] = run_secondary(a, rk)
     if rk.rank == 0:
         line["process_group"] = None if rk.dist is None else rk.dist.get_backend()   # "nccl" = RCCL on ROCm
-        paths = write_full(line, a)
+        paths = write_full(line, a) if (a.full or a.full_out) else []
         print(json.dumps(compact_line(line, paths), separators=(",", ":")), flush=True)
     rk.finish()
 

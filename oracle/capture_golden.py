@@ -55,6 +55,26 @@ from egonerf_amd import synth  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
 os.makedirs(OUT, exist_ok=True)
+PART_BYTES = 1_000_000   # raw bytes per fixture file: every committed file stays under 1 MiB
+
+
+def save_split(name: str, fx: dict):
+    """np.savez_compressed of `fx` as tests/golden/<name>.npz, continued in <name>.part2.npz, <name>.part3.npz, ... once the arrays
+    add up to more than PART_BYTES (keys in order; tests/conftest.py's `golden` fixture reads the parts as one file)."""
+    import glob
+    for old in glob.glob(os.path.join(OUT, name + ".part*.npz")):
+        os.remove(old)
+    parts, cur, size = [], {}, 0
+    for k, v in fx.items():
+        n = np.asarray(v).nbytes
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(OUT, name + (".npz" if i == 0 else f".part{i + 1}.npz")), **part)
 
 
 def build_reference(cfg: synth.SceneConfig, weights):
@@ -361,6 +381,56 @@ def capture_checkpoint():
                         bg=np_(o[2]), env=np_(o[3]), alpha=np_(o[4]))
 
 
+def capture_ours_checkpoint():
+    """The other direction of capture_checkpoint: a `.th` file written by THIS package's EgoNeRF.save (tiny grid, envmap, global_step
+    17), opened by the reference in a fresh process (stub modules for its missing third-party imports; train.py:52-56:
+    `EgoNeRF(**ckpt['kwargs'])`, `load(ckpt)`) and rendered.  The file and the reference's render of it go to the fixtures."""
+    import subprocess
+    import tempfile
+    import textwrap
+    cfg = synth.SceneConfig(n_voxel=20 ** 3, use_envmap=True, envmap_res_H=16)
+    model = synth.build_model(cfg, synth.make_weights(cfg, seed=77), "cpu")
+    model.coordinates.lut_device("cpu")  # a populated LUT cache must not leak into the file
+    path = os.path.join(OUT, "ours_ckpt.th")
+    model.save(path, 17)
+    rays = synth.make_rays(32, seed=5)
+    with tempfile.TemporaryDirectory() as tmp:
+        np.save(os.path.join(tmp, "rays.npy"), rays)
+        code = textwrap.dedent(f"""
+            import sys, types, io, contextlib
+            sys.dont_write_bytecode = True
+            sys.path.insert(0, {REF!r})
+            import numpy as np, torch
+            def stub(name, **a):
+                m = types.ModuleType(name); m.__dict__.update(a); sys.modules[name] = m; return m
+            stub("kornia", create_meshgrid=None); stub("cv2", COLORMAP_JET=2)
+            tv = stub("torchvision"); tv.transforms = stub("torchvision.transforms")
+            stub("imageio"); stub("plyfile", PlyData=None, PlyElement=None)
+            sk = stub("skimage"); sk.measure = stub("skimage.measure"); stub("lpips")
+            # the reference builds its EnvironmentMap on "cuda" by default (models/envmap.py:18-20): keep its allocations on the CPU
+            _rand, _zeros = torch.rand, torch.zeros
+            torch.rand = lambda *a, **k: _rand(*a, **{{**k, "device": "cpu"}})
+            torch.zeros = lambda *a, **k: _zeros(*a, **{{**k, "device": "cpu"}})
+            with contextlib.redirect_stdout(io.StringIO()):
+                from models.EgoNeRF import EgoNeRF
+                from renderer import volume_renderer
+                ckpt = torch.load({path!r}, map_location="cpu", weights_only=False)
+                kwargs = ckpt["kwargs"]; kwargs.update({{"device": "cpu"}})
+                model = EgoNeRF(**kwargs)
+                step = model.load(ckpt)
+                model.eval()
+                rays = torch.from_numpy(np.load({os.path.join(tmp, "rays.npy")!r}))
+                o = volume_renderer(rays, model, chunk=4096, n_coarse=16, n_fine=16, exp_sampling=True, resampling=True,
+                                    use_coarse_sample=True, device="cpu", interval_th=True)
+            np.savez({os.path.join(tmp, "out.npz")!r}, step=step, rgb=o[0].detach().numpy(), depth=o[1].detach().numpy(), env=o[3].detach().numpy())
+        """)
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = np.load(os.path.join(tmp, "out.npz"))
+        np.savez_compressed(os.path.join(OUT, "ours_ckpt_reference_render.npz"), rays=rays, step=out["step"], rgb=out["rgb"],
+                            depth=out["depth"], env=out["env"])
+
+
 def capture_train_extras():
     """Training-step pieces beyond the MSE gradient (train.py:245-330): ray-entropy gradient through `alpha` with the envmap's
     ones column, envmap-emission gradient, envmap pre-training (train.py:218-236), the TV / L1 / ortho regularisers
@@ -433,7 +503,7 @@ def capture_train_extras():
             fx[f"up/{k}"] = np_(p)
     o = run_forward(model, rays, n_coarse=16, n_fine=16, resampling=True, use_coarse_sample=True)
     fx.update(up_rgb=np_(o[0]), up_depth=np_(o[1]))
-    np.savez_compressed(os.path.join(OUT, "train_extras.npz"), **fx)
+    save_split("train_extras", fx)
 
 
 def capture_metrics():
@@ -729,7 +799,7 @@ def capture_shapes_grad():
         if cfg.use_envmap:
             fx[f"{name}/grad/envmap.emission"] = np_(model.envmap.emission.grad)
     fx["seed_weights"], fx["seed_rays"] = 4321, 17
-    np.savez_compressed(os.path.join(OUT, "shapes_grad.npz"), **fx)
+    save_split("shapes_grad", fx)
 
 
 HEADS = {   # the other appearance heads EgoNeRF.forward runs with (tensorBase.py:186-200); `fea_pe` is what opt.py passes, MLPRender ignores it
@@ -783,7 +853,7 @@ def capture_heads():
 
 if __name__ == "__main__":
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["tiny", "stages", "full", "alpha_mask", "checkpoint", "train_extras", "metrics", "plainexp", "sh", "uniform", "ricoh", "envmap_full", "ws", "skip", "omniblender", "shapes", "shapes_grad", "heads"]
+    which = sys.argv[1:] or ["tiny", "stages", "full", "alpha_mask", "checkpoint", "ours_checkpoint", "train_extras", "metrics", "plainexp", "sh", "uniform", "ricoh", "envmap_full", "ws", "skip", "omniblender", "shapes", "shapes_grad", "heads"]
     for name in which:
         globals()["capture_" + name]()
         print("captured", name)

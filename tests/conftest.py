@@ -35,15 +35,41 @@ def _library_is_current():
     build_library(force=False)
 
 
+class _SplitNpz:
+    """A fixture stored as <name>.npz plus <name>.part2.npz, ... (oracle/capture_golden.py: save_split keeps every committed file
+    under 1 MiB), read like one np.load result: `.files` in order, `fx[key]`, `key in fx`."""
+
+    def __init__(self, paths):
+        import numpy as np
+        self._parts = [np.load(p) for p in paths]
+        self._where = {k: z for z in self._parts for k in z.files}
+        self.files = [k for z in self._parts for k in z.files]
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __iter__(self):
+        return iter(self.files)
+
+    def keys(self):
+        return list(self.files)
+
+
 @pytest.fixture(scope="session")
 def golden():
+    import glob
     import numpy as np
 
     cache = {}
 
     def load(name):
         if name not in cache:
-            cache[name] = np.load(os.path.join(GOLDEN, name + ".npz"))
+            path = os.path.join(GOLDEN, name + ".npz")
+            parts = sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz")), key=lambda p: int(p.rsplit(".part", 1)[1][:-4]))
+            cache[name] = _SplitNpz([path] + parts) if parts else np.load(path)
         return cache[name]
 
     return load

@@ -231,46 +231,58 @@ def test_saved_checkpoint_uses_only_reference_class_paths(tmp_path):
     assert type(c2) is type(model.coordinates) and c2.resolution == [10, 10, 30]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="needs the reference checkout (build container only)")
-def test_reference_opens_a_checkpoint_written_here(tmp_path):
-    """The real reference (subprocess, stub modules for its missing third-party imports) torch.loads a file written by
-    EgoNeRF.save, rebuilds `EgoNeRF(**ckpt['kwargs'])`, `load(ckpt)`s it (train.py:52-56) and renders; compared with the oracle."""
-    import subprocess, sys, textwrap
+def _load_with_stand_ins(path):
+    """torch.load of a checkpoint whose pickle names the reference's class paths, into bare stand-ins of those paths."""
+    import sys, types
+    pkg, mc, me = types.ModuleType("models"), types.ModuleType("models.coordinates"), types.ModuleType("models.envmap")
+    pkg.__path__ = []
+    mc.YinYangSphericalCoords = type("YinYangSphericalCoords", (), {"__module__": "models.coordinates"})
+    me.EnvironmentMap = type("EnvironmentMap", (), {"__module__": "models.envmap"})
+    saved = {n: sys.modules.get(n) for n in ("models", "models.coordinates", "models.envmap")}
+    sys.modules.update({"models": pkg, "models.coordinates": mc, "models.envmap": me})
+    try:
+        return torch.load(path, map_location="cpu", weights_only=False)
+    finally:
+        for n, m in saved.items():
+            if m is None:
+                sys.modules.pop(n, None)
+            else:
+                sys.modules[n] = m
+
+
+def _assert_same_content(a, b, where="ckpt"):
+    """Same keys, types, values; tensors bit-equal with the same dtype and shape; objects compared attribute by attribute."""
+    if isinstance(a, torch.Tensor):
+        assert isinstance(b, torch.Tensor) and a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), where
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), where
+    elif isinstance(a, dict):
+        assert isinstance(b, dict) and list(a) == list(b), (where, list(a), list(b))
+        for k in a:
+            _assert_same_content(a[k], b[k], f"{where}[{k!r}]")
+    elif isinstance(a, (list, tuple)):
+        assert type(a) is type(b) and len(a) == len(b), where
+        for i, (x, y) in enumerate(zip(a, b)):
+            _assert_same_content(x, y, f"{where}[{i}]")
+    elif hasattr(a, "__dict__"):
+        assert type(a).__module__ == type(b).__module__ and type(a).__name__ == type(b).__name__, where
+        _assert_same_content(vars(a), vars(b), f"{where}.{type(a).__name__}")
+    else:
+        assert type(a) is type(b) and a == b, (where, a, b)
+
+
+def test_reference_opens_a_checkpoint_written_here(tmp_path, golden):
+    """The real reference (fresh process, stub modules for its missing third-party imports) torch.loads a file written by
+    EgoNeRF.save, rebuilds `EgoNeRF(**ckpt['kwargs'])`, `load(ckpt)`s it (train.py:52-56) and renders: oracle/capture_golden.py
+    (capture_ours_checkpoint) recorded that file (tests/golden/ours_ckpt.th) and the reference's render of it.  The file written
+    here today must carry exactly what the reference opened, and the reference's render must agree with the oracle."""
     from oracle.egonerf_oracle import OracleScene
     cfg, w, model, path = _write_ckpt(tmp_path)
+    opened = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ours_ckpt.th")
+    _assert_same_content(_load_with_stand_ins(path), _load_with_stand_ins(opened))
+    out = golden("ours_ckpt_reference_render")
     rays = synth.make_rays(32, seed=5)
-    np.save(str(tmp_path / "rays.npy"), rays)
-    code = textwrap.dedent(f"""
-        import sys, types, io, contextlib
-        sys.dont_write_bytecode = True
-        sys.path.insert(0, "/root/reference")
-        import numpy as np, torch
-        def stub(name, **a):
-            m = types.ModuleType(name); m.__dict__.update(a); sys.modules[name] = m; return m
-        stub("kornia", create_meshgrid=None); stub("cv2", COLORMAP_JET=2)
-        tv = stub("torchvision"); tv.transforms = stub("torchvision.transforms")
-        stub("imageio"); stub("plyfile", PlyData=None, PlyElement=None)
-        sk = stub("skimage"); sk.measure = stub("skimage.measure"); stub("lpips")
-        # the reference builds its EnvironmentMap on "cuda" by default (models/envmap.py:18-20): keep its allocations on the CPU
-        _rand, _zeros = torch.rand, torch.zeros
-        torch.rand = lambda *a, **k: _rand(*a, **{{**k, "device": "cpu"}})
-        torch.zeros = lambda *a, **k: _zeros(*a, **{{**k, "device": "cpu"}})
-        with contextlib.redirect_stdout(io.StringIO()):
-            from models.EgoNeRF import EgoNeRF
-            from renderer import volume_renderer
-            ckpt = torch.load({path!r}, map_location="cpu", weights_only=False)
-            kwargs = ckpt["kwargs"]; kwargs.update({{"device": "cpu"}})
-            model = EgoNeRF(**kwargs)
-            step = model.load(ckpt)
-            model.eval()
-            rays = torch.from_numpy(np.load({str(tmp_path / "rays.npy")!r}))
-            o = volume_renderer(rays, model, chunk=4096, n_coarse=16, n_fine=16, exp_sampling=True, resampling=True,
-                                use_coarse_sample=True, device="cpu", interval_th=True)
-        np.savez({str(tmp_path / "out.npz")!r}, step=step, rgb=o[0].detach().numpy(), depth=o[1].detach().numpy(), env=o[3].detach().numpy())
-    """)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = np.load(str(tmp_path / "out.npz"))
+    assert np.array_equal(out["rays"], rays)
     assert int(out["step"]) == 17
     ref = OracleScene(cfg, w).forward(torch.from_numpy(rays), n_coarse=16, n_fine=16, resampling=True)
     assert np.abs(out["rgb"] - ref[0].numpy()).max() <= 2e-6 and np.abs(out["depth"] - ref[1].numpy()).max() <= 2e-5

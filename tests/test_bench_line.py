@@ -95,3 +95,39 @@ def test_compact_line_handles_missing_blocks_and_non_finite_numbers():
     back = json.loads(text)
     assert back["cpu_baseline"] is None and back["parity"] is None and back["roofline"]["traffic"] is None
     assert back["roofline"]["from_counter_pass"] is None
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_rows_above_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench_module()
+    arrays = dict(rgb_map=torch.arange(12, dtype=torch.float32).view(4, 3), depth_map=np.arange(4, dtype=np.float64),
+                  mask=np.array([1, 0, 1], dtype=np.uint8))
+    b.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert got["rgb_map"].dtype == np.float32 and np.array_equal(got["rgb_map"], arrays["rgb_map"].numpy())
+    assert got["depth_map"].dtype == np.float64 and np.array_equal(got["depth_map"], arrays["depth_map"])
+    assert got["mask"].dtype == np.float32 and got["mask"].tolist() == [1.0, 0.0, 1.0]
+    # over the budget: a fixed row sample, the same on every call, within the budget
+    old = b.DUMP_LIMIT_BYTES
+    b.DUMP_LIMIT_BYTES = 4096
+    try:
+        big = np.arange(1000 * 4, dtype=np.float32).reshape(1000, 4)
+        for d in ("b", "c"):
+            b.dump_outputs(str(tmp_path / d), dict(alpha=big))
+    finally:
+        b.DUMP_LIMIT_BYTES = old
+    s1, s2 = np.load(str(tmp_path / "b" / "alpha.npy")), np.load(str(tmp_path / "c" / "alpha.npy"))
+    assert np.array_equal(s1, s2) and s1.nbytes <= 4096 and s1.shape[1] == 4
+    rows = s1[:, 0].astype(np.int64) // 4
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, big[rows])
+
+
+def test_full_and_dump_options(monkeypatch):
+    b = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "9", "--warmup", "3"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 9 and a.warmup == 3
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out"

@@ -129,11 +129,41 @@ def _bench(*args, env_extra=None, launcher=None, env=None):
     return full
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """The plain command (no --full) times the headline and nothing else - no roofline, CPU baseline, parity or secondary in its line -
+    and --dump-outputs writes what the timed EgoNeRF.forward returned in its last step: the same forward run here agrees with it."""
+    dump = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", dump]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and r.stdout.rstrip().splitlines()[-1] == lines[0], r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] is None and "secondary" not in d
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) <= 1e-4 * d["value"]
+    cfg = synth.SceneConfig()
+    model = synth.build_model(cfg, synth.make_weights(cfg, seed=1234), "cuda")
+    rays = torch.from_numpy(synth.make_rays(4096, seed=1)).cuda()
+    with torch.no_grad():
+        out = model(rays, n_coarse=512, exp_sampling=True)
+    names = ("rgb_map", "depth_map", "bg_map", "env_map", "alpha")
+    want = {n: t.float().cpu().numpy() for n, t in zip(names, out) if t is not None}
+    assert sorted(os.listdir(dump)) == sorted(n + ".npy" for n in want)
+    assert {"rgb_map", "depth_map"} <= set(want)
+    for n, ref in want.items():
+        got = np.load(os.path.join(dump, n + ".npy"))
+        assert got.dtype == np.float32 and got.shape == ref.shape, n
+        assert np.isfinite(got).all() and np.abs(got - ref).max() <= 1e-6, n
+
+
 def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` with no launcher environment re-executes itself through torch.distributed.run."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["EGO_BENCH_TEST_SHARED_GPU"] = "1"
-    d = _bench("--gpus", "2", "--steps", "5", "--warmup", "2", env=env)
+    d = _bench("--gpus", "2", "--steps", "5", "--warmup", "2", "--full", env=env)
     assert d["n_gpus"] == 2 and d["steps"] == 5 and d["scaling"] == "weak" and d["cpu_baseline"] is None
     assert d["value"] > 0 and abs(d["value"] - 2 * 4096 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-9
     assert d["roofline"]["frac"] <= 1.0 and d["roofline"]["bound"] == "mfma" and "secondary" not in d and d["process_group"] == "gloo"
@@ -142,7 +172,7 @@ def test_bench_self_launches_two_ranks():
 def test_bench_default_line_contract():
     """The driver's command: one JSON line whose headline is BASELINE configs[1] and whose `secondary` block carries short runs of
     configs[3] (train) and configs[2] (erp), each with its own roofline and cpu_baseline."""
-    d = _bench("--steps", "10", "--warmup", "2", "--cpu-rays", "128")
+    d = _bench("--steps", "10", "--warmup", "2", "--cpu-rays", "128", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline", "secondary"):
         assert k in d, k

@@ -8,7 +8,7 @@ for rep in $(seq $REPS); do
   for v in $NAMES; do
     cp egonerf_amd/libvariant_$v.so egonerf_amd/libegonerf_hip.so
     for cfg in $CFGS; do
-      python bench.py --config $cfg --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+      python bench.py --config $cfg --full --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d.get('roofline') or {}

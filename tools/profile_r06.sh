@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 export EGO_SKIP_SELFTEST=1   # the self-test launches the SHIPPED shade kernels on a tiny scene: it would dilute their per-dispatch averages
-B="python $ROOT/bench.py --no-cpu-baseline --no-secondary"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-secondary"
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_fresh" -o trace -- $B --fresh-rays 64 --steps 128 --warmup 8 > "$OUT/bench_fresh_under_trace.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_big" -o trace -- $B --fresh-rays 64 --n-voxel 216e6 --steps 64 --warmup 8 > "$OUT/bench_big_under_trace.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_probe" -o trace -- python $ROOT/tools/stage_probe.py > "$OUT/stage_probe.log" 2>&1

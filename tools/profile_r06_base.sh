@@ -13,7 +13,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 export EGO_SKIP_SELFTEST=1   # the self-test launches the SHIPPED shade kernels on a tiny scene: it would dilute their per-dispatch averages
-B="python $ROOT/bench.py --no-cpu-baseline --no-secondary"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-secondary"
 # kernel-trace stats: render at its default step count (steady-state per-kernel averages), train, erp
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_render" -o trace -- $B > "$OUT/bench_render_under_trace.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_train" -o trace -- $B --config train --steps 10 --warmup 2 > "$OUT/bench_train_under_trace.log" 2>&1
