@@ -87,6 +87,15 @@ PROTOTYPES = {
     "ego_sample_ray_exp": (C.c_int, [P, P, P, F32, I64, I32, P, P, P]),
     "ego_erp_rays": (C.c_int, [I32, I32, I32, I32, C.POINTER(C.c_float), I32, P, P]),
     "ego_copy_out": (C.c_int, [I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), I32, P]),
+    "ego_density_feature_backward_workspace_bytes": (I64, [SP, I64, I32]),
+    "ego_density_feature_backward": (C.c_int, [SP, P, I64, I32, P, C.POINTER(VmGrad), P, I64, P]),
+    "ego_app_feature_backward_workspace_bytes": (I64, [SP, I64]),
+    "ego_app_feature_backward": (C.c_int, [SP, P, I64, P, C.POINTER(VmGrad), P, I32, P, I64, P]),
+    "ego_mlp_fea_backward_workspace_bytes": (I64, [SP, I64]),
+    "ego_mlp_fea_backward": (C.c_int, [SP, P, P, I64, P, P, P, P, I32, P, I32, P, I32, P, I64, P]),
+    "ego_sh_render_backward": (C.c_int, [P, P, I64, P, P, P, P]),
+    "ego_feature2density_backward": (C.c_int, [SP, P, I64, P, P, P]),
+    "ego_raw2alpha_backward": (C.c_int, [P, P, P, I64, I32, P, P, P, P, P, P]),
     "ego_from_cartesian": (C.c_int, [SP, P, I64, P, P]),
     "ego_normalize_coord": (C.c_int, [SP, P, I64, P, P]),
     "ego_density_feature": (C.c_int, [SP, P, I64, I32, P, P]),

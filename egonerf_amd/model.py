@@ -82,7 +82,18 @@ def _table_ptr(t: torch.Tensor) -> int:
 # ---------------------------------------------------------------------------------------------------
 @_lib.device_guard
 def raw2alpha(sigma: torch.Tensor, dist: torch.Tensor):
-    """alpha, weights, bg_weight of tensorBase.py:22-27 (sigma, dist: [N_rays, N_samples])."""
+    """alpha, weights, bg_weight of tensorBase.py:22-27 (sigma, dist: [N_rays, N_samples]).  Differentiable (to sigma and dist) when grad
+    mode is on and either requires grad: the forward values are the same bits, the backward (stage_autograd.Raw2AlphaFunction) is the
+    fp32-grade gradient of the reference function."""
+    _require_cuda(sigma, "raw2alpha")
+    from .stage_autograd import needs_grad
+    if needs_grad(sigma, dist):
+        from .stage_autograd import Raw2AlphaFunction
+        return Raw2AlphaFunction.apply(sigma, dist)
+    return _raw2alpha(sigma, dist)
+
+
+def _raw2alpha(sigma: torch.Tensor, dist: torch.Tensor):
     _require_cuda(sigma, "raw2alpha")
     sigma, dist = _f32c(sigma), _f32c(dist)
     N, S = sigma.shape
@@ -135,7 +146,17 @@ def SHRender(xyz_sampled, viewdirs: torch.Tensor, features: torch.Tensor) -> tor
     """models/tensorBase.py:30-34: degree-2 SH colour head, viewdirs [M,3], features [M,27] -> rgb [M,3] = relu(SH . f + 0.5).
     (`xyz_sampled` is unused, as in the reference.  The reference's EgoNeRF.forward cannot run with this head — it hands
     SHRender [N,S,3] view directions against [N*S,3,9] features and the broadcast raises — so it is offered as the stage
-    function only.)"""
+    function only.)  Differentiable (to viewdirs and features) when grad mode is on and either requires grad: same forward bits,
+    fp32-grade backward (stage_autograd.SHRenderFunction)."""
+    _require_cuda(viewdirs, "SHRender")
+    from .stage_autograd import needs_grad
+    if needs_grad(viewdirs, features):
+        from .stage_autograd import SHRenderFunction
+        return SHRenderFunction.apply(viewdirs, features)
+    return _sh_render(viewdirs, features)
+
+
+def _sh_render(viewdirs: torch.Tensor, features: torch.Tensor) -> torch.Tensor:
     _require_cuda(viewdirs, "SHRender")
     d, f = _f32c(viewdirs.reshape(-1, 3)), _f32c(features.reshape(-1, 27))
     if d.shape[0] != f.shape[0]:
@@ -161,9 +182,21 @@ class MLPRender_Fea(torch.nn.Module):
 
     @_lib.device_guard
     def forward(self, pts, viewdirs, features):
+        """Differentiable (to mlp.{0,2,4}.{weight,bias}, features and viewdirs) when grad mode is on and any of them requires grad: the
+        forward runs the same kernel with the model's mlp_precision (same bits), the backward (stage_autograd.MLPRenderFunction) is the
+        fp32 gradient of the reference head at the fp32 weights."""
         _require_cuda(features, "MLPRender_Fea")
         if self._owner is None:
             raise RuntimeError("MLPRender_Fea must belong to an EgoNeRF model (it owns the packed MFMA weights)")
+        from .stage_autograd import needs_grad
+        weights = [self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight, self.mlp[2].bias, self.mlp[4].weight, self.mlp[4].bias]
+        if needs_grad(viewdirs, features, *weights):
+            from .stage_autograd import MLPRenderFunction
+            return MLPRenderFunction.apply(self, viewdirs, features, *weights)
+        return self._forward_impl(viewdirs, features)
+
+    def _forward_impl(self, viewdirs, features):
+        _require_cuda(features, "MLPRender_Fea")
         model = self._owner()
         v = _f32c(viewdirs.reshape(-1, 3))
         f = _f32c(features.reshape(-1, features.shape[-1]))
@@ -272,7 +305,16 @@ class TensorBase(torch.nn.Module):
 
     @_lib.device_guard
     def feature2density(self, density_features: torch.Tensor) -> torch.Tensor:
-        """tensorBase.py:415-419."""
+        """tensorBase.py:415-419.  Differentiable when grad mode is on and the features require grad: same forward bits, the backward
+        (stage_autograd.Feature2DensityFunction) differentiates softplus (threshold 20) / relu as torch does."""
+        _require_cuda(density_features, "feature2density")
+        from .stage_autograd import needs_grad
+        if needs_grad(density_features):
+            from .stage_autograd import Feature2DensityFunction
+            return Feature2DensityFunction.apply(self, density_features)
+        return self._feature2density_forward(density_features)
+
+    def _feature2density_forward(self, density_features: torch.Tensor) -> torch.Tensor:
         _require_cuda(density_features, "feature2density")
         f = _f32c(density_features)
         out = torch.empty_like(f)
@@ -843,22 +885,47 @@ class EgoNeRF(TensorBase):
     def _density(self, coords_sampled, coarse: int):
         _require_cuda(coords_sampled, "compute_densityfeature")
         _last_dim(coords_sampled, 7, "compute_densityfeature")
+        from .stage_autograd import needs_grad
+        params = [p for tl in self._table_lists("density") for p in tl]
+        if needs_grad(*params):
+            from .stage_autograd import DensityFeatureFunction
+            return DensityFeatureFunction.apply(self, coarse, coords_sampled.detach(), *params)
+        return self._density_forward(coords_sampled, coarse)
+
+    def _density_forward(self, coords_sampled, coarse: int):
+        _require_cuda(coords_sampled, "compute_densityfeature")
+        _last_dim(coords_sampled, 7, "compute_densityfeature")
         c = _f32c(coords_sampled)
         out = torch.empty(c.shape[:-1], device=c.device)
         _call("ego_density_feature", self.scene(), c.data_ptr(), c.numel() // 7, coarse, out.data_ptr(), _lib.stream_handle())
         return out
 
     def compute_densityfeature(self, coords_sampled):
-        """EgoNeRF.py:291-347: [...,7] normalised coords -> [...]."""
+        """EgoNeRF.py:291-347: [...,7] normalised coords -> [...].  Differentiable to the 12 density tables when grad mode is on and one of
+        them requires grad (stage_autograd.DensityFeatureFunction): same forward bits, fp32-grade backward (grid_sample + relu), bit-
+        reproducible for the shipped 16-component shape.  The coordinates receive no gradient (the reference detaches them)."""
         return self._density(coords_sampled, 0)
 
     def compute_coarse_densityfeature(self, coords_sampled, coarse_sigma_grid_update_rule="conv"):
-        """EgoNeRF.py:232-289."""
+        """EgoNeRF.py:232-289.  Values from the last update_coarse_sigma_grid() snapshot; differentiable to the full-resolution density
+        tables through the 2x average pooling of EgoNeRF.py:124-133, like compute_densityfeature."""
         return self._density(coords_sampled, 1)
 
     @_lib.device_guard
     def compute_appfeature(self, coords_sampled):
-        """EgoNeRF.py:349-413: [...,7] -> [..., app_dim]."""
+        """EgoNeRF.py:349-413: [...,7] -> [..., app_dim].  Differentiable to the 12 appearance tables and basis_mat_{yin,yang}.weight when
+        grad mode is on and one of them requires grad (stage_autograd.AppFeatureFunction): same forward bits (whatever app_table_dtype),
+        fp32-grade backward at the fp32 tables, bit-reproducible for the shipped 48-component shape."""
+        _require_cuda(coords_sampled, "compute_appfeature")
+        _last_dim(coords_sampled, 7, "compute_appfeature")
+        from .stage_autograd import needs_grad
+        params = [p for tl in self._table_lists("app") for p in tl] + [self.basis_mat_yin.weight, self.basis_mat_yang.weight]
+        if needs_grad(*params):
+            from .stage_autograd import AppFeatureFunction
+            return AppFeatureFunction.apply(self, coords_sampled.detach(), *params)
+        return self._app_forward(coords_sampled)
+
+    def _app_forward(self, coords_sampled):
         _require_cuda(coords_sampled, "compute_appfeature")
         _last_dim(coords_sampled, 7, "compute_appfeature")
         c = _f32c(coords_sampled)

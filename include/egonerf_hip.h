@@ -507,6 +507,43 @@ int ego_rgb_ssim(const float* img0, const float* img1, int32_t H, int32_t W, dou
 #define EGO_COPY_OUT_MAX 8
 int ego_copy_out(int32_t count, const float* const* src, float* const* dst, const int64_t* n_floats, int32_t workgroups, void* stream);
 
+/* ---- backward of the separately callable stages (csrc/ego_stage_grad.hip): autograd of the reference's public stage methods, for losses
+ * built from them (the sparsity term of train.py:266-272, a render loop composed of stages).  Coordinates receive no gradient (the reference
+ * detaches them before grid_sample).  The forward entry points above are unchanged; these recompute what they need from the inputs.
+ * Gradient tables are channel-last like the parameters and WRITTEN (no zero fill needed).  `workspace`: dev, 256-byte aligned, of the
+ * size the matching *_workspace_bytes query returns (-1 = bad arguments). ---- */
+/* autograd of F.grid_sample + relu + sum in compute_densityfeature (EgoNeRF.py:291-347), g = dL/d out [M].  coarse != 0:
+ * compute_coarse_densityfeature (EgoNeRF.py:232-289) through the pooled tables into the FULL-resolution density gradients, i.e. the
+ * AvgPool2d / AvgPool1d backward of EgoNeRF.py:124-133 (1/4 per plane texel, 1/2 per line texel; an odd last row / column gets nothing);
+ * the relu masks come from sc->density_coarse, the snapshot the forward read.  16 components, coarse == 0: the sorted walk
+ * (ego_scatter_sort + ego_scatter_density_sorted, bit-reproducible); otherwise ego_scatter_generic's float atomics. */
+int64_t ego_density_feature_backward_workspace_bytes(const ego_scene* sc, int64_t M, int32_t coarse);
+int ego_density_feature_backward(const ego_scene* sc, const float* c7n, int64_t M, int32_t coarse, const float* g, const ego_vm_grad* gdensity,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+/* autograd of compute_appfeature (EgoNeRF.py:349-413), g = dL/d out [M][app_dim]: the appearance table gradients (48 components: sorted
+ * walk, bit-reproducible; otherwise float atomics) and gbasis [64][ldg >= 160]: row 32 grid + feature, column plane x n_comp + channel =
+ * d(basis_mat_{yin,yang}.weight) (ego_weight_grad_det, fixed summation order). */
+int64_t ego_app_feature_backward_workspace_bytes(const ego_scene* sc, int64_t M);
+int ego_app_feature_backward(const ego_scene* sc, const float* c7n, int64_t M, const float* g, const ego_vm_grad* gapp, float* gbasis, int32_t ldg,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+/* autograd of MLPRender_Fea.forward (tensorBase.py:54-78) / MLPRender.forward (:107-129, fea_pe = 0) from the fp32 reference-layout weights
+ * sc->mlp_w / mlp_b (not the packed blob), g_rgb = dL/d rgb [M][3].  d_feat [M][app_dim], d_viewdirs [M][3] (either may be NULL) through
+ * both positional encodings; g1 [featureC][ld1 >= 160 ceil((mlp_in + 1) / 160)] = [d W1 | d b1], g2 [featureC][ld2 >= 160] = [d W2 | d b2],
+ * g3 [32][ld3 >= 160] = [d W3 | d b3] in rows 0..2 (bias in column mlp_in / featureC; ego_weight_grad_det, fixed summation order). */
+int64_t ego_mlp_fea_backward_workspace_bytes(const ego_scene* sc, int64_t M);
+int ego_mlp_fea_backward(const ego_scene* sc, const float* viewdirs, const float* feat, int64_t M, const float* g_rgb, float* d_feat, float* d_viewdirs,
+                         float* g1, int32_t ld1, float* g2, int32_t ld2, float* g3, int32_t ld3, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+/* autograd of SHRender (tensorBase.py:30-34, sh.py:87-112): d_viewdirs [M][3], d_features [M][27] (either may be NULL) */
+int ego_sh_render_backward(const float* viewdirs, const float* features, int64_t M, const float* g_rgb, float* d_viewdirs, float* d_features,
+                           void* stream);
+/* autograd of feature2density (tensorBase.py:415-419): softplus(f + density_shift) with torch's threshold 20, or relu */
+int ego_feature2density_backward(const ego_scene* sc, const float* feat, int64_t M, const float* g, float* d_feat, void* stream);
+/* autograd of raw2alpha (tensorBase.py:22-27) over [N][S]: gradients g_alpha, g_weight [N][S], g_bg [N] (any may be NULL) -> d_sigma,
+ * d_dist [N][S].  The cumprod backward as a per-ray reverse scan without division by 1 - alpha + 1e-10 (exact where it underflows). */
+int ego_raw2alpha_backward(const float* sigma, const float* dist, const float* alpha, int64_t N, int32_t S, const float* g_alpha, const float* g_weight,
+                           const float* g_bg, float* d_sigma, float* d_dist, void* stream);
+
 typedef struct ego_render_args {
   int32_t n_coarse, n_fine;
   int32_t resampling, use_coarse_sample;
