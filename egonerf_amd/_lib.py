@@ -118,6 +118,7 @@ PROTOTYPES = {
     "ego_composite": (C.c_int, [SP, P, P, P, P, P, I64, I32, P, P, P, P, P, P]),
     "ego_shade_composite": (C.c_int, [SP, P, P, P, P, P, I64, I32, P, P, P, P, P, P]),
     "ego_render_forward_folds": (C.c_int32, [SP, I64, I32]),
+    "ego_render_forward_compacts": (C.c_int32, [SP, I64, I32]),
     "ego_train_packed_floats": (I64, []),
     "ego_pack_train": (C.c_int, [SP, P, P]),
     "ego_train_layout": (C.c_int, [I32, C.POINTER(C.c_int32), I32]),
@@ -148,6 +149,7 @@ PROTOTYPES = {
     "ego_rgb_ssim": (C.c_int, [P, P, I32, I32, C.c_double, I32, C.c_double, C.c_double, C.c_double, P, P, P]),
     "ego_render_workspace_bytes": (I64, [I64, C.POINTER(RenderArgs)]),
     "ego_render_forward": (C.c_int, [SP, C.POINTER(RenderArgs), P, I64, P, P, P, P, P, P, P]),
+    "ego_render_shaded_samples": (C.c_int, [I64, C.POINTER(RenderArgs), P, P, P]),
 }
 
 _lib = None

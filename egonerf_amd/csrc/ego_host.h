@@ -26,6 +26,13 @@ inline int ego_fail(int code, const char* fmt, ...) {
 // csrc/ego_shade.hip: can ego_shade_composite serve this scene and sample count? (asked by ego_render_forward)
 bool ego_can_fold_composite(const ego_scene* sc, int32_t S);
 bool ego_fold_is_balanced(int64_t N, int32_t S);
+// ... and the compact path's pieces: the live-sample list (csrc/ego_compact.hip) and the shade over it (csrc/ego_shade.hip)
+int64_t ego_live_blocks(int64_t N);
+int ego_compact_live(const float* weight, int64_t N, int32_t S, float above, int32_t* live, int32_t* count, int32_t* part, int32_t* n_live,
+                     void* stream);
+int ego_shaded_count(int32_t mode, const int32_t* n_live, const uint8_t* act, int64_t N, int32_t S, int64_t* out, void* stream);
+int ego_shade_live(const ego_scene* sc, const float* rays, const float* z, const float* coords, int64_t N, int32_t S, const int32_t* live,
+                   const int32_t* n_live, float* rgb, void* stream);
 
 inline int ego_launch_status(const char* kernel) {
   const hipError_t e = hipGetLastError();

@@ -1,10 +1,14 @@
 // libegonerf_hip.so, part 3: EgoNeRF.forward as one call (models/EgoNeRF.py:491-602) — a fixed
 // sequence of launches on the caller's stream, no host synchronisation, no allocation.
 #include "ego_host.h"
+#include "ego_generic.h"
+
+#include <cstdlib>
+#include <mutex>
 
 namespace {
 struct Plan {
-  int64_t zc, wc, zf, w, bg, rgb, crd, act, total;  // float offsets
+  int64_t zc, wc, zf, w, bg, rgb, crd, act, live, cnt, part, nlive, total;  // float offsets (live / cnt / part / nlive: int32)
   int32_t S_out;
 };
 
@@ -23,8 +27,41 @@ Plan make_plan(int64_t N, const ego_render_args* a) {
   p.rgb = o; o = align64(o + N * (int64_t)p.S_out * 3);
   p.crd = o; o = align64(o + N * (int64_t)p.S_out * 4);
   p.act = o; o = align64(o + (N * (int64_t)p.S_out / 32 + 1 + 3) / 4);  // tile flags (bytes)
+  // compact path (ego_render_forward_compacts): the live-sample list, per-ray counts, per-block offsets, the live count
+  p.live = o; o = align64(o + N * (int64_t)p.S_out);
+  p.cnt = o; o = align64(o + N);
+  p.part = o; o = align64(o + ego_live_blocks(N));
+  p.nlive = o; o = align64(o + 1);
   p.total = o;
   return p;
+}
+
+// Which path the last ego_render_forward on a workspace took, for ego_render_shaded_samples: the choice is made on the host, so it is
+// recorded there (a marker in the workspace would cost the paths without a list a write of their own).  A few recent workspaces suffice.
+enum { SHADED_ALL = 0, SHADED_TILES = 1, SHADED_LIVE = 2 };
+struct ShadeRecord {
+  const void* ws;
+  int64_t N;
+  int32_t S, mode;
+};
+constexpr int N_RECORDS = 64;
+std::mutex records_mu;
+ShadeRecord records[N_RECORDS];
+int records_next = 0;
+
+void record_path(const void* ws, int64_t N, int32_t S, int32_t mode) {
+  std::lock_guard<std::mutex> g(records_mu);
+  for (ShadeRecord& r : records)
+    if (r.ws == ws) { r = ShadeRecord{ws, N, S, mode}; return; }
+  records[records_next] = ShadeRecord{ws, N, S, mode};
+  records_next = (records_next + 1) % N_RECORDS;
+}
+
+bool find_path(const void* ws, ShadeRecord* out) {
+  std::lock_guard<std::mutex> g(records_mu);
+  for (const ShadeRecord& r : records)
+    if (r.ws == ws) { *out = r; return true; }
+  return false;
 }
 }  // namespace
 
@@ -41,6 +78,13 @@ int64_t ego_render_workspace_bytes(int64_t N, const ego_render_args* args) {
   return make_plan(N, args).total * (int64_t)sizeof(float);
 }
 
+int32_t ego_render_forward_compacts(const ego_scene* sc, int64_t N, int32_t S) {
+  const char* f = getenv("EGO_RENDER_COMPACT");
+  if (f && f[0] == '0') return 0;
+  if (!sc || N < 1 || S < 1 || N * (int64_t)S >= (1ll << 31) || !ego_shape_is_tuned(sc) || !(sc->weight_thres >= 0.f)) return 0;
+  return (f && f[0] == '1') || sc->occ || sc->weight_thres > 0.f ? 1 : 0;
+}
+
 int ego_render_forward(const ego_scene* sc, const ego_render_args* a, const float* rays, int64_t N, void* workspace,
                        float* rgb_map, float* depth, float* alpha, float* bg_map, float* env_map, void* stream) {
   EGO_TRACE("ego_render_forward");
@@ -55,8 +99,11 @@ int ego_render_forward(const ego_scene* sc, const ego_render_args* a, const floa
   const int32_t astride = sc->envmap ? S + 1 : S;
   int e;
   const float* z;
-  // tile-level skipping only when a mask, early termination or the weight threshold is switched on (otherwise every sample is shaded)
-  uint8_t* act = (sc->occ || sc->term_eps > 0.f || sc->weight_thres >= 0.f) ? (uint8_t*)(ws + p.act) : nullptr;
+  // the compact path shades the samples of a list built from the weights; the tile paths skip 32-sample tiles of the flat order only when
+  // a mask, early termination or the weight threshold is switched on (otherwise every sample is shaded)
+  const bool compact = ego_render_forward_compacts(sc, N, S) != 0;
+  uint8_t* act = (!compact && (sc->occ || sc->term_eps > 0.f || sc->weight_thres >= 0.f)) ? (uint8_t*)(ws + p.act) : nullptr;
+  record_path(workspace, N, S, compact ? SHADED_LIVE : act ? SHADED_TILES : SHADED_ALL);
   if (act && (S & 31) != 0) {  // with whole tiles per ray the march writes every flag itself (0 or 1)
     const hipError_t me = hipMemsetAsync(act, 0, (size_t)(N * (int64_t)S / 32 + 1), (hipStream_t)stream);
     if (me != hipSuccess) return ego_fail((int)me, "render_forward: hipMemsetAsync failed: %s", hipGetErrorString(me));
@@ -83,10 +130,28 @@ int ego_render_forward(const ego_scene* sc, const ego_render_args* a, const floa
   // since the folded kernel loads a plane's basis fragments ahead of the next plane's taps (it has the registers for that, the two-launch
   // kernel does not) it is 3.5 % faster than ego_shade, 2.8 % at step level (round 5; before that it lost by 0.25 %).  EGO_RENDER_FOLD=0
   // keeps the two launches, =1 folds whenever the scene allows it.
+  if (compact) {
+    int32_t* live = (int32_t*)(ws + p.live);
+    int32_t* n_live = (int32_t*)(ws + p.nlive);
+    if ((e = ego_compact_live(ws + p.w, N, S, fmaxf(sc->weight_thres, 0.f), live, (int32_t*)(ws + p.cnt), (int32_t*)(ws + p.part), n_live, stream)))
+      return e;
+    if ((e = ego_shade_live(sc, rays, z, ws + p.crd, N, S, live, n_live, ws + p.rgb, stream))) return e;
+    return ego_composite(sc, rays, z, ws + p.w, ws + p.bg, ws + p.rgb, N, S, rgb_map, depth, bg_map, env_map, nullptr, stream);
+  }
   if (ego_render_forward_folds(sc, N, S))
     return ego_shade_composite(sc, rays, z, ws + p.crd, ws + p.w, ws + p.bg, N, S, act, rgb_map, depth, bg_map, env_map, stream);
   if ((e = ego_shade(sc, rays, z, ws + p.crd, N, S, ws + p.rgb, nullptr, act, stream))) return e;
   return ego_composite(sc, rays, z, ws + p.w, ws + p.bg, ws + p.rgb, N, S, rgb_map, depth, bg_map, env_map, nullptr, stream);
+}
+
+int ego_render_shaded_samples(int64_t N, const ego_render_args* args, const void* workspace, int64_t* out_dev, void* stream) {
+  EGO_TRACE("ego_render_shaded_samples");
+  EGO_REQUIRE(args && workspace && out_dev && N >= 1 && args->n_coarse >= 2, "render_shaded_samples: null argument, N < 1 or n_coarse < 2");
+  const Plan p = make_plan(N, args);
+  ShadeRecord r;
+  EGO_REQUIRE(find_path(workspace, &r) && r.N == N && r.S == p.S_out, "render_shaded_samples: no ego_render_forward of this N and sample count on this workspace");
+  const float* ws = (const float*)workspace;
+  return ego_shaded_count(r.mode, (const int32_t*)(ws + p.nlive), (const uint8_t*)(ws + p.act), N, p.S_out, out_dev, stream);
 }
 
 }  // extern "C"

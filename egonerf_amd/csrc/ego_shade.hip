@@ -440,6 +440,9 @@ struct ShadeArgs {
   float* env_map;         // [N][3] or null
   int64_t M;
   int32_t S;
+  // COMPACT (ego_shade_live): lane j of tile t shades sample live[32 t + j] of [N][S]; the tile count follows from *n_live (device)
+  const int32_t* live;
+  const int32_t* n_live;
 };
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -500,8 +503,9 @@ __device__ __forceinline__ void basis_mixed(const f32x4* __restrict__ BAS, int l
   basis_mfma(a, v, g != 0, fe);
 }
 
-template <int MODE>
+template <int MODE, bool COMPACT = false>
 __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
+  static_assert(!COMPACT || MODE == MODE_SHADE, "the live-sample list is an input of the shade only");
   __shared__ __attribute__((aligned(16))) float lds[(MODE == MODE_APP ? 0 : LDS_W_FLOATS) + (MODE == MODE_MLP ? 4 : LUT_MAX)];
   float* lut = lds + (MODE == MODE_APP ? 0 : LDS_W_FLOATS);
   if (MODE != MODE_APP) {
@@ -518,7 +522,8 @@ __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
   // waves w and w+4 share a SIMD and would otherwise run their gather and MFMA phases in lockstep (equal sharing
   // of the matrix pipe keeps them synchronised); a static priority for one of them staggers the phases
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-  const int64_t n_tiles = (A.M + 31) >> 5;
+  const int32_t n_live = COMPACT ? *A.n_live : 0;
+  const int64_t n_tiles = ((COMPACT ? (int64_t)n_live : A.M) + 31) >> 5;
   const f32x4* W1 = (const f32x4*)(lds + OFF_W1);
   const f32x4* W2 = (const f32x4*)(lds + OFF_W2);
   const f32x4* B1 = (const f32x4*)(lds + OFF_B1);
@@ -527,15 +532,16 @@ __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
   const f32x4* BAS = (const f32x4*)(A.packed + OFF_BASIS);
 
   for (int64_t tile = (int64_t)blockIdx.x * 8 + wave; tile < n_tiles; tile += (int64_t)gridDim.x * 8) {
-    if (MODE == MODE_SHADE && A.tile_active && !A.tile_active[tile]) continue;
+    if (MODE == MODE_SHADE && !COMPACT && A.tile_active && !A.tile_active[tile]) continue;
     // LDS weights are loop-invariant: without an opaque per-iteration index LICM hoists all 240
     // ds_read_b128 out of the tile loop and spills them to scratch
     int lw = lane;
     asm volatile("" : "+v"(lw));
     const int hw = lw >> 5;
     const int64_t m_raw = tile * 32 + j;
-    const bool valid = m_raw < A.M;
-    const int64_t m = valid ? m_raw : A.M - 1;
+    const bool valid = m_raw < (COMPACT ? (int64_t)n_live : A.M);
+    // COMPACT: the list entry (a lane past the end repeats the last live sample and writes nothing)
+    const int64_t m = COMPACT ? (int64_t)A.live[valid ? m_raw : n_live - 1] : valid ? m_raw : A.M - 1;
 
     f32x16 fe;  // basis output: register r holds feature 2r + h
     float vd0 = 0.f, vd1 = 0.f, vd2 = 0.f;
@@ -1320,10 +1326,14 @@ __device__ __forceinline__ void gather_basis_f16(const DevField& F, const VMTaps
 // tiles), keeps sum w rgb / sum w (lane half 0) and sum w z (lane half 1) per lane across the ray's tiles and finishes the pixel -
 // background, clamp, depth - itself; no per-sample colours are written and k_composite (12 us per 4096 x 512 launch: 25 MB of colours
 // written here, 42 MB read there) is not launched.
-template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false>
+// COMPACT: the tiles are cut from the live-sample list (ego_shade_live) instead of the flat [N][S] order: lane j of tile t shades sample
+// live[32 t + j], reads its coordinates at that index and its direction from ray live[..] / S, and writes its colour there.  Every lane's
+// result depends on its own sample only, so the colours are the bits the tile walk writes for the same samples.
+template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false, bool COMPACT = false>
 __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   constexpr bool P8 = PX == 1, P6 = PX == 2;
   static_assert(!FOLD || (MODE == MODE_SHADE && !DUMP), "compositing folds into the fused inference kernel only");
+  static_assert(!COMPACT || (MODE == MODE_SHADE && !DUMP && !FOLD), "the live-sample list is an input of the two-launch inference shade only");
   static_assert(!PX || (!DUMP && MODE != MODE_APP), "the fp8 / fp6 correction arithmetic exists for the inference MLP only");
   __shared__ __attribute__((aligned(16))) float lds[(MODE == MODE_APP ? 0 : LDS_W_FLOATS) + 4];
   const float* blob = A.packed + PACKED_FLOATS;  // the f16x3 half of the packed blob
@@ -1357,7 +1367,8 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   const int j = lane & 31, h = lane >> 5;
   // wave priority follows the phase: high while gathering (latency-bound: get the loads out), low in the MLP phase, whose MFMAs
   // fill the matrix pipe anyway - 0.9 % faster than the static priority of k_shade (no priority / static: measured, removed)
-  const int64_t n_tiles = (A.M + 31) >> 5;
+  const int32_t n_live = COMPACT ? *A.n_live : 0;
+  const int64_t n_tiles = ((COMPACT ? (int64_t)n_live : A.M) + 31) >> 5;
   const u32x4* W1 = (const u32x4*)(lds + OFF_W1);
   const u32x4* W2 = (const u32x4*)(lds + OFF_W2);
   const f32x4* B1 = (const f32x4*)(lds + OFF_B1);
@@ -1388,7 +1399,7 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
     {
       const int64_t t = wbase + (int64_t)lane;
       const bool in = t < seg1;
-      wmask = (MODE == MODE_SHADE && A.tile_active) ? __ballot(in && A.tile_active[in ? t : seg0] != 0) : __ballot(in);
+      wmask = (MODE == MODE_SHADE && !COMPACT && A.tile_active) ? __ballot(in && A.tile_active[in ? t : seg0] != 0) : __ballot(in);
     }
   while (wmask != 0ull) {
     const int64_t tile = wbase + (int64_t)__builtin_ctzll(wmask);
@@ -1398,8 +1409,9 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
     if (MODE != MODE_MLP) __builtin_amdgcn_s_setprio(2);
     const int hw = lw >> 5;
     const int64_t m_raw = tile * 32 + j;
-    const bool valid = m_raw < A.M;
-    const int64_t m = valid ? m_raw : A.M - 1;
+    const bool valid = m_raw < (COMPACT ? (int64_t)n_live : A.M);
+    // COMPACT: the list entry (a lane past the end repeats the last live sample and writes nothing)
+    const int64_t m = COMPACT ? (int64_t)A.live[valid ? m_raw : n_live - 1] : valid ? m_raw : A.M - 1;
     // FOLD: the sample's weight and distance travel while the tile is computed (fetched where they are used, their latency is exposed once per tile)
     float fold_w = 0.f, fold_z = 0.f;
     if (FOLD) { fold_w = A.comp_w[m]; fold_z = A.z[m]; }
@@ -1452,7 +1464,7 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
 #pragma unroll
         for (int rd = 0; rd < 2; ++rd) {
           const int64_t mt_raw = EGO_GATHER_TEAMS ? tile * 32 + 2 * ((lw >> 1) & 15) + rd : tile * 32 + (lw & 31);
-          const int64_t mt = mt_raw < A.M ? mt_raw : A.M - 1;
+          const int64_t mt = COMPACT ? (int64_t)A.live[mt_raw < n_live ? mt_raw : n_live - 1] : mt_raw < A.M ? mt_raw : A.M - 1;
           if (MODE == MODE_APP) {
             const float* p = A.c7n + mt * 7;
             ts[rd].g = (p[6] == 0.f) ? 0 : 1;
@@ -2052,6 +2064,38 @@ int ego_shade(const ego_scene* sc, const float* rays, const float* z, const floa
   else k_shade_h<MODE_SHADE><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
   return ego_launch_status("k_shade<SHADE>");
 }
+
+}  // extern "C"
+
+// ego_render_forward's compact path: ego_shade over the samples of the list live[*n_live] (csrc/ego_compact.hip) only; colours land at the
+// samples' [N][S] places, the others are not written.  The grid is sized for N S samples and the kernel deals the ceil(*n_live / 32) tiles.
+int ego_shade_live(const ego_scene* sc, const float* rays, const float* z, const float* coords, int64_t N, int32_t S, const int32_t* live,
+                   const int32_t* n_live, float* rgb, void* stream) {
+  EGO_TRACE("ego_shade_live");
+  EGO_REQUIRE(rays && z && coords && live && n_live && rgb && N >= 1 && S >= 1 && N * (int64_t)S < (1ll << 31),
+              "shade_live: null argument or N*S outside [1, 2^31)");
+  EGO_REQUIRE(sc && ego_shape_is_tuned(sc), "shade_live: tuned model shape only");
+  if (int e = check_shade_config(sc, "shade_live", true, true)) return e;
+  EGO_REQUIRE(sc->r_lut && sc->n_r_lut >= 2 && sc->n_r_lut <= LUT_MAX, "shade_live: r_lut missing or > 1024 entries");
+  ShadeArgs a{};
+  a.c = make_coords(*sc); a.F = make_field(sc->app); a.packed = sc->packed; a.rays = rays; a.z = z; a.coords = coords; a.out = rgb;
+  a.live = live; a.n_live = n_live;
+  a.M = N * (int64_t)S; a.S = S;
+  const unsigned grid = shade_grid(a.M);
+  if (sc->mlp_precision == EGO_PREC_F32) k_shade<MODE_SHADE, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+  else if (sc->app_f16) {
+    if (int e = check_app16(sc, "shade_live")) return e;
+    a.F = make_field(sc->app16);
+    if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, true, 1, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+    else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, true, 2, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+    else k_shade_h<MODE_SHADE, false, true, 0, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+  } else if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, false, 1, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+  else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, false, 2, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+  else k_shade_h<MODE_SHADE, false, false, 0, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
+  return ego_launch_status("k_shade<SHADE, live list>");
+}
+
+extern "C" {
 
 int ego_shade_composite(const ego_scene* sc, const float* rays, const float* z, const float* coords, const float* weight, const float* bg_weight,
                         int64_t N, int32_t S, const uint8_t* tile_active, float* rgb_map, float* depth, float* bg_map, float* env_map, void* stream) {

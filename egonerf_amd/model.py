@@ -979,6 +979,7 @@ class EgoNeRF(TensorBase):
                 pretrain_envmap=False, pivotal_sample_th=0.0, resampling=False, use_coarse_sample=True, interval_th=False,
                 jitter: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, need_alpha: bool = True,
                 marched_event: Optional["torch.cuda.Event"] = None):
+        self._last_render, self._last_shaded = None, None   # set again by a call that runs ego_render_forward
         out = self._forward(rays_chunk, is_train, ndc_ray, n_coarse, n_fine, exp_sampling, pretrain_envmap, resampling, use_coarse_sample,
                             jitter, u, need_alpha, marched_event)
         if marched_event is not None and not getattr(self, "_marched_recorded", False):
@@ -1065,7 +1066,27 @@ class EgoNeRF(TensorBase):
         env_map = torch.empty(N, 3, device=dev) if has_env else None
         _call("ego_render_forward", sc, C.byref(args), rays.data_ptr(), N, ws.data_ptr(), rgb_map.data_ptr(), depth.data_ptr(),
               _lib.ptr(alpha), _lib.ptr(bg_map), _lib.ptr(env_map), _lib.stream_handle())
+        if N:
+            self._last_render = (N, args, ws)   # for last_shaded_samples (the workspace holds the live count / tile flags)
         return rgb_map, depth, bg_map, env_map, alpha
+
+    @property
+    def last_shaded_samples(self) -> Optional[torch.Tensor]:
+        """How many samples the last forward sent through the appearance lookup and the MLP, as a 0-d int64 device tensor (no host
+        synchronisation; ego_render_shaded_samples): the live samples - weight > max(weight_thres, 0), tensorBase.py:480-487's app_mask - on
+        the compact path (include/egonerf_hip.h: ego_render_forward_compacts), 32 x the shaded tiles (at most N S) on the tile paths, N S
+        without skipping.  None when the last forward did not run ego_render_forward (training, envmap pre-training, the ray-0-distance
+        evaluation, N = 0).  Computed on first access from the workspace the forward keeps for it."""
+        last = getattr(self, "_last_render", None)
+        if last is None:
+            return None
+        if self._last_shaded is None:
+            N, args, ws = last
+            with torch.cuda.device(ws.device):
+                out = torch.empty((), dtype=torch.int64, device=ws.device)
+                _call("ego_render_shaded_samples", N, C.byref(args), ws.data_ptr(), out.data_ptr(), _lib.stream_handle())
+            self._last_shaded = out
+        return self._last_shaded
 
     def _forward_eval_ray0_distances(self, rays, z_pos, n_coarse, n_fine, resampling, use_coarse_sample, need_alpha):
         """Eval with exp_sampling=False and rays whose aabb entry distances differ (rays starting outside the box).  The reference

@@ -305,6 +305,15 @@ int ego_shade_composite(const ego_scene* sc, const float* rays, const float* z, 
  * whenever the scene qualifies.  No device work. */
 int32_t ego_render_forward_folds(const ego_scene* sc, int64_t N, int32_t S);
 
+/* 1 iff ego_render_forward shades only the LIVE samples of N rays x S samples of this scene - weight > max(weight_thres, 0), the
+ * app_mask of TensorBase.forward (models/tensorBase.py:480-487), which runs the appearance lookup and the MLP on coords_sampled[app_mask]
+ * only - instead of the 32-sample tiles of the flat [N][S] order that hold one: it builds the list of those samples (ray-major, no
+ * atomics, no host synchronisation, inside the workspace), shades tiles cut from the list and composites with ego_composite; same bits.
+ * Taken for the tuned shape with weight_thres >= 0 when the call can leave dead samples INSIDE rays (an occupancy mask, or
+ * weight_thres > 0); with the exact skip alone the dead samples are ray tails, which the tile skip already passes over.  Environment:
+ * EGO_RENDER_COMPACT=0 never compacts, =1 compacts whenever the shape is the tuned one and weight_thres >= 0.  No device work. */
+int32_t ego_render_forward_compacts(const ego_scene* sc, int64_t N, int32_t S);
+
 /* acc, rgb_map (+ envmap background), clamp, depth (+ (1-acc)*d_z quirk, EgoNeRF.py:598).
  * Outputs rgb_map [N][3], depth [N]; bg_map/env_map [N][3] written only when sc->envmap != NULL (may be NULL);
  * rgb_raw [N][3] optional = rgb_map before the clamp (the backward pass needs the clamp mask). */
@@ -567,6 +576,12 @@ typedef struct ego_render_args {
 int64_t ego_render_workspace_bytes(int64_t N, const ego_render_args* args);
 int ego_render_forward(const ego_scene* sc, const ego_render_args* args, const float* rays, int64_t N, void* workspace,
                        float* rgb_map, float* depth, float* alpha, float* bg_map, float* env_map, void* stream);
+
+/* How many samples the last ego_render_forward of N rays with these args on `workspace` sent through the appearance lookup and the
+ * MLP: the live count on the compact path (ego_render_forward_compacts; the size of tensorBase.py:480-487's app_mask), 32 x the
+ * shaded tiles, at most N S, on the tile paths, N S without skipping.  Written to *out_dev (device int64) on `stream` by one launch,
+ * no host synchronisation.  EGO_E_BADARG if no ego_render_forward of this N and sample count has run on `workspace` in this process. */
+int ego_render_shaded_samples(int64_t N, const ego_render_args* args, const void* workspace, int64_t* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
