@@ -67,6 +67,14 @@ class ShadeDump(C.Structure):
     _fields_ = [("x", C.c_void_p), ("h1", C.c_void_p), ("h2", C.c_void_p), ("v", C.c_void_p), ("relu_bits", C.c_void_p), ("fe", C.c_void_p)]
 
 
+class RayBankStruct(C.Structure):
+    """ego_ray_bank: K poses + K RGBA images on the device and the ROI window (egonerf_amd.data.RayBank fills it)."""
+    _fields_ = [("poses", C.c_void_p), ("images", C.c_void_p), ("K", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("r0", C.c_int32), ("n_rows", C.c_int32), ("c0", C.c_int32), ("n_cols", C.c_int32), ("normalize", C.c_int32)]
+
+
+BATCH_SIMPLE, BATCH_THETA = 0, 1   # EGO_BATCH_* of include/egonerf_hip.h
+
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SP = C.POINTER(Scene)
 
@@ -86,6 +94,8 @@ PROTOTYPES = {
     "ego_packed_floats_scene": (I64, [SP]),
     "ego_sample_ray_exp": (C.c_int, [P, P, P, F32, I64, I32, P, P, P]),
     "ego_erp_rays": (C.c_int, [I32, I32, I32, I32, C.POINTER(C.c_float), I32, P, P]),
+    "ego_ray_batch_gather": (C.c_int, [C.POINTER(RayBankStruct), P, I64, P, P, P]),
+    "ego_ray_batch_sample": (C.c_int, [C.POINTER(RayBankStruct), I32, C.c_uint64, P, P, I64, P, P, P, P]),
     "ego_copy_out": (C.c_int, [I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), I32, P]),
     "ego_density_feature_backward_workspace_bytes": (I64, [SP, I64, I32]),
     "ego_density_feature_backward": (C.c_int, [SP, P, I64, I32, P, C.POINTER(VmGrad), P, I64, P]),
@@ -182,7 +192,7 @@ def load() -> C.CDLL:
     if why and not os.environ.get("EGO_ALLOW_STALE_LIB"):
         raise RuntimeError(f"{LIB} cannot be matched to the sources next to it: {why}; rebuild it (`python -m egonerf_amd.build`) "
                            "or set EGO_ALLOW_STALE_LIB=1 for an experiment build")
-    for which, struct in ((0, Scene), (1, RenderArgs), (2, VmField), (3, AdamTensor), (4, ShadeDump)):
+    for which, struct in ((0, Scene), (1, RenderArgs), (2, VmField), (3, AdamTensor), (4, ShadeDump), (5, RayBankStruct)):
         if lib.ego_sizeof(which) != C.sizeof(struct):
             raise RuntimeError(f"ABI mismatch: struct {struct.__name__} is {C.sizeof(struct)} B here, "
                                f"{lib.ego_sizeof(which)} B in {LIB}")

@@ -278,6 +278,25 @@ __device__ __forceinline__ void envmap_lookup(const float* __restrict__ em, int 
   }
 }
 
+// Equirectangular camera ray of pixel (row, col) of an H x W panorama: get_ray_directions_360 (dataLoader/ray_utils.py:24-40),
+// the datasets' normalisation and get_rays (:85-113).  m = camera-to-world pose, 3x4 row-major (kernel argument or device memory);
+// o[6] = origin, direction.  ONE body for ego_erp_rays (csrc/ego_ops.hip) and the ray-bank gather (csrc/ego_batch.hip): a gathered ray
+// has the bits of the corresponding row of ego_erp_rays.
+__device__ __forceinline__ void erp_ray(int H, int W, int row, int col, const float* m, int normalize, float* o) {
+  const float i = (float)col + 0.5f, j = (float)row + 0.5f;
+  const float phi = __fmul_rn(__fsub_rn(1.f, __fdiv_rn(__fmul_rn(2.f, i), (float)W)), 3.14159265358979323846f);
+  const float theta = __fdiv_rn(__fmul_rn(__fsub_rn(1.f, __fdiv_rn(__fmul_rn(2.f, j), (float)H)), 3.14159265358979323846f), 2.f);
+  const float ct = cosf(theta);
+  float d0 = -ct * sinf(phi), d1 = sinf(theta), d2 = -ct * cosf(phi);
+  if (normalize) {  // directions / torch.norm(directions, dim=-1): sqrt of the sum of squares, then three divisions
+    const float n = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+    d0 = __fdiv_rn(d0, n); d1 = __fdiv_rn(d1, n); d2 = __fdiv_rn(d2, n);
+  }
+  o[0] = m[3]; o[1] = m[7]; o[2] = m[11];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) o[3 + r] = (d0 * m[4 * r] + d1 * m[4 * r + 1]) + d2 * m[4 * r + 2];
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);

@@ -987,19 +987,7 @@ __global__ void k_erp_rays(int H, int W, int row0, int n_rows, Pose34 c2w, int n
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)n_rows * W) return;
   const int col = (int)(idx % W), row = row0 + (int)(idx / W);
-  const float i = (float)col + 0.5f, j = (float)row + 0.5f;
-  const float phi = __fmul_rn(__fsub_rn(1.f, __fdiv_rn(__fmul_rn(2.f, i), (float)W)), 3.14159265358979323846f);
-  const float theta = __fdiv_rn(__fmul_rn(__fsub_rn(1.f, __fdiv_rn(__fmul_rn(2.f, j), (float)H)), 3.14159265358979323846f), 2.f);
-  const float ct = cosf(theta);
-  float d0 = -ct * sinf(phi), d1 = sinf(theta), d2 = -ct * cosf(phi);
-  if (normalize) {  // directions / torch.norm(directions, dim=-1): sqrt of the sum of squares, then three divisions
-    const float n = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
-    d0 = __fdiv_rn(d0, n); d1 = __fdiv_rn(d1, n); d2 = __fdiv_rn(d2, n);
-  }
-  float* o = rays + idx * 6;
-  o[0] = c2w.m[3]; o[1] = c2w.m[7]; o[2] = c2w.m[11];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) o[3 + r] = (d0 * c2w.m[4 * r] + d1 * c2w.m[4 * r + 1]) + d2 * c2w.m[4 * r + 2];
+  erp_ray(H, W, row, col, c2w.m, normalize, rays + idx * 6);   // ego_device.h: shared with the ray-bank gather (csrc/ego_batch.hip)
 }
 
 // =============================================================================================

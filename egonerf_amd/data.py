@@ -4,15 +4,110 @@
 Same attribute surface as the reference's dataset object where the render / training loop reads it: `poses [K,4,4]`, `img_wh`,
 `near_far`, `center`, `scene_bbox [2,3]` (dataset_omniblender.py:22-32: camera-position centre +- (half diagonal of the camera
 positions' extent + far)), `radius`, `all_rays`, `all_rgbs`, `image_paths`, `white_bg`, `indoor`.
+
+`RayBank` is the device-resident alternative to `all_rays` / `all_rgbs`: the poses and the 8-bit images stay on the device and a row
+of either array is computed when it is asked for (ego_ray_batch_gather), bit-equal to the materialised one.
 """
 from __future__ import annotations
 
+import ctypes as C
 import json
 import os
 from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
+
+from . import _lib
+
+
+class RayBank:
+    """K poses + K uint8 images on the device, standing for the reference's `all_rays [K*h*w, 6]` / `all_rgbs [K*h*w, 3]`
+    (dataset_omniblender.py:81-89) at 4 B per pixel + 48 B per image instead of 36 B per pixel.
+
+    poses [K,4,4] or [K,3,4] camera-to-world; images_u8 [K,H,W,3|4] uint8 (array or tensor; RGB is stored as RGBA with A = 255);
+    img_wh = (W, H); roi = (h0, h1, w0, w1) fractions as in get_rays (ray_utils.py:100-103).  Index space = the layout of
+    `all_rays`: idx = img * (n_rows * n_cols) + row * n_cols + col, (row, col) inside the ROI window.  With a ROI the colours are those
+    of the window's pixels, i.e. the rows of the per-image `all_rgbs` that belong to the rays (`all_rgbs` itself keeps every pixel
+    of the image, as the reference's does).
+
+    A bank on device="cpu" holds the host state only (shapes, window, struct): gather / sampling need the HIP device."""
+
+    def __init__(self, poses, images_u8, img_wh: Sequence[int], roi: Sequence[float] = (0, 1, 0, 1), normalize: bool = True, device="cuda"):
+        W, H = int(img_wh[0]), int(img_wh[1])
+        poses = torch.as_tensor(np.asarray(poses) if not torch.is_tensor(poses) else poses).float()
+        if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+            raise ValueError(f"RayBank: poses must be [K,4,4] or [K,3,4], got {tuple(poses.shape)}")
+        img = images_u8 if torch.is_tensor(images_u8) else torch.from_numpy(np.ascontiguousarray(images_u8))
+        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] not in (3, 4):
+            raise ValueError(f"RayBank: images must be uint8 [K,H,W,3|4], got {img.dtype} {tuple(img.shape)}")
+        K = poses.shape[0]
+        if K < 1 or tuple(img.shape[:3]) != (K, H, W):
+            raise ValueError(f"RayBank: {K} poses and img_wh {(W, H)} do not match images {tuple(img.shape)}")
+        if img.shape[-1] == 3:
+            img = torch.cat([img, torch.full_like(img[..., :1], 255)], dim=-1)
+        h0, h1, w0, w1 = roi
+        r0, r1, c0, c1 = int(h0 * H), int(h1 * H), int(w0 * W), int(w1 * W)     # ray_utils.py:100-103
+        if not (0 <= r0 < r1 <= H and 0 <= c0 < c1 <= W):
+            raise ValueError(f"RayBank: roi {list(roi)} selects no pixel of a {H} x {W} image")
+        self.device = torch.device(device)
+        self.poses = poses[:, :3, :].contiguous().to(self.device)
+        self.images = img.contiguous().to(self.device)
+        self.K, self.H, self.W = K, H, W
+        self.r0, self.n_rows, self.c0, self.n_cols = r0, r1 - r0, c0, c1 - c0
+        self.roi, self.normalize = list(roi), bool(normalize)
+        self.total = K * self.n_rows * self.n_cols
+        self.struct = _lib.RayBankStruct(self.poses.data_ptr(), self.images.data_ptr(), K, H, W, self.r0, self.n_rows, self.c0, self.n_cols,
+                                         int(self.normalize))
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes the bank holds (on its device): K * H * W * 4 for the images + K * 48 for the poses."""
+        return self.images.numel() * self.images.element_size() + self.poses.numel() * self.poses.element_size()
+
+    def __len__(self) -> int:
+        return self.total
+
+    def gather(self, idx: torch.Tensor):
+        """(rays [B,6], rgb [B,3]) = (all_rays[idx], all_rgbs[idx]) of the materialised arrays, bit for bit.  idx: int64 on the bank's
+        device, every entry in [0, total) (not checked - that would synchronise; a row with an index outside comes back as NaN)."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        rays = torch.empty(idx.shape[0], 6, device=self.device, dtype=torch.float32)
+        rgb = torch.empty(idx.shape[0], 3, device=self.device, dtype=torch.float32)
+        ray_batch_gather(idx, rays, rgb, self)
+        return rays, rgb
+
+
+def _need_hip(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} needs a HIP device (no CPU fallback exists); the bank lives on {t.device}")
+
+
+def ray_batch_gather(idx: torch.Tensor, rays: Optional[torch.Tensor], rgb: Optional[torch.Tensor], bank: RayBank) -> None:
+    """ego_ray_batch_gather into caller-owned buffers (contiguous float32 [B,6] / [B,3], either may be None)."""
+    _need_hip(idx, "RayBank.gather")
+    _gather(idx, rays, rgb, bank)
+
+
+def ray_batch_sample(idx: torch.Tensor, rays: Optional[torch.Tensor], rgb: Optional[torch.Tensor], bank: RayBank, mode: int, seed: int,
+                     counter: torch.Tensor, row_cdf: Optional[torch.Tensor]) -> None:
+    """ego_ray_batch_sample into caller-owned buffers: idx [B] int64, rays [B,6] / rgb [B,3] float32 or None; counter = int64 device
+    scalar holding the iteration to draw (read by the kernel, so a captured launch follows it)."""
+    _need_hip(idx, "ray batch sampling")
+    _sample(idx, rays, rgb, bank, mode, seed, counter, row_cdf)
+
+
+@_lib.device_guard
+def _gather(idx, rays, rgb, bank):
+    _lib.check(_lib.load().ego_ray_batch_gather(C.byref(bank.struct), idx.data_ptr(), idx.shape[0], _lib.ptr(rays), _lib.ptr(rgb),
+                                                _lib.stream_handle()), "ego_ray_batch_gather")
+
+
+@_lib.device_guard
+def _sample(idx, rays, rgb, bank, mode, seed, counter, row_cdf):
+    _lib.check(_lib.load().ego_ray_batch_sample(C.byref(bank.struct), int(mode), int(seed), counter.data_ptr(), _lib.ptr(row_cdf),
+                                                idx.shape[0], idx.data_ptr(), _lib.ptr(rays), _lib.ptr(rgb), _lib.stream_handle()),
+               "ego_ray_batch_sample")
 
 
 class OmniBlenderDataset:
@@ -77,6 +172,25 @@ class OmniBlenderDataset:
         if t.shape[-1] == 4:
             t = t[:, :3] * t[:, -1:] + (1 - t[:, -1:])
         return t
+
+    def _load_image_u8(self, path: str) -> np.ndarray:
+        """The same PIL image as `_load_image` (after the LANCZOS resize when downsampling), kept as uint8 [h, w, 3|4]."""
+        from PIL import Image
+        img = Image.open(path)
+        if self.downsample != 1.0:
+            img = img.resize(self.img_wh, Image.LANCZOS)
+        a = np.array(img)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] not in (3, 4):
+            raise ValueError(f"ray_bank: {path} is not an 8-bit RGB / RGBA image (array {a.dtype} {a.shape})")
+        return a
+
+    def ray_bank(self, device=None) -> RayBank:
+        """The training rays and colours as a device-resident `RayBank` (poses + uint8 images read from disk here): what
+        `all_rays[idx]` / `all_rgbs[idx]` return, without materialising either array."""
+        if self.is_stack:
+            raise ValueError("ray_bank: the flat ray index space is that of is_stack=False")
+        imgs = np.stack([self._load_image_u8(p) for p in self.image_paths], 0)
+        return RayBank(self.poses, imgs, self.img_wh, roi=self.roi, normalize=True, device=device or self.device)
 
     def rays(self, idx: int, device=None) -> torch.Tensor:
         """[h*w, 6] rays of image `idx`: get_ray_directions_360 + normalisation + get_rays(roi) (dataset_omniblender.py:41-43,79),

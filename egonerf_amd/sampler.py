@@ -1,5 +1,7 @@
 """Training ray-index samplers: mirror of sampler.py:4-38 (CPU, numpy legacy RNG so that
-np.random.seed(20221028) (train.py:413) reproduces the reference's index stream)."""
+np.random.seed(20221028) (train.py:413) reproduces the reference's index stream), and their device-resident counterparts
+(`DeviceSimpleSampler`, `DeviceThetaImportanceSampler`): the same two sampling rules drawn by a counter-based generator inside
+one kernel launch together with the batch's rays and colours (ego_ray_batch_sample) - another index stream, no host work."""
 import numpy as np
 import torch
 
@@ -42,3 +44,75 @@ class ThetaImportanceSampler:
         col = np.random.choice(self.W, self.batch)
         row = np.random.choice(self.H, self.batch, p=self.weight)
         return img * self.W * self.H + (col + row * self.W)
+
+
+class _DeviceSampler:
+    """Indices, rays and colours of training batch number `counter` from a `RayBank` (egonerf_amd.data), drawn on the device: every
+    index is a pure function of (seed, counter, lane).  `counter` is an int64 device scalar the kernel reads, so a launch captured
+    into a hipGraph draws a new batch at every replay once the counter is advanced inside the graph (GraphedTrainStep does)."""
+    mode = None
+
+    def __init__(self, bank, batch, seed=0):
+        self.bank, self.batch = bank, int(batch)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        if self.batch < 1:
+            raise ValueError("batch must be >= 1")
+        self.counter = torch.zeros((), dtype=torch.int64, device=bank.device)
+        self.cdf = None
+
+    def sample_into(self, idx, rays, rgb, counter=None):
+        """One launch: idx [batch] int64 and (unless None) rays [batch,6], rgb [batch,3] for iteration `counter` (default: the
+        sampler's own device counter, which is NOT advanced here)."""
+        from .data import ray_batch_sample
+        ray_batch_sample(idx, rays, rgb, self.bank, self.mode, self.seed, self.counter if counter is None else counter, self.cdf)
+
+    def next_batch(self):
+        """(idx, rays, rgb) of the current iteration; advances the counter on the device (no synchronisation)."""
+        dev = self.bank.device
+        idx = torch.empty(self.batch, dtype=torch.int64, device=dev)
+        rays, rgb = torch.empty(self.batch, 6, device=dev), torch.empty(self.batch, 3, device=dev)
+        self.sample_into(idx, rays, rgb)
+        self.counter.add_(1)
+        return idx, rays, rgb
+
+    def indices_at(self, counter: int) -> torch.Tensor:
+        """The indices iteration `counter` draws (pure: the sampler's own counter is untouched)."""
+        dev = self.bank.device
+        idx = torch.empty(self.batch, dtype=torch.int64, device=dev)
+        self.sample_into(idx, None, None, torch.full((), int(counter), dtype=torch.int64, device=dev))
+        return idx
+
+    def seek(self, counter: int) -> None:
+        """Positions the device counter (resuming a run at iteration `counter`)."""
+        self.counter.fill_(int(counter))
+
+
+class DeviceSimpleSampler(_DeviceSampler):
+    """SimpleSampler's rule (sampler.py:4-16) - permutation epochs of floor(total / batch) batches, the tail of each permutation
+    dropped - without a permutation in memory: position -> index through a keyed bijection of [0, total) (Feistel network with
+    cycle-walking, keys from (seed, epoch))."""
+    mode = 0   # EGO_BATCH_SIMPLE
+
+    def __init__(self, bank, batch, seed=0):
+        super().__init__(bank, batch, seed)
+        if bank.total < 2 * self.batch:
+            raise ValueError(f"DeviceSimpleSampler: {bank.total} rays do not hold two batches of {self.batch}")
+        self.batches_per_epoch = bank.total // self.batch
+
+
+class DeviceThetaImportanceSampler(_DeviceSampler):
+    """ThetaImportanceSampler's rule (sampler.py:19-38): image and column uniform, row by inverse CDF of cos(latitude) * lambda + 1
+    over the bank's ROI rows.  The weights are ThetaImportanceSampler.get_weight's; the table is their float32 cumulative sum with
+    the last entry 1."""
+    mode = 1   # EGO_BATCH_THETA
+
+    def __init__(self, theta_importance_lambda, bank, batch, seed=0):
+        super().__init__(bank, batch, seed)
+        host = ThetaImportanceSampler(theta_importance_lambda, bank.K, (bank.W, bank.H), self.batch, bank.roi)
+        if len(host.weight) != bank.n_rows:
+            raise ValueError("DeviceThetaImportanceSampler: the roi rows of the weights and of the bank differ")
+        self.weight = host.weight
+        cdf = np.cumsum(host.weight).astype(np.float32)
+        cdf[-1] = 1.0
+        self.cdf_host = cdf
+        self.cdf = torch.from_numpy(cdf).to(bank.device)

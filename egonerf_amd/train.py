@@ -582,12 +582,31 @@ class GraphedTrainStep:
     iteration and are gated on iter_ignore_TV / iter_ignore_entropy) must not be Python floats - a float is frozen into the graph at
     capture.  A `loss_fn` whose fourth parameter is named `sched` / `schedule` (or any loss_fn with `schedule_aware=True`) receives `self.schedule` (a TrainSchedule: device-side iteration counter advanced
     inside the graph) and writes e.g. `sched.decayed(TV_weight_density, lr_factor, active_before=iter_ignore_TV) * model.TV_loss_density(tv)`;
-    tests/test_hip_train_graph.py::test_graphed_step_with_decaying_regulariser_weights pins that against the eager loop."""
+    tests/test_hip_train_graph.py::test_graphed_step_with_decaying_regulariser_weights pins that against the eager loop.
 
-    def __init__(self, model, optimizer, rays, target, render_kwargs, loss_fn=None, warmup=3, noise_fn=None, start_iteration=0,
-                 schedule_aware=None):
+    `batch_source` (a DeviceSimpleSampler / DeviceThetaImportanceSampler of egonerf_amd.sampler over a RayBank): the batch is drawn
+    INSIDE the graph - the iteration starts with the source's one launch writing indices, rays and colours into the static buffers
+    `self.idx` / `self.rays` / `self.target`, and the source's device counter is advanced next to `schedule.it` - so `rays` / `target`
+    are omitted, `step()` takes no arguments and nothing crosses the host link per iteration.  `start_iteration` positions the source's
+    counter as well: iteration k of a resumed run draws `batch_source.indices_at(k)`."""
+
+    def __init__(self, model, optimizer, rays=None, target=None, render_kwargs=None, loss_fn=None, warmup=3, noise_fn=None, start_iteration=0,
+                 schedule_aware=None, batch_source=None):
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs FusedAdam(capturable=True): the step count and lr schedule must live on the device")
+        if render_kwargs is None:
+            raise ValueError("GraphedTrainStep needs render_kwargs")
+        self.source = batch_source
+        if batch_source is not None:
+            if rays is not None or target is not None:
+                raise ValueError("GraphedTrainStep: with a batch_source the batches are drawn on the device; pass no rays / target")
+            dev0 = batch_source.bank.device
+            rays = torch.empty(batch_source.batch, 6, device=dev0, dtype=torch.float32)
+            target = torch.empty(batch_source.batch, 3, device=dev0, dtype=torch.float32)
+            self.idx = torch.empty(batch_source.batch, device=dev0, dtype=torch.int64)
+            batch_source.seek(start_iteration)
+        elif rays is None or target is None:
+            raise ValueError("GraphedTrainStep needs an example batch (rays, target) or a batch_source")
         self.model, self.opt, self.kw = model, optimizer, dict(render_kwargs)
         self.loss_fn = loss_fn or (lambda rgb, tgt, alpha: torch.mean((rgb - tgt) ** 2))
         # Explicit opt-in, not arity sniffing (ADVICE r04: a fourth parameter like reduction="mean" must not receive the schedule, a
@@ -621,6 +640,8 @@ class GraphedTrainStep:
         N = self.rays.shape[0]
         dev = self.rays.device
         kw = self.kw
+        if self.source is not None:   # this iteration's batch, drawn from the source's device counter straight into the static inputs
+            self.source.sample_into(self.idx, self.rays, self.target)
         # the is_train noise comes from the device generator (graph-safe: every replay draws new numbers)
         jitter = self.noise_fn(N, kw["n_coarse"], dev)
         u = self.noise_fn(N, kw["n_fine"], dev) if kw.get("resampling") else None
@@ -632,11 +653,19 @@ class GraphedTrainStep:
         if kw.get("resampling"):
             self.model.update_coarse_sigma_grid()  # train.py:356-357
         self.schedule.it.add_(1.0)   # inside the graph: the next replay sees the next iteration index
+        if self.source is not None:
+            self.source.counter.add_(1)
         return loss.detach()
 
-    def __call__(self, rays, target):
-        self.rays.copy_(rays, non_blocking=True)
-        self.target.copy_(target, non_blocking=True)
+    def __call__(self, rays=None, target=None):
+        if self.source is not None:
+            if rays is not None or target is not None:
+                raise ValueError("this GraphedTrainStep draws its batches from its batch_source inside the graph: call step() without arguments")
+        elif rays is None or target is None:
+            raise ValueError("this GraphedTrainStep was built without a batch_source: call step(rays, target)")
+        else:
+            self.rays.copy_(rays, non_blocking=True)
+            self.target.copy_(target, non_blocking=True)
         self.graph.replay()
         self.iterations += 1
         # the replayed optimiser wrote the parameters through raw pointers: tell autograd and the model's packed-weight cache

@@ -10,6 +10,8 @@
  *
  * Reference interface replaced by each entry point (paths relative to the reference repo):
  *   ego_erp_rays            get_ray_directions_360 + get_rays      dataLoader/ray_utils.py:24-40, :85-113
+ *   ego_ray_batch_gather    allrays[ids], allrgbs[ids]            train.py:247-248, dataLoader/dataset_omniblender.py:71-84
+ *   ego_ray_batch_sample    SimpleSampler / ThetaImportanceSampler.nextids   sampler.py:4-38 (device generator, not numpy's stream)
  *   ego_sample_ray_exp      EgoNeRF.sample_ray_exp                models/EgoNeRF.py:56-87
  *   ego_from_cartesian      YinYangSphericalCoords.from_cartesian  models/coordinates.py:468-498
  *   ego_normalize_coord     YinYangSphericalCoords.normalize_coord models/coordinates.py:442-466 (+ :110-131)
@@ -156,7 +158,7 @@ int64_t ego_packed_floats_scene(const ego_scene* sc);
 
 int ego_abi_version(void);
 const char* ego_last_error(void);
-/* sizeof the ABI structs as compiled (0 ego_scene, 1 ego_render_args, 2 ego_vm_field, 3 ego_adam_tensor, 4 ego_shade_dump): lets a foreign-
+/* sizeof the ABI structs as compiled (0 ego_scene, 1 ego_render_args, 2 ego_vm_field, 3 ego_adam_tensor, 4 ego_shade_dump, 5 ego_ray_bank): lets a foreign-
  * language binding verify its struct mirrors at load time */
 int64_t ego_sizeof(int32_t which);
 
@@ -182,6 +184,41 @@ int ego_sample_ray_exp(const float* rays, const float* r_sched, const float* jit
  * dataset_omniblender.py:42-43).  rays [n_rows*W][6] dev. */
 int ego_erp_rays(int32_t H, int32_t W, int32_t row0, int32_t n_rows, const float* c2w, int32_t normalize, float* rays,
                  void* stream);
+
+/* ---- device-resident training batches (csrc/ego_batch.hip; append-only additions, EGO_ABI_VERSION stays 17: no existing symbol,
+ * struct or argument list changed) ----
+ * A ray bank is what train.py:247-248 indexes as allrays[ids] / allrgbs[ids], kept as its sources instead of materialised: K poses and K
+ * 8-bit RGBA images (a 3-channel image is stored with A = 255) of H x W pixels, and the ROI window of get_rays (dataLoader/ray_utils.py:
+ * 100-103: rows [r0, r0 + n_rows), columns [c0, c0 + n_cols)).  Ray index space = the layout of the reference's all_rays:
+ * idx = img * (n_rows * n_cols) + row * n_cols + col with (row, col) counted inside the window; total = K * n_rows * n_cols. */
+typedef struct ego_ray_bank {
+  const float* poses;    /* dev [K][3][4] camera-to-world, row-major */
+  const uint8_t* images; /* dev [K][H][W][4] RGBA, 4-byte aligned; may be NULL when no colours are asked for */
+  int32_t K, H, W;       /* images, full image size */
+  int32_t r0, n_rows, c0, n_cols;
+  int32_t normalize;     /* as ego_erp_rays */
+} ego_ray_bank;
+
+/* allrays[idx], allrgbs[idx] of train.py:247-248 without the arrays: idx [B] int64 dev -> rays [B][6] (bit-equal to the rows ego_erp_rays
+ * writes for that pose and pixel), rgb [B][3] = the pixel's u8 / 255 blended on white, rgb * a + (1 - a), each operation rounded on its own
+ * (dataLoader/dataset_omniblender.py:71-81; with a = 1 exactly u8 / 255).  rays or rgb may be NULL (not written).  The entry point cannot
+ * see device values: 0 <= idx[i] < total is the caller's contract; a row whose index is outside reads nothing and is filled with NaN.
+ * B == 0 is a no-op. */
+int ego_ray_batch_gather(const ego_ray_bank* bank, const int64_t* idx, int64_t B, float* rays, float* rgb, void* stream);
+
+/* sampler.nextids() of train.py:247 (sampler.py:4-38) on the device: fills idx [B] (int64 dev) for iteration *counter (int64 dev, read by the
+ * kernel: a replayed hipGraph draws a new batch whenever the counter has been advanced) and, where rays / rgb are not NULL, gathers them in the
+ * same launch.  Every index is a pure function of (seed, *counter, lane) through Philox4x32-10 - NOT numpy's legacy stream.
+ * EGO_BATCH_SIMPLE (SimpleSampler, sampler.py:4-16): permutation epochs of floor(total / B) batches (the tail of a permutation is dropped as
+ * there), epoch = *counter / that, position p = (*counter % that) * B + lane sent through a keyed bijection of [0, total): a six-round
+ * balanced Feistel network over the smallest even number of bits covering total, cycle-walked back into range, round keys = Philox(seed,
+ * epoch); no permutation is materialised.  Needs total >= 2 B.
+ * EGO_BATCH_THETA (ThetaImportanceSampler, sampler.py:19-38): image uniform in [0, K), column uniform in [0, n_cols), row by inverse CDF:
+ * row_cdf [n_rows] float32 dev, non-decreasing, last entry 1 (the cumulative sum of the host-built weights cos(lat) * lambda + 1), row =
+ * first entry > u for a 24-bit uniform u. */
+enum { EGO_BATCH_SIMPLE = 0, EGO_BATCH_THETA = 1 };
+int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, const int64_t* counter, const float* row_cdf, int64_t B,
+                         int64_t* idx, float* rays, float* rgb, void* stream);
 
 int ego_from_cartesian(const ego_scene* sc, const float* xyz, int64_t M, float* c7, void* stream);
 int ego_normalize_coord(const ego_scene* sc, const float* c7, int64_t M, float* c7n, void* stream);
