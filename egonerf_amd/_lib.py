@@ -54,8 +54,23 @@ class RenderArgs(C.Structure):
                 ("u", C.c_void_p), ("near_", C.c_float), ("reserved", C.c_int32), ("z_coarse", C.c_void_p), ("marched", C.c_void_p)]
 
 
+def sample_count(n_coarse: int, n_fine: int, resampling: bool, use_coarse_sample: bool) -> int:
+    """Samples per ray of a render with these RenderArgs: the merged list after resampling (EgoNeRF.py:534-541), else the first pass."""
+    return (n_coarse + n_fine if use_coarse_sample else n_fine) if resampling else n_coarse
+
+
 class VmGrad(C.Structure):
     _fields_ = [("plane", (C.c_void_p * 3) * 2), ("line", (C.c_void_p * 3) * 2)]
+
+
+def grad_struct(tensors) -> VmGrad:
+    """tensors: [plane_yin x3, line_yin x3, plane_yang x3, line_yang x3] gradient tables (channel-last memory)."""
+    g = VmGrad()
+    for gi in range(2):
+        for i in range(3):
+            g.plane[gi][i] = tensors[gi * 6 + i].data_ptr()
+            g.line[gi][i] = tensors[gi * 6 + 3 + i].data_ptr()
+    return g
 
 
 class AdamTensor(C.Structure):
@@ -252,6 +267,47 @@ def stream_handle() -> int:
     """Raw hipStream_t of torch's current stream on the CURRENT device; entry points run under `device_guard`, which makes
     the device of their tensors current first."""
     return torch.cuda.current_stream().cuda_stream
+
+
+_SIDE_STREAMS = {}
+
+
+def side_stream(device) -> "torch.cuda.Stream":
+    """The one side stream of `device` (created on first use)."""
+    key = torch.device(device).index
+    if key not in _SIDE_STREAMS:
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
+    return _SIDE_STREAMS[key]
+
+
+class SideStream:
+    """The side-stream protocol in one place.  `run` forks: the side stream waits for everything queued on the main
+    stream so far, then the call is queued on it.  `join` makes the main stream wait for the side stream.  Every buffer the side stream
+    touches must stay referenced until the main stream has joined: a tensor freed earlier goes back to the main stream's allocator pool
+    and the next main-stream allocation may overwrite it while the side stream still uses it (the intermittently wrong appearance
+    gradient of the first attempt).  So the backward joins in a `finally`: whatever happens in between (a failing `check`
+    raises), the main stream has waited before the caller's locals die.  What is left in flight without a join (the forward's sort) is
+    handed to `leave_in_flight`.  Without a side stream (SIDE_STREAM_SCATTER = False) every call runs in line on the current stream."""
+
+    def __init__(self, side: "torch.cuda.Stream | None", device):
+        self.side, self.main = side, torch.cuda.current_stream(device)
+
+    def run(self, call) -> None:
+        """call(stream handle), ordered behind everything queued on the main stream so far."""
+        if self.side is None:
+            return call(stream_handle())
+        self.side.wait_stream(self.main)
+        with torch.cuda.stream(self.side):
+            call(stream_handle())
+
+    def join(self) -> None:
+        if self.side is not None:
+            self.main.wait_stream(self.side)
+
+    def leave_in_flight(self, *tensors) -> None:
+        """The allocator must not reuse these blocks for the main stream before the side stream's queued work is done with them."""
+        for t in tensors if self.side is not None else ():
+            t.record_stream(self.side)
 
 
 def _device_of(args) -> "torch.device | None":

@@ -1052,7 +1052,7 @@ class EgoNeRF(TensorBase):
         if marched_event is not None and N:
             args.marched = marched_event.cuda_event
             self._marched_recorded = True
-        S = (n_coarse + n_fine if use_coarse_sample else n_fine) if resampling else n_coarse
+        S = _lib.sample_count(n_coarse, n_fine, resampling, use_coarse_sample)
         lib = _lib.load()
         ws_bytes = lib.ego_render_workspace_bytes(N, C.byref(args))
         if ws_bytes < 0:
@@ -1101,7 +1101,7 @@ class EgoNeRF(TensorBase):
         z0 = z_pos[0:1].expand(N, n_coarse).contiguous()
         shifted = rays.clone()
         shifted[:, :3] = rays[:, :3] + rays[:, 3:6] * (z_pos[:, :1] - z_pos[0:1, :1])
-        S = (n_coarse + n_fine if use_coarse_sample else n_fine) if resampling else n_coarse
+        S = _lib.sample_count(n_coarse, n_fine, resampling, use_coarse_sample)
         has_env = self.envmap is not None
         astride = S + int(has_env)
         alpha = f(N, astride) if need_alpha else None

@@ -18,15 +18,13 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import check as _chk
+from .model import _carve_channel_last
 
 
 def needs_grad(*tensors) -> bool:
     """The condition under which a stage op records a graph: grad mode on and any of `tensors` requiring grad."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
-
-
-def _chk(code: int, what: str) -> None:
-    _lib.check(code, what)
 
 
 def _workspace(model, nbytes: int, device) -> torch.Tensor:
@@ -42,10 +40,8 @@ def _workspace(model, nbytes: int, device) -> torch.Tensor:
 
 def _grad_tables(params: List[torch.Tensor]):
     """Channel-last gradient tables shaped like `params` (one buffer, like the parameters) + the ego_vm_grad struct over them."""
-    from .model import _carve_channel_last
-    from .train import _grad_struct
     gs = _carve_channel_last([(p.shape[1], p.shape[2], p.shape[3]) for p in params], params[0].device)
-    return gs, _grad_struct(gs)
+    return gs, _lib.grad_struct(gs)
 
 
 class DensityFeatureFunction(torch.autograd.Function):

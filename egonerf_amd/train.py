@@ -3,78 +3,60 @@ EgoNeRF.forward that train.py:312-314 runs in the reference).
 
 The differentiable call is a `torch.autograd.Function` whose forward is the same kernel sequence as inference
 (coarse march on the pooled tables -> inverse-CDF resampling -> fine march -> shade -> composite; the fine
-sample positions are detached like EgoNeRF.py:534) and whose backward runs `ego_march_backward`
-(compositing + density, scatter-add into the density tables) and `ego_shade_backward` (MLP / basis data
-gradients on the fp16-split MFMA path, scatter-add into the appearance tables).  The basis / MLP weight and
-bias gradients come from `ego_weight_grad` (csrc/ego_wgrad.hip: one bf16 hi/lo MFMA pass per layer over the per-sample
-buffers the kernels leave behind), un-permuted with the column maps of `ego_train_layout`.
+sample positions are detached like EgoNeRF.py:534) plus one sort of the step's samples by texel cell on a side stream
+(DESIGN.md 4.2).  Its backward runs `ego_march_backward` (compositing + density), `ego_shade_backward` (MLP / basis data
+gradients on the fp16-split MFMA path) and, on the side stream, the two table scatters: sorted, atomic-free and
+bit-reproducible by default (`ego_scatter_*_sorted`; the appearance walk also produces d(basis) and re-derives dv), float
+atomics for `model.deterministic_scatter = False` and table shapes the sorted kernels are not built for.  The MLP weight and
+bias gradients come from `ego_weight_grad` (csrc/ego_wgrad.hip), un-permuted with the column maps of `ego_train_layout`.
+`forward` records every decision that shapes the step in one `StepPlan`; `backward` only reads it.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
-from typing import List, Optional
+import functools
+import os
+import warnings
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import SideStream, grad_struct as _grad_struct  # noqa: F401  (tests and tools import _grad_struct from here)
 
-_LAYOUT_CACHE = {}
 
-
+@functools.lru_cache(maxsize=None)
 def _layout(which: int, n: int, device) -> torch.Tensor:
-    key = (which, str(device))
-    if key not in _LAYOUT_CACHE:
-        buf = (C.c_int32 * n)()
-        _lib.check(_lib.load().ego_train_layout(which, buf, n), "ego_train_layout")
-        _LAYOUT_CACHE[key] = torch.from_numpy(np.frombuffer(buf, dtype=np.int32).astype(np.int64).copy()).to(device)
-    return _LAYOUT_CACHE[key]
+    buf = (C.c_int32 * n)()
+    _lib.check(_lib.load().ego_train_layout(which, buf, n), "ego_train_layout")
+    return torch.from_numpy(np.frombuffer(buf, dtype=np.int32).astype(np.int64).copy()).to(device)
 
 
 _INDEX_CACHE = {}
 
-# The two table scatters (VALU / atomic bound) run on a side stream next to the shade backward and the weight-gradient passes
-# (HBM bound).  Every buffer the side stream reads stays referenced until the main stream has waited for it: a tensor freed
-# earlier goes back to the main stream's allocator pool and the next main-stream allocation may overwrite it while the side
-# stream still reads (the intermittent wrong appearance gradient of the first attempt, DESIGN.md 4.2).  EGO_TRAIN_SIDE_STREAM=0
-# serialises everything on one stream.
-SIDE_STREAM_SCATTER = __import__("os").environ.get("EGO_TRAIN_SIDE_STREAM", "1") != "0"
-# r06: d(basis) rides along in the sorted appearance scatter's walk (plane value x line value = v is in its registers), so the forward
-# dumps no v and the d(basis) weight-gradient pass is gone; EGO_TRAIN_WALK_BASIS=0 keeps the dump + ego_weight_grad form
-WALK_BASIS = __import__("os").environ.get("EGO_TRAIN_WALK_BASIS", "1") != "0"
-# r06: ... and re-derives dv = basis^T dfe there too (27 slot gradients in, 48 channels out per plane), so ego_shade_backward writes no dv
-# (576 B per sample) for the scatter to read back; EGO_TRAIN_WALK_DV=0 keeps the dv hand-over
-WALK_DV = __import__("os").environ.get("EGO_TRAIN_WALK_DV", "1") != "0"
-DUMP_X = __import__("os").environ.get("EGO_TRAIN_DUMP_X", "0") != "0"   # keep the forward's x dump (rounds 1-4) instead of re-deriving x for d(W1)
-_SIDE_STREAMS = {}
+
+def _env_on(name: str, default: str) -> bool:
+    return os.environ.get(name, default) != "0"
 
 
-def _side_stream(device) -> "torch.cuda.Stream":
-    key = torch.device(device).index
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[key]
-
+# The module switches: attributes read when a step is planned (callers and tests set them at run time); the environment gives the defaults.
+# The table scatters (and the forward's sort) run on a side stream next to the shade backward and the weight-gradient passes (`_lib.SideStream`)
+SIDE_STREAM_SCATTER = _env_on("EGO_TRAIN_SIDE_STREAM", "1")
+# d(basis) rides along in the sorted appearance walk (v is in its registers): no v dump, no d(basis) weight-gradient pass; off = dump + ego_weight_grad
+WALK_BASIS = _env_on("EGO_TRAIN_WALK_BASIS", "1")
+# ... and the walk re-derives dv = basis^T dfe too, so ego_shade_backward writes no dv (576 B per sample); off = the dv hand-over
+WALK_DV = _env_on("EGO_TRAIN_WALK_DV", "1")
+# keep the forward's x dump (rounds 1-4) instead of re-deriving x for d(W1) from the feature slots and the view direction (ego_weight_grad_x)
+DUMP_X = _env_on("EGO_TRAIN_DUMP_X", "0")
+# debugging: synchronise and print after every library call
+_DEBUG_SYNC = _env_on("EGO_TRAIN_DEBUG_SYNC", "0")
 
 # Optional per-call timing (bench.py): when KERNEL_MARKS is a list, an event is recorded on the current stream after every library
 # call of the step and appended as (name, event); the interval between two consecutive marks is that call's kernel time plus the
 # torch glue (zero fills, index scatters) queued in front of it.  Meaningful with SIDE_STREAM_SCATTER = False (one stream).
 KERNEL_MARKS = None
-
-
-_DEBUG_SYNC = __import__("os").environ.get("EGO_TRAIN_DEBUG_SYNC", "0") != "0"   # debugging: synchronise and print after every library call
-
-
-def _chk(code: int, what: str) -> None:
-    _lib.check(code, what)
-    if _DEBUG_SYNC and not torch.cuda.is_current_stream_capturing():
-        print("[ego train] queued", what, flush=True)
-        torch.cuda.synchronize()
-        print("[ego train] done  ", what, flush=True)
-    if KERNEL_MARKS is not None:
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        KERNEL_MARKS.append((what, ev))
 
 
 def mark(what: str) -> None:
@@ -85,6 +67,15 @@ def mark(what: str) -> None:
         KERNEL_MARKS.append((what, ev))
 
 
+def _chk(code: int, what: str) -> None:
+    _lib.check(code, what)
+    if _DEBUG_SYNC and not torch.cuda.is_current_stream_capturing():
+        print("[ego train] queued", what, flush=True)
+        torch.cuda.synchronize()
+        print("[ego train] done  ", what, flush=True)
+    mark(what)
+
+
 # Weight-gradient products of one step land in ONE zero-filled buffer [352][160] (rows: do^T h2 | dh2^T h1 | dh1^T x | dfe^T v) and
 # ONE gather turns it into the eight reference-shaped gradients (basis yin / yang, w1, b1, w2, b2, w3, b3): two small kernels
 # instead of a zero fill per product and a fill + an index_put per gradient (22 launches of ~5 us each on the critical path).
@@ -92,7 +83,7 @@ _G_ROWS = dict(G3=(0, 32), G2=(32, 160), G1=(160, 288), Gb=(288, 352))
 _G_LD = 160
 
 
-def _grad_plan(model, device, basis_reference_columns: bool = False):
+def _gather_plan(model, device, basis_reference_columns: bool = False):
     """(flat gather index, split sizes, shapes, pad column) derived once from the layouts (no host synchronisation per step).
     basis_reference_columns: the Gb block's columns are already plane x 48 + channel (ego_scatter_app_sorted's gbasis) instead of the
     v dump's column order (ego_weight_grad over ego_shade_dump.v)."""
@@ -133,18 +124,13 @@ def _zeros_like_many(tensors, zero: bool = True):
     out, off = [], 0
     for t in tensors:
         out.append(torch.as_strided(flat, t.shape, t.stride(), off))
+        assert out[-1].stride() == t.stride()
         off += t.numel()
     return out
 
 
-def _grad_struct(tensors: List[torch.Tensor]) -> "_lib.VmGrad":
-    """tensors: [plane_yin x3, line_yin x3, plane_yang x3, line_yang x3] gradient tables (channel-last memory)."""
-    g = _lib.VmGrad()
-    for gi in range(2):
-        for i in range(3):
-            g.plane[gi][i] = tensors[gi * 6 + i].data_ptr()
-            g.line[gi][i] = tensors[gi * 6 + 3 + i].data_ptr()
-    return g
+def _empty(device, *shape, dtype=torch.float32) -> torch.Tensor:
+    return torch.empty(*shape, device=device, dtype=dtype)
 
 
 def table_params(model, kind: str) -> List[torch.nn.Parameter]:
@@ -152,20 +138,6 @@ def table_params(model, kind: str) -> List[torch.nn.Parameter]:
     for g in ("yin", "yang"):
         out += list(getattr(model, f"{kind}_plane_{g}")) + list(getattr(model, f"{kind}_line_{g}"))
     return out
-
-
-def head_is_tuned(model) -> bool:
-    """True when the appearance head has the shape the MFMA kernels (forward dumps, ego_shade_backward, ego_scatter_app) are built for:
-    48 components, app_dim 27, MLP_Fea 150 -> 128 -> 128 -> 3 with view_pe = fea_pe = 2.  (The density field's component count is
-    independent: 16 takes ego_scatter_density, anything else ego_scatter_generic.)"""
-    return model.head_is_tuned
-
-
-def _generic_head_sorted_app(model, sort_ws, M: int) -> bool:
-    """A head of another shape over 48-component appearance tables: ego_shade_backward_generic writes the blocked dv and the sorted walk
-    scatters it (the step's sort exists whenever the density field has its tuned shape)."""
-    return (sort_ws is not None and model.app_n_comp[0] == 48 and __import__("os").environ.get("EGO_SORTED_WALK", "1") != "0"
-            and (M + 31) // 32 * 32 * 144 < 2 ** 30)
 
 
 def differentiable_params(model) -> List[torch.nn.Parameter]:
@@ -177,315 +149,343 @@ def differentiable_params(model) -> List[torch.nn.Parameter]:
     return table_params(model, "density") + table_params(model, "app") + head
 
 
+def _generic_head_sorted_app(model, sort_ws, M: int) -> bool:
+    """A head of another shape over 48-component appearance tables: ego_shade_backward_generic writes the blocked dv and the sorted walk
+    scatters it (the step's sort exists whenever the density field has its tuned shape; sort_ws: its workspace, or True for "it will").
+    Also what lets the tuned head's walk take dfe.  EGO_SORTED_WALK is read here and nowhere else, once per step when the step is planned
+    (not at import: the library reads it per call too, csrc/ego_scatter_sorted.hip::walk_wanted, and the two must agree)."""
+    return sort_ws is not None and _env_on("EGO_SORTED_WALK", "1") and model.app_n_comp[0] == 48 and (M + 31) // 32 * 32 * 144 < 2 ** 30
+
+
+class StepPlan(NamedTuple):
+    """Every decision that shapes one training step, taken once in RenderFunction.forward; the backward reads it and re-derives nothing."""
+    N: int
+    S: int
+    M: int                   # N * S samples
+    Mp: int                  # ... padded to whole 32-sample tiles (the tuned dumps are tile-blocked: include/egonerf_hip.h, ego_shade_dump)
+    head_tuned: bool         # the MFMA head kernels (else the fp32 compatibility kernels: another shape, or the parity mode)
+    compat: Optional[torch.Tensor]   # parity mode (model.train_fp32_head): the tuned head's weights packed in the compatibility layout
+    sorts: bool              # the step's samples are binned by texel cell (ego_scatter_sort) for the deterministic scatters
+    sorted_dens: bool        # density / appearance table gradients by the sorted, atomic-free scatter (else float atomics into zeros)
+    sorted_app: bool
+    walk_basis: bool         # the appearance walk produces d(basis): no v dump, no d(basis) weight-gradient pass
+    walk_dv: bool            # ... and re-derives dv from dfe: ego_shade_backward writes no dv
+    dump_x: bool             # the forward dumps x / v for the weight gradients
+    dump_v: bool
+    side: Optional["torch.cuda.Stream"]   # where the sort and the scatters run (None: in line)
+
+
+def _plan_step(model, sc, N: int, S: int) -> StepPlan:
+    M, device = N * S, model.density_plane_yin[0].device
+    head_tuned = model.head_is_tuned and not model.train_fp32_head
+    dens16 = model.density_n_comp[0] == 16
+    # Deterministic table gradients (model.deterministic_scatter, the default): tuned table shapes only (16 / 48 components); anything
+    # else keeps the atomic scatters
+    sorts = bool(model.deterministic_scatter and (dens16 or head_tuned))
+    walk = _generic_head_sorted_app(model, sorts or None, M)
+    walk_basis = bool(head_tuned and WALK_BASIS and walk)
+    compat = None
+    if model.head_is_tuned and not head_tuned:
+        compat = _empty(device, _lib.load().ego_packed_floats_compat(sc))
+    return StepPlan(N=N, S=S, M=M, Mp=(M + 31) // 32 * 32, head_tuned=head_tuned, compat=compat, sorts=sorts, sorted_dens=sorts and dens16,
+                    sorted_app=sorts and (head_tuned or walk), walk_basis=walk_basis, walk_dv=bool(walk_basis and WALK_DV),
+                    dump_x=bool(DUMP_X) if head_tuned else model.shadingMode != "RGB", dump_v=not walk_basis,
+                    side=_lib.side_stream(device) if SIDE_STREAM_SCATTER else None)
+
+
+def _head_scene(sc, plan: StepPlan, pack: bool = False) -> "_lib.Scene":
+    """The scene the head's kernels see.  Parity mode (model.train_fp32_head / EGO_TRAIN_FP32=1): the tuned head trained through the fp32 compatibility
+    kernels - fp32 activations, fp32 dumps, fp32 weight-gradient operands like the reference's autograd - on a copy of the
+    scene whose packed blob is the compatibility layout (the tuned path keeps x / h1 / h2 / dh1 / dh2 as halves: DESIGN.md 4.2)."""
+    if plan.compat is not None:
+        sc = _lib.Scene.from_buffer_copy(sc)
+        if pack:
+            _chk(_lib.load().ego_pack_mlp_compat(sc, plan.compat.data_ptr(), _lib.stream_handle()), "ego_pack_mlp_compat")
+        sc.packed = plan.compat.data_ptr()
+    return sc
+
+
+def _warn_inference_precision(model) -> None:
+    """mlp_precision is an INFERENCE switch; before r05 a differentiable call with "f32" raised, now it would silently
+    train through split-fp16 products and half-precision activation dumps - say so once, and say what the real switch is."""
+    if model._mlp_precision == "f32" and not model.train_fp32_head and not getattr(model, "_warned_f32_training", False):
+        warnings.warn("EgoNeRF.mlp_precision = 'f32' applies to inference only: the differentiable path runs the f16x3 training kernels "
+                      "(fp16-split MFMA products, half-precision activation dumps).  For fp32 activations and operands in training set "
+                      "model.train_fp32_head = True (or EGO_TRAIN_FP32=1): the parity mode, several times slower.", RuntimeWarning, stacklevel=4)
+        model._warned_f32_training = True
+
+
+# One operand of an A^T B weight-gradient product (ego_weight_grad_det): pointer, leading dimension, columns used, layout code
+# (include/egonerf_hip.h: 0 row-major fp32, 1 / 2 the tuned dumps' fp32 / half order, 3 dfe routed by coords.w), per-sample scale
+_Operand = collections.namedtuple("_Operand", "ptr ld cols layout scale", defaults=(0, None))
+
+
+def _weight_grad(G, A, B, ones_col: int, M: int, part) -> None:
+    """G [rows][_G_LD] += A^T [B | 1 at ones_col].  part: the workgroups' partial products, added in a fixed order (deterministic mode,
+    model.deterministic_scatter) instead of float atomics."""
+    _chk(_lib.load().ego_weight_grad_det(A.ptr, A.ld, A.cols, A.layout, A.scale, B.ptr, B.ld, B.cols, B.layout, ones_col, M, G.data_ptr(), _G_LD,
+                                         _lib.ptr(part), 0 if part is None else part.numel(), _lib.stream_handle()), "ego_weight_grad")
+
+
+def _march(plan: StepPlan, sc, model, rays, opts) -> dict:
+    """coarse march on the pooled tables -> pdf merge -> fine march, or one march: z, alpha, weight, sigma, bg, coords of the step's samples."""
+    lib, st, dev, N, S = _lib.load(), _lib.stream_handle(), rays.device, plan.N, plan.S
+    n_coarse, zc_in = opts["n_coarse"], opts.get("z_coarse")  # explicit first-pass distances (exp_sampling=False) instead of schedule + jitter
+    near = float(model.near_far[0])
+    sched, jitter = (model._sched(n_coarse, dev).data_ptr(), _lib.ptr(opts["jitter"])) if zc_in is None else (None, None)
+    b = dict(z=_empty(dev, N, S), alpha=_empty(dev, N, S + int(model.envmap is not None)), weight=_empty(dev, N, S), sigma=_empty(dev, N, S),
+             bg=_empty(dev, N), coords=_empty(dev, N, S, 4))
+    outs = (b["alpha"].data_ptr(), b["alpha"].shape[1], b["weight"].data_ptr(), b["bg"].data_ptr(), b["coords"].data_ptr(), b["sigma"].data_ptr())
+    if opts["resampling"]:
+        zc, wc = (_empty(dev, N, n_coarse) if zc_in is None else zc_in), _empty(dev, N, n_coarse)
+        _chk(lib.ego_march_density(sc, rays.data_ptr(), N, n_coarse, _lib.ptr(zc_in), sched, jitter, near, 1, zc.data_ptr() if zc_in is None else None,
+                                   None, 0, wc.data_ptr(), None, None, None, None, st), "ego_march_density")
+        _chk(lib.ego_sample_pdf_merge(zc.data_ptr(), wc.data_ptr(), _lib.ptr(opts["u"]), N, n_coarse, opts["n_fine"], int(opts["use_coarse_sample"]),
+                                      b["z"].data_ptr(), None, st), "ego_sample_pdf_merge")
+        # fine pass: full tables and the full-resolution r grid (bit 1; EgoNeRF.py:546 normalises without `downsample`)
+        _chk(lib.ego_march_density(sc, rays.data_ptr(), N, S, b["z"].data_ptr(), None, None, near, 2, None, *outs, None, st), "ego_march_density")
+    else:
+        _chk(lib.ego_march_density(sc, rays.data_ptr(), N, S, _lib.ptr(zc_in), sched, jitter, near, 0, b["z"].data_ptr(), *outs, None, st),
+             "ego_march_density")
+    return b
+
+
+def _sort(plan: StepPlan, sc, coords) -> Optional[torch.Tensor]:
+    """The step's samples binned by texel cell once, from the coordinates the march just wrote - on the side stream, next to the dumping
+    shade forward - so that the backward's two scatters write every gradient texel once, in a fixed order (csrc/ego_scatter_sorted.hip)."""
+    if not plan.sorts:
+        return None
+    lib, N, S = _lib.load(), plan.N, plan.S
+    nbytes = lib.ego_scatter_sorted_workspace_bytes(sc, N, S)
+    if nbytes <= 0:
+        raise RuntimeError("ego_scatter_sorted_workspace_bytes rejected the scene: " + lib.ego_last_error().decode())
+    ws = _empty(coords.device, nbytes, dtype=torch.uint8)
+    side = SideStream(plan.side, coords.device)
+    side.run(lambda s: _chk(lib.ego_scatter_sort(sc, coords.data_ptr(), N, S, ws.data_ptr(), nbytes, s), "ego_scatter_sort"))
+    side.leave_in_flight(ws, coords)   # no join here (the backward's scatters queue behind the sort): a forward whose backward never runs
+    return ws
+
+
+def _shade_tuned(plan: StepPlan, sc, rays, b, rgb) -> dict:
+    """The MFMA shade with its tile-blocked dumps: h1 / h2 (x only with DUMP_X: d(W1) re-derives it from the feature slots `fe` and the view
+    direction, ego_weight_grad_x: bit-identical operands, 0.67 GB less written and 0.4 GB less read per 8192 x 256 step) as halves in the
+    kernels' operand order, v unless the appearance walk produces d(basis)."""
+    dev, Mp = rays.device, plan.Mp
+    f16 = lambda *shape: _empty(dev, *shape, dtype=torch.float16)
+    dump = dict(x=f16(Mp, 160) if plan.dump_x else None, h1=f16(Mp, 128), h2=f16(Mp, 128), v=_empty(dev, Mp, 144) if plan.dump_v else None,
+                relu_bits=_empty(dev, Mp // 32, 2, 64, 2, dtype=torch.int32), fe=_empty(dev, Mp // 32, 4, 64, 4))
+    _chk(_lib.load().ego_shade(sc, rays.data_ptr(), b["z"].data_ptr(), b["coords"].data_ptr(), plan.N, plan.S, rgb.data_ptr(),
+                               C.byref(_shade_dump(dump)), None, _lib.stream_handle()), "ego_shade")
+    return dump
+
+
+def _shade_dump(sv: dict) -> "_lib.ShadeDump":
+    return _lib.ShadeDump(*(_lib.ptr(sv[k]) for k in ("x", "h1", "h2", "v", "relu_bits", "fe")))
+
+
+def _shade_generic(plan: StepPlan, sc, model, rays, b, rgb) -> dict:
+    """Any other model shape (opt.py:87-100): fp32 compatibility kernels over row-major dumps, padded to whole 160-column blocks (what
+    ego_weight_grad multiplies at a time) with at least one zero column left for the bias gradients."""
+    ldx = (model.head_in_mlpC // _G_LD + 1) * _G_LD
+    z0 = lambda *shape: torch.zeros(*shape, device=rays.device, dtype=torch.float32)
+    # shadingMode "RGB", no network (not dump_x): only the plane x line products are kept (they feed the basis gradient)
+    dump = dict(x=z0(plan.M, ldx), h1=z0(plan.M, _G_LD), h2=z0(plan.M, _G_LD)) if plan.dump_x else dict(x=None, h1=None, h2=None)
+    dump["v"] = z0(plan.M, _G_LD)
+    _chk(_lib.load().ego_shade_train_generic(sc, rays.data_ptr(), b["coords"].data_ptr(), plan.N, plan.S, rgb.data_ptr(), _lib.ptr(dump["x"]), ldx,
+                                             _lib.ptr(dump["h1"]), _lib.ptr(dump["h2"]), _G_LD, dump["v"].data_ptr(), _G_LD, _lib.stream_handle()),
+         "ego_shade_train_generic")
+    return dump
+
+
+def _scatter_tables(plan: StepPlan, sc, sv, side: SideStream, kind: str, d, g_tables, walk=(None, None, None, 0)) -> None:
+    """The table gradients of one field ("density": d = dfeat, "app": d = dv or None) on the side stream: the sorted scatter, the
+    float-atomic one of the tuned shape, or the any-shape atomics.  walk (tuned head, sorted): (max |dv|, dfe, d(basis) block, its ld)."""
+    lib, N, S, coords, ws, g = _lib.load(), plan.N, plan.S, sv["coords"].data_ptr(), sv["sort_ws"], _grad_struct(g_tables)
+    density = kind == "density"
+    if density and plan.sorted_dens:
+        what = "ego_scatter_density_sorted"
+        call = lambda s: lib.ego_scatter_density_sorted(sc, C.byref(g), coords, d.data_ptr(), N, S, ws.data_ptr(), ws.numel(), s)
+    elif density and sc.density.n_comp == 16:
+        what, call = "ego_scatter_density", lambda s: lib.ego_scatter_density(sc, C.byref(g), coords, d.data_ptr(), N, S, s)
+    elif not density and plan.sorted_app:
+        what = "ego_scatter_app_sorted" if plan.head_tuned else "ego_scatter_app_sorted(generic head)"
+        call = lambda s: lib.ego_scatter_app_sorted(sc, C.byref(g), coords, _lib.ptr(d), *walk, N, S, ws.data_ptr(), ws.numel(), s)
+    elif not density and plan.head_tuned:
+        what, call = "ego_scatter_app", lambda s: lib.ego_scatter_app(sc, C.byref(g), coords, d.data_ptr(), N, S, s)
+    else:
+        field, ld = (sc.density, 0) if density else (sc.app, _G_LD)
+        what, call = f"ego_scatter_generic({kind})", lambda s: lib.ego_scatter_generic(C.byref(field), C.byref(g), coords, d.data_ptr(), ld, N, S, s)
+    side.run(lambda s: _chk(call(s), what))
+
+
+def _head_backward_tuned(plan: StepPlan, sc, sv, dc, g_app, side: SideStream) -> dict:
+    """ego_shade_backward, then the appearance scatter on the side stream -> what the weight gradients read.  dh2 / dh1: scaled fp16 in
+    the kernel's own operand order + one power of two per sample (include/egonerf_hip.h); dv: blocked fp32, not written with walk_dv."""
+    lib, st, dev, M, Mp = _lib.load(), _lib.stream_handle(), dc.device, plan.M, plan.Mp
+    tp = _empty(dev, lib.ego_train_packed_floats())
+    _chk(lib.ego_pack_train(sc, tp.data_ptr(), st), "ego_pack_train")
+    f16 = lambda *shape: _empty(dev, *shape, dtype=torch.float16)
+    hb = dict(dh2=f16(Mp, 128), dh1=f16(Mp, 128), dh_scale=_empty(dev, 2, Mp), dfe=_empty(dev, M, 32))
+    dv = None if plan.walk_dv else _empty(dev, Mp, 144)
+    # max |dv| (walk_dv: max |dfe|), found by the backward while it holds the values: the sorted scatter's fixed-point unit comes from it
+    hb["dv_absmax"] = _empty(dev, 1)
+    _chk(lib.ego_shade_backward(sc, tp.data_ptr(), sv["coords"].data_ptr(), dc.data_ptr(), sv["rgb"].data_ptr(), C.byref(_shade_dump(sv)),
+                                hb["dh2"].data_ptr(), hb["dh1"].data_ptr(), hb["dh_scale"].data_ptr(), hb["dfe"].data_ptr(), _lib.ptr(dv),
+                                hb["dv_absmax"].data_ptr(), plan.N, plan.S, st), "ego_shade_backward")
+    # the product buffer exists (zero-filled, on the main stream) BEFORE the side stream is allowed to write its d(basis) block into it
+    hb["Gall"] = torch.zeros(352, _G_LD, device=dev)
+    walk = (hb["dv_absmax"].data_ptr(), None, None, 0)
+    if plan.walk_basis:
+        walk = (hb["dv_absmax"].data_ptr(), hb["dfe"].data_ptr(), hb["Gall"][_G_ROWS["Gb"][0]:].data_ptr(), _G_LD)
+    _scatter_tables(plan, sc, sv, side, "app", dv, g_app, walk)
+    if side.side is not None:   # in line the scatter is queued and dv's block may be reused at once; the side stream reads it until the join
+        hb["dv"] = dv
+    return hb
+
+
+def _weight_grads_tuned(plan: StepPlan, model, sv, hb, dc, side: SideStream) -> list:
+    """One pass of ego_weight_grad (bf16 hi/lo MFMA over transposed LDS tiles, bias gradients from a ones column) per layer over the dumped
+    buffers into one product buffer, then one gather un-permutes the lane-order columns into the reference-shaped gradients
+    (basis yin, basis yang, w1, b1, w2, b2, w3, b3: differentiable_params order)."""
+    M, S, Gall = plan.M, plan.S, hb["Gall"]
+    G = {k: Gall[a:b] for k, (a, b) in _G_ROWS.items()}
+    gidx, gsizes, gshapes, pad = _gather_plan(model, dc.device, plan.walk_basis)  # pad: a zero padding column of x doubles as the ones column
+    part = _empty(dc.device, _lib.load().ego_weight_grad_partial_floats()) if model.deterministic_scatter else None
+    half = lambda t, cols, scale=None: _Operand(t.data_ptr(), t.shape[1], cols, 2, _lib.ptr(scale))
+    _weight_grad(G["G3"], _Operand(dc.data_ptr(), 3, 3), half(sv["h2"], 128), 128, M, part)   # dc: now d(pre-sigmoid)
+    _weight_grad(G["G2"], half(hb["dh2"], 128, hb["dh_scale"][0]), half(sv["h1"], 128), 128, M, part)
+    if plan.dump_x:
+        _weight_grad(G["G1"], half(hb["dh1"], 128, hb["dh_scale"][1]), half(sv["x"], 160), pad, M, part)
+    else:   # the layer-1 input re-derived from the feature slots and the rays' directions inside the product's B-tile fetch
+        _chk(_lib.load().ego_weight_grad_x(hb["dh1"].data_ptr(), hb["dh_scale"][1].data_ptr(), sv["fe"].data_ptr(), sv["rays"].data_ptr(), S, pad, M,
+                                           G["G1"].data_ptr(), _G_LD, _lib.ptr(part), 0 if part is None else part.numel(), _lib.stream_handle()),
+             "ego_weight_grad")
+    if plan.walk_basis:
+        side.join()   # the walk's k_basis_reduce wrote Gall's Gb block on the side stream
+    else:   # 32 stored columns of dfe, routed to the yin / yang block by coords.w
+        _weight_grad(G["Gb"], _Operand(hb["dfe"].data_ptr(), 32, 64, 3, sv["coords"].data_ptr()), _Operand(sv["v"].data_ptr(), 144, 144, 1), -1, M, part)
+    return [t.view(shp) for t, shp in zip(Gall.view(-1).index_select(0, gidx).split(gsizes), gshapes)]
+
+
+def _head_backward_generic(plan: StepPlan, sc, model, sv, dc, g_app, side: SideStream) -> dict:
+    """Backward of the appearance head for any model shape the compatibility kernels support (row-major buffers).  Another head over the
+    SHIPPED table shape: dv in the tuned scatters' blocked layout, and the sorted walk takes the table gradients (deterministic, 0.75 ms
+    where the any-shape atomic scatter takes 9.8)."""
+    dev, M, hid, rgb_head = dc.device, plan.M, model.head_hidden, not plan.dump_x
+    hb = dict(dh2=None if rgb_head else _empty(dev, M, hid), dh1=None if rgb_head else _empty(dev, M, hid), dfe=_empty(dev, M, 64),
+              ldx=_G_LD if rgb_head else sv["x"].shape[1])
+    hb["dv"] = _empty(dev, plan.Mp, 144) if plan.sorted_app else _empty(dev, M, _G_LD)
+    _chk(_lib.load().ego_shade_backward_generic(sc, sv["coords"].data_ptr(), dc.data_ptr(), sv["rgb"].data_ptr(), _lib.ptr(sv["x"]), hb["ldx"],
+                                                _lib.ptr(sv["h1"]), _lib.ptr(sv["h2"]), _G_LD, _lib.ptr(hb["dh2"]), _lib.ptr(hb["dh1"]),
+                                                hb["dfe"].data_ptr(), hb["dv"].data_ptr(), 0 if plan.sorted_app else _G_LD, plan.N, plan.S,
+                                                _lib.stream_handle()), "ego_shade_backward_generic")
+    _scatter_tables(plan, sc, sv, side, "app", hb["dv"], g_app)
+    return hb
+
+
+def _weight_grads_generic(plan: StepPlan, model, sv, hb, dc) -> list:
+    """The weight gradients as A^T B products in 160-column blocks, already in the reference's [out][in] orientation."""
+    M, hid, in_c, ncol, D, ldx = plan.M, model.head_hidden, model.head_in_mlpC, 3 * model.app_n_comp[0], model.app_dim, hb["ldx"]
+    hp = (hid + 31) // 32 * 32
+    part = _empty(dc.device, _lib.load().ego_weight_grad_partial_floats()) if model.deterministic_scatter else None
+
+    def product(A, ca, B_ptr, ldb, ones_col, rows):
+        G = torch.zeros(rows, _G_LD, device=dc.device)
+        _weight_grad(G, _Operand(A.data_ptr(), ca, ca), _Operand(B_ptr, ldb, _G_LD), ones_col, M, part)
+        return G
+
+    Gb = product(hb["dfe"], 64, sv["v"].data_ptr(), _G_LD, -1, 64)                      # [yin | yang] feature gradients ^T v
+    wg = [Gb[0:D, :ncol].contiguous(), Gb[32:32 + D, :ncol].contiguous()]
+    if plan.dump_x:
+        G3 = product(dc.view(M, 3), 3, sv["h2"].data_ptr(), _G_LD, hid, 32)               # do^T [h2 | 1]
+        G2 = product(hb["dh2"], hid, sv["h1"].data_ptr(), _G_LD, hid, hp)                 # dh2^T [h1 | 1]
+        G1 = []
+        for c0 in range(0, ldx, _G_LD):
+            ones = in_c - c0 if c0 <= in_c < c0 + _G_LD else -1                           # the first zero-padding column doubles as the ones column
+            G1.append(product(hb["dh1"], hid, sv["x"].data_ptr() + 4 * c0, ldx, ones, hp))
+        G1 = torch.cat(G1, dim=1)
+        wg += [G1[:hid, :in_c].contiguous(), G1[:hid, in_c].contiguous(), G2[:hid, :hid].contiguous(), G2[:hid, hid].contiguous(),
+               G3[:3, :hid].contiguous(), G3[:3, hid].contiguous()]
+    return wg
+
+
+def _envmap_grad(sc, model, sv, g_rgb) -> torch.Tensor:
+    g_em = torch.zeros_like(model.envmap.emission)
+    _chk(_lib.load().ego_envmap_backward(sc, sv["rays"].data_ptr() + 12, 6, g_rgb.data_ptr(), sv["raw"].data_ptr(), sv["bg"].data_ptr(),
+                                         sv["env"].data_ptr(), g_rgb.shape[0], g_em.data_ptr(), _lib.stream_handle()), "ego_envmap_backward")
+    return g_em
+
+
 class RenderFunction(torch.autograd.Function):
     @staticmethod
     @_lib.device_guard
     def forward(ctx, model, rays, opts, *params):
         """params = differentiable_params(model) (+ envmap.emission last when the model has an envmap)."""
-        lib, st = _lib.load(), _lib.stream_handle()
+        lib, st, dev = _lib.load(), _lib.stream_handle(), rays.device
         ctx.set_materialize_grads(False)
-        dev = rays.device
         # training gathers from the fp32 parameters (the backward re-gathers from them), shades every sample like EgoNeRF.forward (the
         # appearance skip is an inference option) and keeps all three fp16 terms of every product, whatever model.mlp_precision says
-        if model._mlp_precision == "f32" and not model.train_fp32_head and not getattr(model, "_warned_f32_training", False):
-            # ADVICE r05: mlp_precision is an INFERENCE switch; before r05 a differentiable call with "f32" raised, now it would silently
-            # train through split-fp16 products and half-precision activation dumps - say so once, and say what the real switch is
-            import warnings
-            warnings.warn("EgoNeRF.mlp_precision = 'f32' applies to inference only: the differentiable path runs the f16x3 training kernels "
-                          "(fp16-split MFMA products, half-precision activation dumps).  For fp32 activations and operands in training set "
-                          "model.train_fp32_head = True (or EGO_TRAIN_FP32=1): the parity mode, several times slower.", RuntimeWarning, stacklevel=3)
-            model._warned_f32_training = True
+        _warn_inference_precision(model)
         sc = model.scene(training=True)
         N = rays.shape[0]
-        n_coarse, n_fine = opts["n_coarse"], opts["n_fine"]
-        resampling, use_coarse = opts["resampling"], opts["use_coarse_sample"]
-        jitter, u = opts["jitter"], opts["u"]
-        zc_in = opts.get("z_coarse")  # explicit first-pass distances (exp_sampling=False) instead of schedule + jitter
-        near = float(model.near_far[0])
-        sched = model._sched(n_coarse, dev)
-        S = (n_coarse + n_fine if use_coarse else n_fine) if resampling else n_coarse
-        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
-        z, alpha, weight, sigma, bg = f(N, S), f(N, S + int(model.envmap is not None)), f(N, S), f(N, S), f(N)
-        coords = f(N, S, 4)
-        astride = alpha.shape[1]
-        if resampling:
-            zc, wc = (f(N, n_coarse) if zc_in is None else zc_in), f(N, n_coarse)
-            _chk(lib.ego_march_density(sc, rays.data_ptr(), N, n_coarse, _lib.ptr(zc_in), None if zc_in is not None else sched.data_ptr(),
-                                             None if zc_in is not None else _lib.ptr(jitter), near, 1,
-                                             None if zc_in is not None else zc.data_ptr(), None, 0, wc.data_ptr(), None, None, None, None, st),
-                       "ego_march_density")
-            _chk(lib.ego_sample_pdf_merge(zc.data_ptr(), wc.data_ptr(), _lib.ptr(u), N, n_coarse, n_fine, int(use_coarse),
-                                                z.data_ptr(), None, st), "ego_sample_pdf_merge")
-            # fine pass: full tables and the full-resolution r grid (bit 1; EgoNeRF.py:546 normalises without `downsample`)
-            _chk(lib.ego_march_density(sc, rays.data_ptr(), N, S, z.data_ptr(), None, None, near, 2, None, alpha.data_ptr(),
-                                             astride, weight.data_ptr(), bg.data_ptr(), coords.data_ptr(), sigma.data_ptr(), None, st),
-                       "ego_march_density")
-        else:
-            _chk(lib.ego_march_density(sc, rays.data_ptr(), N, S, _lib.ptr(zc_in), None if zc_in is not None else sched.data_ptr(),
-                                             None if zc_in is not None else _lib.ptr(jitter), near, 0,
-                                             z.data_ptr(), alpha.data_ptr(), astride, weight.data_ptr(), bg.data_ptr(),
-                                             coords.data_ptr(), sigma.data_ptr(), None, st), "ego_march_density")
-        M = N * S
-        rgb = f(N, S, 3)
-        # Deterministic table gradients (model.deterministic_scatter, the default): the step's samples are binned by texel cell once, from
-        # the coordinates the march just wrote - on the side stream, next to the dumping shade forward - and the backward's two scatters
-        # then write every gradient texel once, in a fixed order (csrc/ego_scatter_sorted.hip).  Tuned table shapes only (16 / 48
-        # components); anything else keeps the atomic scatters.
-        sort_ws = None
-        if model.deterministic_scatter and (model.density_n_comp[0] == 16 or (head_is_tuned(model) and not model.train_fp32_head)):
-            nbytes = lib.ego_scatter_sorted_workspace_bytes(sc, N, S)
-            if nbytes <= 0:
-                raise RuntimeError("ego_scatter_sorted_workspace_bytes rejected the scene: " + lib.ego_last_error().decode())
-            sort_ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            main = torch.cuda.current_stream(dev)
-            side = _side_stream(dev) if SIDE_STREAM_SCATTER else None
-            if side is None:
-                _chk(lib.ego_scatter_sort(sc, coords.data_ptr(), N, S, sort_ws.data_ptr(), nbytes, st), "ego_scatter_sort")
-            else:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    _chk(lib.ego_scatter_sort(sc, coords.data_ptr(), N, S, sort_ws.data_ptr(), nbytes, _lib.stream_handle()), "ego_scatter_sort")
-                # a forward whose backward never runs must not hand these blocks back to the main stream's pool while the sort is in flight
-                sort_ws.record_stream(side)
-                coords.record_stream(side)
-        head_tuned = head_is_tuned(model) and not model.train_fp32_head
-        compat = None
-        if head_is_tuned(model) and not head_tuned:
-            # parity mode (model.train_fp32_head / EGO_TRAIN_FP32=1): the tuned head trained through the fp32 compatibility kernels -
-            # fp32 activations, fp32 dumps, fp32 weight-gradient operands like the reference's autograd - on a copy of the scene whose
-            # packed blob is the compatibility layout (the tuned path keeps x / h1 / h2 / dh1 / dh2 as halves: DESIGN.md 4.2)
-            sc = _lib.Scene.from_buffer_copy(sc)
-            compat = f(lib.ego_packed_floats_compat(sc))
-            _chk(lib.ego_pack_mlp_compat(sc, compat.data_ptr(), st), "ego_pack_mlp_compat")
-            sc.packed = compat.data_ptr()
-        if head_tuned:
-            Mp = (M + 31) // 32 * 32  # the dumps are tile-blocked (include/egonerf_hip.h, ego_shade_dump): whole tiles
-            f16 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float16)   # x / h1 / h2: halves in the kernels' operand order
-            # x (the 160-column MLP input) is not dumped: d(W1) re-derives it from the feature slots `fe` and the view direction
-            # (ego_weight_grad_x: bit-identical operands, 0.67 GB less written and 0.4 GB less read per 8192 x 256 step); DUMP_X keeps the dump
-            walk_basis = bool(WALK_BASIS and sort_ws is not None and __import__("os").environ.get("EGO_SORTED_WALK", "1") != "0" and Mp * 144 < 2 ** 30)
-            dump = dict(x=f16(Mp, 160) if DUMP_X else None, h1=f16(Mp, 128), h2=f16(Mp, 128), v=None if walk_basis else f(Mp, 144),
-                        relu_bits=torch.empty(Mp // 32, 2, 64, 2, device=dev, dtype=torch.int32), fe=f(Mp // 32, 4, 64, 4))
-            ds = _lib.ShadeDump(*(_lib.ptr(dump[k]) for k in ("x", "h1", "h2", "v", "relu_bits", "fe")))
-            _chk(lib.ego_shade(sc, rays.data_ptr(), z.data_ptr(), coords.data_ptr(), N, S, rgb.data_ptr(), C.byref(ds), None, st), "ego_shade")
-        else:
-            # any other model shape (opt.py:87-100): fp32 compatibility kernels over row-major dumps, padded to whole 160-column
-            # blocks (what ego_weight_grad multiplies at a time) with at least one zero column left for the bias gradients
-            in_c = model.head_in_mlpC
-            ldx = (in_c // _G_LD + 1) * _G_LD
-            z0 = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)
-            if model.shadingMode == "RGB":   # no network: only the plane x line products are kept (they feed the basis gradient)
-                dump = dict(x=None, h1=None, h2=None, v=z0(M, _G_LD))
-            else:
-                dump = dict(x=z0(M, ldx), h1=z0(M, _G_LD), h2=z0(M, _G_LD), v=z0(M, _G_LD))
-            _chk(lib.ego_shade_train_generic(sc, rays.data_ptr(), coords.data_ptr(), N, S, rgb.data_ptr(), _lib.ptr(dump["x"]), ldx,
-                                             _lib.ptr(dump["h1"]), _lib.ptr(dump["h2"]), _G_LD, dump["v"].data_ptr(), _G_LD, st),
-                 "ego_shade_train_generic")
-        rgb_map, depth, raw = f(N, 3), f(N), f(N, 3)
+        S = _lib.sample_count(opts["n_coarse"], opts["n_fine"], opts["resampling"], opts["use_coarse_sample"])
+        plan = _plan_step(model, sc, N, S)
+        b = _march(plan, sc, model, rays, opts)
+        rgb = _empty(dev, N, S, 3)
+        sort_ws = _sort(plan, sc, b["coords"])
+        sc = _head_scene(sc, plan, pack=True)
+        dump = _shade_tuned(plan, sc, rays, b, rgb) if plan.head_tuned else _shade_generic(plan, sc, model, rays, b, rgb)
+        rgb_map, depth, raw = _empty(dev, N, 3), _empty(dev, N), _empty(dev, N, 3)
         has_env = model.envmap is not None
-        bg_map = f(N, 3) if has_env else None
-        env_map = f(N, 3) if has_env else None
-        _chk(lib.ego_composite(sc, rays.data_ptr(), z.data_ptr(), weight.data_ptr(), bg.data_ptr(), rgb.data_ptr(), N, S,
-                                     rgb_map.data_ptr(), depth.data_ptr(), _lib.ptr(bg_map), _lib.ptr(env_map), raw.data_ptr(), st),
-                   "ego_composite")
-        ctx.model, ctx.N, ctx.S, ctx.head_tuned, ctx.compat, ctx.sort_ws = model, N, S, head_tuned, compat, sort_ws
-        ctx.saved = dict(z=z, alpha=alpha, weight=weight, sigma=sigma, bg=bg, coords=coords, rgb=rgb, raw=raw, env=env_map, rays=rays,
-                         **dump)
+        bg_map, env_map = (_empty(dev, N, 3), _empty(dev, N, 3)) if has_env else (None, None)
+        _chk(lib.ego_composite(sc, rays.data_ptr(), b["z"].data_ptr(), b["weight"].data_ptr(), b["bg"].data_ptr(), rgb.data_ptr(), N, S,
+                               rgb_map.data_ptr(), depth.data_ptr(), _lib.ptr(bg_map), _lib.ptr(env_map), raw.data_ptr(), st), "ego_composite")
+        ctx.model, ctx.plan = model, plan
+        ctx.saved = dict(b, rgb=rgb, raw=raw, env=env_map, rays=rays, sort_ws=sort_ws, **dump)
         # depth is computed under no_grad in the reference (EgoNeRF.py:595-598); one call: a second would replace the first
         if has_env:
             ctx.mark_non_differentiable(depth, bg_map, env_map)
-            return rgb_map, depth, alpha, bg_map, env_map
+            return rgb_map, depth, b["alpha"], bg_map, env_map
         ctx.mark_non_differentiable(depth)
-        return rgb_map, depth, alpha
+        return rgb_map, depth, b["alpha"]
 
     @staticmethod
     @_lib.device_guard
     def backward(ctx, g_rgb, _g_depth=None, g_alpha=None, *_unused):
-        lib, st = _lib.load(), _lib.stream_handle()
-        model, N, S, sv = ctx.model, ctx.N, ctx.S, ctx.saved
+        model, plan, sv = ctx.model, ctx.plan, ctx.saved
         dev = sv["z"].device
-        M = N * S
-        sc = model.scene(training=True)
-        if ctx.compat is not None:   # the forward's compatibility blob (fp32 parity mode of the tuned head)
-            sc = _lib.Scene.from_buffer_copy(sc)
-            sc.packed = ctx.compat.data_ptr()
-        g_rgb = torch.zeros(N, 3, device=dev) if g_rgb is None else g_rgb.contiguous().float()
-        astride = sv["alpha"].shape[1]
+        sc = _head_scene(model.scene(training=True), plan)
+        g_rgb = torch.zeros(plan.N, 3, device=dev) if g_rgb is None else g_rgb.contiguous().float()
         if g_alpha is not None:  # ray_entropy_loss (train.py:306-309); the envmap's ones column takes no gradient
             g_alpha = g_alpha.contiguous().float()
             assert g_alpha.shape == sv["alpha"].shape
-        dens, app = table_params(model, "density"), table_params(model, "app")
         # keeps the channel-last strides of the parameters; the sorted scatters store every texel, the atomic ones add into zeros
-        sorted_dens = ctx.sort_ws is not None and model.density_n_comp[0] == 16
-        sorted_app = ctx.sort_ws is not None and (ctx.head_tuned or _generic_head_sorted_app(model, ctx.sort_ws, N * S))
-        g_dens, g_app = _zeros_like_many(dens, zero=not sorted_dens), _zeros_like_many(app, zero=not sorted_app)
-        for p, g in zip(dens + app, g_dens + g_app):
-            assert g.stride() == p.stride()
-        f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
-        dc, dfeat = f(N, S, 3), f(N, S)
-        _chk(lib.ego_march_backward(sc, sv["z"].data_ptr(), sv["alpha"].data_ptr(), astride, sv["weight"].data_ptr(),
-                                          sv["sigma"].data_ptr(), sv["bg"].data_ptr(), sv["rgb"].data_ptr(), g_rgb.data_ptr(),
-                                          _lib.ptr(g_alpha), sv["raw"].data_ptr(), _lib.ptr(sv["env"]), N, S, dc.data_ptr(),
-                                          dfeat.data_ptr(), st), "ego_march_backward")
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if SIDE_STREAM_SCATTER else None
-        gd = _grad_struct(g_dens)
-
-        def on_side(fn):
-            """Run fn(stream handle) on the side stream once everything queued on the main stream so far has finished."""
-            if side is None:
-                return fn(st)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                fn(_lib.stream_handle())
-
+        g_dens = _zeros_like_many(table_params(model, "density"), zero=not plan.sorted_dens)
+        g_app = _zeros_like_many(table_params(model, "app"), zero=not plan.sorted_app)
+        dc, dfeat = _empty(dev, plan.N, plan.S, 3), _empty(dev, plan.N, plan.S)   # d colour (-> d(pre-sigmoid) in the head backward), d density feature
+        _chk(_lib.load().ego_march_backward(sc, sv["z"].data_ptr(), sv["alpha"].data_ptr(), sv["alpha"].shape[1], sv["weight"].data_ptr(),
+                                            sv["sigma"].data_ptr(), sv["bg"].data_ptr(), sv["rgb"].data_ptr(), g_rgb.data_ptr(), _lib.ptr(g_alpha),
+                                            sv["raw"].data_ptr(), _lib.ptr(sv["env"]), plan.N, plan.S, dc.data_ptr(), dfeat.data_ptr(),
+                                            _lib.stream_handle()), "ego_march_backward")
+        side = SideStream(plan.side, dev)
         try:
-            return RenderFunction._backward_body(ctx, lib, st, model, N, S, sv, dev, M, sc, g_rgb, astride, g_dens, g_app, dc, dfeat, gd,
-                                                 main, side, on_side, f)
+            _scatter_tables(plan, sc, sv, side, "density", dfeat, g_dens)
+            if plan.head_tuned:
+                hb = _head_backward_tuned(plan, sc, sv, dc, g_app, side)
+                wg = _weight_grads_tuned(plan, model, sv, hb, dc, side)
+            else:
+                hb = _head_backward_generic(plan, sc, model, sv, dc, g_app, side)
+                wg = _weight_grads_generic(plan, model, sv, hb, dc)
+            grads = g_dens + g_app + wg
+            if sv["env"] is not None:
+                grads.append(_envmap_grad(sc, model, sv, g_rgb))
+            side.join()  # the table gradients are complete
+            return (None, None, None, *grads)
         finally:
-            # Whatever happens in between (a failing _lib.check raises), the main stream must have waited for the side stream before
-            # dfeat / dv / coords / the gradient buffer go back to the main stream's allocator pool: the side-stream kernels may still
-            # be reading or writing them.
-            if side is not None:
-                main.wait_stream(side)
+            # also when a call above raised: the main stream waits for the side stream before dfeat, dv / dfe (hb), coords and sort_ws
+            # (sv) and the gradient buffers can go back to the main stream's allocator pool
+            side.join()
             ctx.saved = None
-
-    @staticmethod
-    def _backward_body(ctx, lib, st, model, N, S, sv, dev, M, sc, g_rgb, astride, g_dens, g_app, dc, dfeat, gd, main, side, on_side, f):
-        ws = ctx.sort_ws
-        if model.density_n_comp[0] == 16 and ws is not None:
-            on_side(lambda s_: _chk(lib.ego_scatter_density_sorted(sc, C.byref(gd), sv["coords"].data_ptr(), dfeat.data_ptr(), N, S, ws.data_ptr(),
-                                                                   ws.numel(), s_), "ego_scatter_density_sorted"))
-        elif model.density_n_comp[0] == 16:
-            on_side(lambda s_: _chk(lib.ego_scatter_density(sc, C.byref(gd), sv["coords"].data_ptr(), dfeat.data_ptr(), N, S, s_),
-                                          "ego_scatter_density"))
-        else:
-            on_side(lambda s_: _chk(lib.ego_scatter_generic(C.byref(sc.density), C.byref(gd), sv["coords"].data_ptr(), dfeat.data_ptr(), 0, N, S, s_),
-                                          "ego_scatter_generic(density)"))
-        if not ctx.head_tuned:
-            return RenderFunction._backward_generic_head(ctx, lib, st, model, N, S, sv, dev, M, sc, g_rgb, g_dens, g_app, dc, main, side, on_side, f)
-        tp = f(lib.ego_train_packed_floats())
-        _chk(lib.ego_pack_train(sc, tp.data_ptr(), st), "ego_pack_train")
-        Mp = (M + 31) // 32 * 32
-        # dh2 / dh1: scaled fp16 in the kernel's own operand order + one power of two per sample (include/egonerf_hip.h); dv: blocked fp32
-        half = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float16)
-        walk_basis = ws is not None and sv["v"] is None
-        walk_dv = walk_basis and WALK_DV
-        dh2, dh1, dh_scale, dfe, dv = half(Mp, 128), half(Mp, 128), f(2, Mp), f(M, 32), (None if walk_dv else f(Mp, 144))
-        dv_absmax = f(1)   # max |dv| (walk_dv: max |dfe|), found by the backward while it holds the values: the sorted scatter's fixed-point unit comes from it
-        ds = _lib.ShadeDump(*(_lib.ptr(sv[k]) for k in ("x", "h1", "h2", "v", "relu_bits", "fe")))
-        _chk(lib.ego_shade_backward(sc, tp.data_ptr(), sv["coords"].data_ptr(), dc.data_ptr(), sv["rgb"].data_ptr(), C.byref(ds),
-                                          dh2.data_ptr(), dh1.data_ptr(), dh_scale.data_ptr(), dfe.data_ptr(), _lib.ptr(dv), dv_absmax.data_ptr(), N, S, st),
-             "ego_shade_backward")
-        ga = _grad_struct(g_app)
-        # the product buffer exists (zero-filled, on the main stream) BEFORE the side stream is allowed to write its d(basis) block into it
-        Gall = torch.zeros(352, _G_LD, device=dev)
-        if ws is not None:   # (this is the tuned-head path: sorted_app above)
-            Gb_ptr = Gall[_G_ROWS["Gb"][0]:].data_ptr() if walk_basis else None
-            on_side(lambda s_: _chk(lib.ego_scatter_app_sorted(sc, C.byref(ga), sv["coords"].data_ptr(), _lib.ptr(dv), dv_absmax.data_ptr(),
-                                                               dfe.data_ptr() if walk_basis else None, Gb_ptr, _G_LD if walk_basis else 0, N, S,
-                                                               ws.data_ptr(), ws.numel(), s_), "ego_scatter_app_sorted"))
-        else:
-            on_side(lambda s_: _chk(lib.ego_scatter_app(sc, C.byref(ga), sv["coords"].data_ptr(), dv.data_ptr(), N, S, s_), "ego_scatter_app"))
-        if side is None:
-            del dv
-        # ---- weight gradients: one pass of ego_weight_grad (bf16 hi/lo MFMA over transposed LDS tiles, bias gradients from a
-        # ones column) per layer over the dumped buffers into one product buffer, then one gather un-permutes the lane-order
-        # columns into the reference-shaped gradients ----
-        do = dc.view(M, 3)  # now d(pre-sigmoid)
-        gidx, gsizes, gshapes, pad = _grad_plan(model, dev, walk_basis)  # pad: a padding column of the x dump (holds zeros) doubles as the ones column
-        # deterministic mode (model.deterministic_scatter): per-workgroup partial products added in a fixed order instead of float atomics
-        det = model.deterministic_scatter
-        part = f(lib.ego_weight_grad_partial_floats()) if det else None
-
-        def wgrad(which, A, ca, a_layout, B, cb, ones_col, a_scale=None):
-            G = Gall[_G_ROWS[which][0]:_G_ROWS[which][1]]
-            b_layout = 2 if B.dtype == torch.float16 else 1
-            _chk(lib.ego_weight_grad_det(A.data_ptr(), A.shape[1], ca, a_layout, _lib.ptr(a_scale), B.data_ptr(), B.shape[1], cb, b_layout, ones_col, M,
-                                         G.data_ptr(), _G_LD, _lib.ptr(part), 0 if part is None else part.numel(), st), "ego_weight_grad")
-
-        wgrad("G3", do, 3, 0, sv["h2"], 128, 128)
-        wgrad("G2", dh2, 128, 2, sv["h1"], 128, 128, dh_scale[0])
-        if sv["x"] is not None:
-            wgrad("G1", dh1, 128, 2, sv["x"], 160, pad, dh_scale[1])
-        else:   # the layer-1 input re-derived from the feature slots and the rays' directions inside the product's B-tile fetch
-            G1 = Gall[_G_ROWS["G1"][0]:_G_ROWS["G1"][1]]
-            _chk(lib.ego_weight_grad_x(dh1.data_ptr(), dh_scale[1].data_ptr(), sv["fe"].data_ptr(), sv["rays"].data_ptr(), S, pad, M, G1.data_ptr(), _G_LD,
-                                       _lib.ptr(part), 0 if part is None else part.numel(), st), "ego_weight_grad")
-        if walk_basis:
-            main.wait_stream(side) if side is not None else None   # the walk's k_basis_reduce wrote Gall's Gb block on the side stream
-        else:
-            wgrad("Gb", dfe, 64, 3, sv["v"], 144, -1, sv["coords"].view(M, 4))   # 32 stored columns, routed to the yin / yang block by coords.w
-        wg = [t.view(shp) for t, shp in zip(Gall.view(-1).index_select(0, gidx).split(gsizes), gshapes)]
-        grads = g_dens + g_app + wg  # wg: basis yin, basis yang, w1, b1, w2, b2, w3, b3 (differentiable_params order)
-        if sv["env"] is not None:
-            g_em = torch.zeros_like(model.envmap.emission)
-            rays = sv["rays"]
-            _chk(lib.ego_envmap_backward(sc, rays.data_ptr() + 12, 6, g_rgb.data_ptr(), sv["raw"].data_ptr(), sv["bg"].data_ptr(),
-                                               sv["env"].data_ptr(), N, g_em.data_ptr(), st), "ego_envmap_backward")
-            grads.append(g_em)
-        if side is not None:
-            main.wait_stream(side)  # the table gradients are complete; dv / dfeat / coords may be released from here on
-        return (None, None, None, *grads)
-
-
-    @staticmethod
-    def _backward_generic_head(ctx, lib, st, model, N, S, sv, dev, M, sc, g_rgb, g_dens, g_app, dc, main, side, on_side, f):
-        """Backward of the appearance head for any model shape the compatibility kernels support (row-major buffers; the weight
-        gradients are A^T B products in 160-column blocks, already in the reference's [out][in] orientation)."""
-        hid, in_c, ncol, D = model.head_hidden, model.head_in_mlpC, 3 * model.app_n_comp[0], model.app_dim
-        rgb_head = model.shadingMode == "RGB"
-        ldx = _G_LD if rgb_head else sv["x"].shape[1]
-        # another head over the SHIPPED table shape: dv in the tuned scatters' blocked layout, and the sorted walk takes the table gradients
-        # (deterministic, 0.75 ms where the any-shape atomic scatter takes 9.8)
-        ws = ctx.sort_ws
-        app_sorted = _generic_head_sorted_app(model, ws, M)
-        dh2, dh1, dfe = (None if rgb_head else f(M, hid)), (None if rgb_head else f(M, hid)), f(M, 64)
-        dv = f((M + 31) // 32 * 32, 144) if app_sorted else f(M, _G_LD)
-        _chk(lib.ego_shade_backward_generic(sc, sv["coords"].data_ptr(), dc.data_ptr(), sv["rgb"].data_ptr(), _lib.ptr(sv["x"]), ldx,
-                                            _lib.ptr(sv["h1"]), _lib.ptr(sv["h2"]), _G_LD, _lib.ptr(dh2), _lib.ptr(dh1), dfe.data_ptr(),
-                                            dv.data_ptr(), 0 if app_sorted else _G_LD, N, S, st), "ego_shade_backward_generic")
-        ga = _grad_struct(g_app)
-        if app_sorted:
-            on_side(lambda s_: _chk(lib.ego_scatter_app_sorted(sc, C.byref(ga), sv["coords"].data_ptr(), dv.data_ptr(), None, None, None, 0, N, S,
-                                                               ws.data_ptr(), ws.numel(), s_), "ego_scatter_app_sorted(generic head)"))
-        else:
-            on_side(lambda s_: _chk(lib.ego_scatter_generic(C.byref(sc.app), C.byref(ga), sv["coords"].data_ptr(), dv.data_ptr(), _G_LD, N, S, s_),
-                                    "ego_scatter_generic(app)"))
-        hp = (hid + 31) // 32 * 32
-        n_chunks = ldx // _G_LD
-
-        part = f(lib.ego_weight_grad_partial_floats()) if model.deterministic_scatter else None
-
-        def product(A, lda, ca, B_ptr, ldb, ones_col, rows):
-            G = torch.zeros(rows, _G_LD, device=dev)
-            _chk(lib.ego_weight_grad_det(A.data_ptr(), lda, ca, 0, None, B_ptr, ldb, _G_LD, 0, ones_col, M, G.data_ptr(), _G_LD, _lib.ptr(part),
-                                         0 if part is None else part.numel(), st), "ego_weight_grad")
-            return G
-
-        Gb = product(dfe, 64, 64, sv["v"].data_ptr(), _G_LD, -1, 64)                      # [yin | yang] feature gradients ^T v
-        wg = [Gb[0:D, :ncol].contiguous(), Gb[32:32 + D, :ncol].contiguous()]
-        if not rgb_head:
-            G3 = product(dc.view(M, 3), 3, 3, sv["h2"].data_ptr(), _G_LD, hid, 32)          # do^T [h2 | 1]
-            G2 = product(dh2, hid, hid, sv["h1"].data_ptr(), _G_LD, hid, hp)                  # dh2^T [h1 | 1]
-            G1 = []
-            for c in range(n_chunks):
-                c0 = c * _G_LD
-                ones = in_c - c0 if c0 <= in_c < c0 + _G_LD else -1                          # the first zero-padding column doubles as the ones column
-                G1.append(product(dh1, hid, hid, sv["x"].data_ptr() + 4 * c0, ldx, ones, hp))
-            G1 = torch.cat(G1, dim=1)
-            wg += [G1[:hid, :in_c].contiguous(), G1[:hid, in_c].contiguous(), G2[:hid, :hid].contiguous(), G2[:hid, hid].contiguous(),
-                   G3[:3, :hid].contiguous(), G3[:3, hid].contiguous()]
-        grads = g_dens + g_app + wg
-        if sv["env"] is not None:
-            g_em = torch.zeros_like(model.envmap.emission)
-            rays = sv["rays"]
-            _chk(lib.ego_envmap_backward(sc, rays.data_ptr() + 12, 6, g_rgb.data_ptr(), sv["raw"].data_ptr(), sv["bg"].data_ptr(),
-                                         sv["env"].data_ptr(), N, g_em.data_ptr(), st), "ego_envmap_backward")
-            grads.append(g_em)
-        if side is not None:
-            main.wait_stream(side)
-        return (None, None, None, *grads)
 
 
 class EnvRadianceFunction(torch.autograd.Function):
