@@ -1,0 +1,182 @@
+// Camera paths on the device (include/egonerf_hip.h: ego_camera_rays, ego_finish_frame): the two ends of the reference's
+// evaluation_path (renderer.py:199-255).  ego_camera_rays generates the rays of a window of pixels of an equirectangular or pinhole
+// camera from a pose that lives in device memory, so a captured frame follows a pose that is overwritten between replays;
+// ego_finish_frame turns a chunk's float32 colour and depth into the 8-bit images the reference writes (clamp, * 255, truncate;
+// depth -> 8-bit index -> palette), straight into device memory or mapped pinned host memory.
+//
+// Both kernels are one thread per pixel (per four pixels for the bytes) over at most a few million elements: bound by their stores,
+// a few microseconds per chunk next to a render of about a millisecond; nothing here wants LDS or the matrix pipe.
+#include "ego_device.h"
+#include "ego_host.h"
+
+namespace {
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct CamArgs {
+  int32_t model, H, W, normalize;
+  float fx, fy, cx, cy;
+};
+
+__global__ __launch_bounds__(256) void k_camera_rays(CamArgs c, const float* __restrict__ pose, int64_t first, int64_t count,
+                                                     float* __restrict__ rays) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const int64_t p = first + i;
+  const int row = (int)(p / c.W), col = (int)(p - (int64_t)row * c.W);
+  float o[6];
+  if (c.model == EGO_CAM_ERP) {
+    erp_ray(c.H, c.W, row, col, pose, c.normalize, o);   // ego_device.h: the body ego_erp_rays runs
+  } else {
+    // get_ray_directions / get_ray_directions_blender (dataLoader/ray_utils.py:43-82): grid + 0.5, (i - cx) / fx, (j - cy) / fy, 1 -
+    // every operation rounded on its own, true divisions - then get_rays (:85-113): d = R dir, o = t, no normalisation
+    const float x = __fdiv_rn(__fsub_rn((float)col + 0.5f, c.cx), c.fx);
+    float y = __fdiv_rn(__fsub_rn((float)row + 0.5f, c.cy), c.fy), z = 1.f;
+    if (c.model == EGO_CAM_PINHOLE_BLENDER) { y = -y; z = -1.f; }
+    o[0] = pose[3]; o[1] = pose[7]; o[2] = pose[11];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      o[3 + r] = __fadd_rn(__fadd_rn(__fmul_rn(x, pose[4 * r]), __fmul_rn(y, pose[4 * r + 1])), __fmul_rn(z, pose[4 * r + 2]));
+  }
+  f32x2* out = (f32x2*)(rays + i * 6);   // 24 bytes per row: 8-byte aligned whenever `rays` is (checked by the entry point)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = f32x2{o[2 * k], o[2 * k + 1]};
+}
+
+struct FinishArgs {
+  const float* rgb;       // [count][3]
+  const float* depth;     // [count]
+  int64_t first, count;
+  int32_t W, side_by_side;
+  float mi, den;
+  const uint8_t* palette; // [256][3] or null
+  uint8_t* rgb8;          // frame base: [n][3], or [H][2W][3] side by side
+  uint8_t* depth8;        // frame base: [n][3] with a palette, [n] without; unused side by side
+};
+
+// (rgb.clamp(0, 1) * 255).astype('uint8') of renderer.py:227, :233: float32 multiply, truncation
+__device__ __forceinline__ uint32_t quantise_colour(float v) {
+  const float c = fminf(fmaxf(v, 0.f), 1.f);   // fmaxf(NaN, 0) = 0: a NaN colour, undefined in the reference's cast, becomes 0
+  return (uint32_t)(int)__fmul_rn(c, 255.f);
+}
+
+// visualize_depth_numpy (utils.py:14-25): (255 * ((nan_to_num(depth) - mi) / den)).astype(uint8), saturated to [0, 255] where the
+// reference's cast is undefined
+__device__ __forceinline__ uint32_t depth_index(float d, float mi, float den) {
+  float x = (d != d) ? 0.f : d;                                   // np.nan_to_num: NaN -> 0, +-inf -> +-FLT_MAX
+  x = fminf(fmaxf(x, -3.402823466e+38f), 3.402823466e+38f);
+  const float v = __fmul_rn(255.f, __fdiv_rn(__fsub_rn(x, mi), den));
+  if (!(v >= 0.f)) return 0u;
+  return v >= 255.f ? 255u : (uint32_t)(int)v;
+}
+
+// 12 bytes (four pixels of three channels) to `dst`: three whole words where `dst` is 4-byte aligned, bytes otherwise
+__device__ __forceinline__ void store12(uint8_t* dst, const uint32_t b[12]) {
+  if (((uintptr_t)dst & 3) == 0) {
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+      ((uint32_t*)dst)[w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dst[k] = (uint8_t)b[k];
+  }
+}
+
+// One thread per group of four pixels [4 g, 4 g + 4) of the FRAME (not of the chunk), so a group's 12 output bytes start on a word of
+// an aligned image wherever the chunk begins; a group cut by the chunk's ends or by the end of an image row (side by side: the two
+// halves of an output row are not contiguous) is written pixel by pixel.
+__global__ __launch_bounds__(256) void k_finish_frame(FinishArgs a) {
+  const int64_t g = a.first / 4 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t p0 = g * 4, end = a.first + a.count;
+  if (p0 >= end) return;
+  const int64_t lo = p0 < a.first ? a.first : p0, hi = p0 + 4 > end ? end : p0 + 4;
+  uint32_t c8[12], d8[12], idx[4];
+  for (int64_t p = lo; p < hi; ++p) {
+    const int k = (int)(p - p0);
+    const int64_t s = p - a.first;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) c8[3 * k + ch] = quantise_colour(a.rgb[s * 3 + ch]);
+    idx[k] = depth_index(a.depth[s], a.mi, a.den);
+    if (a.palette) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) d8[3 * k + ch] = a.palette[idx[k] * 3 + ch];
+    }
+  }
+  const bool full = lo == p0 && hi == p0 + 4;
+  if (a.side_by_side) {
+    const int64_t row = p0 / a.W;
+    const int col = (int)(p0 - row * a.W);
+    uint8_t* left = a.rgb8 + (row * 2 * a.W + col) * 3;
+    if (full && col + 4 <= a.W) {
+      store12(left, c8);
+      store12(left + (int64_t)a.W * 3, d8);
+    } else {
+      for (int64_t p = lo; p < hi; ++p) {
+        const int k = (int)(p - p0);
+        const int64_t r = p / a.W;
+        uint8_t* l = a.rgb8 + (r * 2 * a.W + (p - r * a.W)) * 3;
+        for (int ch = 0; ch < 3; ++ch) { l[ch] = (uint8_t)c8[3 * k + ch]; l[(int64_t)a.W * 3 + ch] = (uint8_t)d8[3 * k + ch]; }
+      }
+    }
+    return;
+  }
+  if (full) {
+    store12(a.rgb8 + p0 * 3, c8);
+    if (a.palette) store12(a.depth8 + p0 * 3, d8);
+    else if (((uintptr_t)a.depth8 & 3) == 0) ((uint32_t*)a.depth8)[g] = idx[0] | (idx[1] << 8) | (idx[2] << 16) | (idx[3] << 24);
+    else for (int k = 0; k < 4; ++k) a.depth8[p0 + k] = (uint8_t)idx[k];
+    return;
+  }
+  for (int64_t p = lo; p < hi; ++p) {
+    const int k = (int)(p - p0);
+    for (int ch = 0; ch < 3; ++ch) a.rgb8[p * 3 + ch] = (uint8_t)c8[3 * k + ch];
+    if (a.palette) for (int ch = 0; ch < 3; ++ch) a.depth8[p * 3 + ch] = (uint8_t)d8[3 * k + ch];
+    else a.depth8[p] = (uint8_t)idx[k];
+  }
+}
+
+inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+}  // namespace
+
+extern "C" {
+
+int ego_camera_rays(int32_t model, int32_t H, int32_t W, float fx, float fy, float cx, float cy, int32_t normalize, const float* c2w,
+                    int64_t first, int64_t count, float* rays, void* stream) {
+  EGO_TRACE("ego_camera_rays");
+  EGO_REQUIRE(model == EGO_CAM_ERP || model == EGO_CAM_PINHOLE || model == EGO_CAM_PINHOLE_BLENDER, "camera_rays: unknown camera model");
+  EGO_REQUIRE(H >= 1 && W >= 1, "camera_rays: H or W < 1");
+  EGO_REQUIRE(first >= 0 && count >= 0 && first <= (int64_t)H * W && count <= (int64_t)H * W - first,
+              "camera_rays: pixel window [first, first + count) outside the image");
+  if (model != EGO_CAM_ERP) {
+    EGO_REQUIRE(fx == fx && fy == fy && fx != 0.f && fy != 0.f && fabsf(fx) <= 3.402823466e+38f && fabsf(fy) <= 3.402823466e+38f,
+                "camera_rays: a pinhole camera needs a finite, non-zero focal length (fx, fy)");
+    EGO_REQUIRE(cx == cx && cy == cy, "camera_rays: NaN principal point");
+  }
+  if (count == 0) return EGO_OK;
+  EGO_REQUIRE(c2w && rays, "camera_rays: null argument");
+  EGO_REQUIRE(((uintptr_t)rays & 7) == 0 && ((uintptr_t)c2w & 3) == 0, "camera_rays: rays must be 8-byte, c2w 4-byte aligned");
+  const CamArgs c{model, H, W, normalize, fx, fy, cx, cy};
+  k_camera_rays<<<nblk(count, 256), 256, 0, (hipStream_t)stream>>>(c, c2w, first, count, rays);
+  return ego_launch_status("k_camera_rays");
+}
+
+int ego_finish_frame(const float* rgb, const float* depth, int64_t first, int64_t count, int32_t H, int32_t W, float mi, float den,
+                     const uint8_t* palette, int32_t side_by_side, uint8_t* rgb8, uint8_t* depth8, void* stream) {
+  EGO_TRACE("ego_finish_frame");
+  EGO_REQUIRE(H >= 1 && W >= 1, "finish_frame: H or W < 1");
+  EGO_REQUIRE(first >= 0 && count >= 0 && first <= (int64_t)H * W && count <= (int64_t)H * W - first,
+              "finish_frame: pixel window [first, first + count) outside the image");
+  EGO_REQUIRE(mi == mi && den == den && den != 0.f, "finish_frame: mi / den must be numbers, den non-zero");
+  EGO_REQUIRE(!side_by_side || palette, "finish_frame: the side-by-side layout needs a palette (three-channel depth)");
+  if (count == 0) return EGO_OK;
+  EGO_REQUIRE(rgb && depth && rgb8 && (side_by_side || depth8), "finish_frame: null argument");
+  FinishArgs a;
+  a.rgb = rgb; a.depth = depth; a.first = first; a.count = count; a.W = W; a.side_by_side = side_by_side ? 1 : 0;
+  a.mi = mi; a.den = den; a.palette = palette; a.rgb8 = rgb8; a.depth8 = depth8;
+  const int64_t groups = (first + count + 3) / 4 - first / 4;
+  k_finish_frame<<<nblk(groups, 256), 256, 0, (hipStream_t)stream>>>(a);
+  return ego_launch_status("k_finish_frame");
+}
+
+}  // extern "C"

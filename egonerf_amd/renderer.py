@@ -165,6 +165,10 @@ def erp_rays(H: int, W: int, c2w, device, row0: int = 0, n_rows: Optional[int] =
     return rays
 
 
+# camera paths (renderer.py:199-255, evaluation_path): egonerf_amd/camera.py
+from .camera import FrameRenderer, camera_rays, evaluation_path, finish_frame  # noqa: E402,F401
+
+
 # ---------------------------------------------------------------------------------------------------
 # ray sharding + PSNR reduction (one process per GPU)
 # ---------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@
  *   ego_erp_rays            get_ray_directions_360 + get_rays      dataLoader/ray_utils.py:24-40, :85-113
  *   ego_ray_batch_gather    allrays[ids], allrgbs[ids]            train.py:247-248, dataLoader/dataset_omniblender.py:71-84
  *   ego_ray_batch_sample    SimpleSampler / ThetaImportanceSampler.nextids   sampler.py:4-38 (device generator, not numpy's stream)
+ *   ego_camera_rays         get_ray_directions{,_blender,_360} + get_rays   dataLoader/ray_utils.py:24-113 (pose in device memory)
+ *   ego_finish_frame        clamp, * 255, uint8; visualize_depth_numpy; rgbd   renderer.py:227-240, :141-174, utils.py:14-27
  *   ego_sample_ray_exp      EgoNeRF.sample_ray_exp                models/EgoNeRF.py:56-87
  *   ego_from_cartesian      YinYangSphericalCoords.from_cartesian  models/coordinates.py:468-498
  *   ego_normalize_coord     YinYangSphericalCoords.normalize_coord models/coordinates.py:442-466 (+ :110-131)
@@ -219,6 +221,44 @@ int ego_ray_batch_gather(const ego_ray_bank* bank, const int64_t* idx, int64_t B
 enum { EGO_BATCH_SIMPLE = 0, EGO_BATCH_THETA = 1 };
 int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, const int64_t* counter, const float* row_cdf, int64_t B,
                          int64_t* idx, float* rays, float* rgb, void* stream);
+
+/* ---- camera paths (csrc/ego_camera.hip; append-only additions, EGO_ABI_VERSION stays 17: no existing symbol, struct or argument list
+ * changed): the two ends of evaluation_path (renderer.py:199-255) and of the tail of evaluation (renderer.py:141-174) ---- */
+enum { EGO_CAM_ERP = 0, EGO_CAM_PINHOLE = 1, EGO_CAM_PINHOLE_BLENDER = 2 };
+
+/* Rays [count][6] (8-byte aligned, dev) of pixels [first, first + count) - row-major pixel index row * W + col - of an H x W image, for the
+ * camera-to-world pose c2w: DEVICE memory, [3][4] row-major, read by the kernel, so a captured launch follows a pose that is overwritten
+ * between replays (ego_erp_rays takes a host pointer).  A chunk of an image is generated in place: no full-image ray array.
+ * EGO_CAM_ERP: get_ray_directions_360 + get_rays (dataLoader/ray_utils.py:24-40, :85-113) with `normalize` as ego_erp_rays; every row has
+ *   the bits of the row ego_erp_rays writes for that pixel (one device function computes both).  fx, fy, cx, cy are ignored.
+ * EGO_CAM_PINHOLE: get_ray_directions (dataLoader/ray_utils.py:43-61): dir = ((col + 0.5 - cx) / fx, (row + 0.5 - cy) / fy, 1); the
+ *   reference's default centre is cx = W / 2, cy = H / 2 (the caller passes it).
+ * EGO_CAM_PINHOLE_BLENDER: get_ray_directions_blender (dataLoader/ray_utils.py:64-82): the same with y and z negated.
+ * Both pinhole models continue with get_rays (dataLoader/ray_utils.py:85-113): d = R dir, o = t, NOT normalised, as there; `normalize` is
+ * ignored.  Every operation is rounded on its own in float32, in the reference's order, with true divisions: the camera-space direction has
+ * the bits of the float32 torch computation; the three-term dot products are summed left to right ((x R0 + y R1) + z R2) without fused
+ * multiply-adds.  count == 0 is a no-op; bad sizes, a window outside the image or a pinhole camera without a finite non-zero focal length
+ * return EGO_E_BADARG before anything is queued. */
+int ego_camera_rays(int32_t model, int32_t H, int32_t W, float fx, float fy, float cx, float cy, int32_t normalize, const float* c2w,
+                    int64_t first, int64_t count, float* rays, void* stream);
+
+/* The frame products of renderer.py:227-240 (evaluation_path) and :141-174 (evaluation) for pixels [first, first + count) of an H x W frame:
+ * rgb [count][3], depth [count] float32 dev (the chunk) -> bytes at those pixels' places in whole-frame images (rgb8, depth8 = the FRAME's
+ * base pointers; device memory or mapped pinned host memory, whole 4-byte words are written where the images are 4-byte aligned).
+ *   colour: rgb8 = (uint8)(clamp(rgb, 0, 1) * 255), float32 multiply, truncation: `(rgb_map.clamp(0, 1).numpy() * 255).astype('uint8')`
+ *     (renderer.py:227, :233).
+ *   depth index: idx8 = (uint8)(255 * ((nan_to_num(depth) - mi) / den)), every operation rounded on its own in float32:
+ *     visualize_depth_numpy (utils.py:14-25), where the host passes mi = float32(near) and den = float32(far - near + 1e-8), the sum formed in
+ *     double precision as Python does.
+ *   palette: dev [256][3] uint8 or NULL.  With one, depth8 [H W][3] = palette[idx8] (utils.py:26, cv2.applyColorMap: the caller supplies
+ *     the table, none is embedded); without, depth8 [H W] = idx8.
+ *   side_by_side != 0: rgb8 is the reference's `rgbd` image [H][2 W][3] = concatenate((rgb, depth colours), axis=1) (renderer.py:239);
+ *     needs a palette, depth8 is not used.
+ * DELIBERATE DEVIATION: an index outside [0, 256) - depth below near or above far - SATURATES to 0 / 255 here.  The reference's
+ * float -> uint8 cast is undefined behaviour in C for such values and wraps modulo 256 in numpy on x86 (a depth just above far comes out
+ * near 0); a NaN colour likewise becomes 0. */
+int ego_finish_frame(const float* rgb, const float* depth, int64_t first, int64_t count, int32_t H, int32_t W, float mi, float den,
+                     const uint8_t* palette, int32_t side_by_side, uint8_t* rgb8, uint8_t* depth8, void* stream);
 
 int ego_from_cartesian(const ego_scene* sc, const float* xyz, int64_t M, float* c7, void* stream);
 int ego_normalize_coord(const ego_scene* sc, const float* c7, int64_t M, float* c7n, void* stream);
