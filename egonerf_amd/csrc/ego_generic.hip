@@ -1,6 +1,6 @@
 // libegonerf_hip.so, part 7: the render path for model shapes OTHER than the one every shipped config resolves to
 // (opt.py:87-100 lets a user set n_lamb_sigma / n_lamb_sh, data_dim_color, featureC, view_pe, fea_pe).  The MFMA kernels of
-// ego_shade.hip bake 48 appearance components, app_dim 27, a 150 -> 128 -> 128 -> 3 MLP with two encoding frequencies and 16
+// ego_shade.hip / ego_train.hip (shape: ego_tuned.h) bake 48 appearance components, app_dim 27, a 150 -> 128 -> 128 -> 3 MLP with two encoding frequencies and 16
 // density components into their register layouts; these kernels take the shape as runtime numbers (hidden width as a template
 // parameter) and compute in plain fp32 with the reference's operation order, so that any reference checkpoint renders on the
 // device.  They are a compatibility path, an order of magnitude slower than the tuned one (forward AND, since round 4, backward); the
@@ -876,7 +876,7 @@ __device__ __forceinline__ float gen_row_sum16(float v) {
 }
 
 // A 16-lane group per (sample, plane), lane = channel (16 at a time): every gather and every atomic of a group is one 64-byte line, as in
-// the tuned k_vm_scatter (ego_train.inc) but without its run merging.  (Rounds 2-5 had a THREAD per (sample, plane): 64 lanes = 64 texels
+// the tuned k_vm_scatter (ego_train.hip) but without its run merging.  (Rounds 2-5 had a THREAD per (sample, plane): 64 lanes = 64 texels
 // = 64 lines per atomic instruction, 105 ms for the shipped tables at 8192 x 256 - 71 % of a training step of the other heads.)
 __global__ __launch_bounds__(256) void k_scatter_generic(GenScatterArgs A) {
 #pragma clang fp contract(fast)

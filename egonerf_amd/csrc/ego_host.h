@@ -1,4 +1,5 @@
-// Host-side error plumbing shared by the translation units of libegonerf_hip.so.
+// Host-side error plumbing shared by the translation units of libegonerf_hip.so.  (The tuned shape's shared constants, K orders and
+// host checks are in ego_tuned.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

@@ -2,7 +2,7 @@
 // item 3).  Backward of F.grid_sample in compute_densityfeature / compute_appfeature (models/EgoNeRF.py:291-347, :349-413) under
 // train.py:312-314, for the tuned table shapes (16 density / 48 appearance components).
 //
-// k_vm_scatter (ego_train.inc) walks rays and sends one float-atomic line per (cell run, tap): ~16 M atomic line requests per 8192 x 256
+// k_vm_scatter (ego_train.hip) walks rays and sends one float-atomic line per (cell run, tap): ~16 M atomic line requests per 8192 x 256
 // step at the L2's ~21 G/s plus ~0.95 ms of cell bookkeeping, and a sum whose order changes from run to run.  Here the step's samples are
 // binned by texel CELL once (three stable LSD radix sorts of 18-bit keys, 9 bits per pass, all three sorts in the same launches:
 // k_radix_hist / k_radix_scan / k_radix_scatter below), and every gradient texel is then written exactly once from sums taken in a
@@ -1160,7 +1160,7 @@ __device__ __forceinline__ void walk_split4(const float x[4], walk_s4& hi, walk_
 }
 
 // x (already scaled into fp16's normal range: |x| < 2^13) = hi + lo + O(2^-21 |x|) as two fp16: hi rounded to nearest, lo = the exact fp32
-// residual cut to fp16 - the operand form of k_shade_bwd's data-gradient chain (ego_train.inc: split8_rn), here for v_mfma_f32_16x16x16_f16
+// residual cut to fp16 - the operand form of k_shade_bwd's data-gradient chain (ego_train.hip: split8_rn), here for v_mfma_f32_16x16x16_f16
 typedef _Float16 walk_h4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void walk_split4_f16(const float x[4], walk_h4& hi, walk_h4& lo) {
   typedef float f2v __attribute__((ext_vector_type(2)));
@@ -1176,7 +1176,7 @@ __device__ __forceinline__ void walk_split4_f16(const float x[4], walk_h4& hi, w
   hi = __builtin_bit_cast(walk_h4, u32x2_w{hw[0], hw[1]});
   lo = __builtin_bit_cast(walk_h4, u32x2_w{lw[0], lw[1]});
 }
-// the power of two that takes amax into [2^12, 2^13) and its inverse (1 for zero, subnormal and non-finite amax), as ego_train.inc's sample_scale
+// the power of two that takes amax into [2^12, 2^13) and its inverse (1 for zero, subnormal and non-finite amax), as ego_train.hip's sample_scale
 __device__ __forceinline__ float walk_pow2_scale(float amax, float& inv) {
   const int e = (__float_as_int(amax) >> 23) & 0xff;
   const int k = (e == 0 || e > 254) ? 0 : 139 - e;

@@ -2,412 +2,16 @@
 // fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains, so parity with the reference's
 // fp32 Linear layers is rounding-order only).
 //
-// Work mapping (wave64): a wave owns a tile of 32 consecutive samples; lane l serves sample
-// j = l & 31 and "half" h = l >> 5.  In D = A*B (32x32x2): A[i][k] comes from lane (i, k) = (l&31, l>>5),
-// B[k][j] from lane (j, k) = (l&31, l>>5), and D[i][j] lands in lane j + 32*((i>>2)&1), register
-// r = (i&3) + 4*(i>>3).  So with samples on the N axis a lane only ever supplies / receives values of
-// ITS OWN sample: the gathered products feed the basis MFMAs straight from registers, the basis
-// output feeds layer 1, layer 1 feeds layer 2 — no cross-lane traffic, no LDS round trip for
-// activations.  The price is a fixed K-order per lane half, which ego_pack_mlp bakes into the weights:
-//   * lane half h gathers appearance channels [24h, 24h+24) of each of the 3 planes  (72 k-steps)
-//   * basis rows are permuted so half h receives features f = 2r + h in register r   (14 slots)
-//   * layer-1 k-steps: 14 slots x (f, sin f, sin 2f, cos f, cos 2f) + 8 view slots + 2 zero pads = 80
-//     (slot-major, so each encoding is produced right before the MFMAs that consume it)
-//   * layer-2 k-step m*16 + r consumes hidden unit m*32 + (r&3) + 8*(r>>2) + 4h
-// Layer 3 (128 -> 3) runs on the VALU from the layer-2 accumulators + one xor-32 exchange.
+// The work mapping (a wave owns a tile of 32 samples, lane l serves sample l & 31 and half l >> 5) and the K order per lane half
+// that the packers bake into the weights are described in ego_tuned.h.
 //
 // W1/W2/W3/biases (150.5 KB packed) live in LDS for the whole persistent workgroup (8 waves = 2 per
 // SIMD, so one wave's gather overlaps the other's MFMA chain); the basis fragments stream from L2.
-#include "ego_device.h"
-#include "ego_host.h"
+#include "ego_tuned.h"
 #include "variants.h"
 #include "ego_generic.h"
 
 namespace {
-
-constexpr int APP_C = 48;      // appearance components per plane
-constexpr int APP_HALF = 24;   // channels gathered by one lane half
-constexpr int APP_DIM = 27;
-constexpr int HID = 128;
-constexpr int NSLOT = 14;      // feature slots per lane half
-constexpr int KS_BASIS = 72;
-constexpr int KS1 = 80;
-constexpr int KS2 = 64;
-constexpr int MLP_IN = 150;
-
-constexpr int OFF_W1 = 0;                           // [KS1/4][4 m][64 lanes][4]
-constexpr int OFF_W2 = OFF_W1 + KS1 * 4 * 64;       // [KS2/4][4 m][64][4]
-constexpr int OFF_B1 = OFF_W2 + KS2 * 4 * 64;       // [4 m][2 h][16 r]
-constexpr int OFF_B2 = OFF_B1 + 128;
-constexpr int OFF_W3 = OFF_B2 + 128;                // [4 m][2 h][16 r][4 (c0,c1,c2,0)]
-constexpr int OFF_B3 = OFF_W3 + 512;                // [4]
-constexpr int LDS_W_FLOATS = OFF_B3 + 4;            // 37636 floats = 150544 B
-constexpr int OFF_BASIS = LDS_W_FLOATS;             // [2 g][KS_BASIS/4][64][4]
-constexpr int PACKED_FLOATS = OFF_BASIS + 2 * (KS_BASIS / 4) * 64 * 4;
-constexpr int LUT_MAX = 1024;
-
-__host__ __device__ constexpr int slot_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// appearance channel (0..143, plane-major) gathered by lane half h as its kk-th product: the halves interleave at
-// 16-byte granularity (half h owns float4 quads 2i+h of a texel), so the two lanes of a sample always read the
-// same 64-byte line in a given load instruction -> half as many L1 tag lookups as a [0,24) / [24,48) split.
-// K order of the f16x3 kernel's gather (gather_team4 below): samples are gathered by 4-lane teams (part p reads quad
-// 4i+p of line i, so a team reads whole 64-byte lines) and transposed into the 2-lanes-per-sample MFMA layout with
-// v_permlane16_swap + v_permlane32_swap.  Lane half h ends up with the parts p = h (first 12 products of a plane) and
-// p = h + 2 (next 12): product kk = plane*24 + half*12 + i*4 + c is channel plane*48 + 16i + 4(h + 2 half) + c.
-// Activation dumps of the training forward / backward (logical [M][2 K] matrices: x 160, h1/h2/dh1/dh2 128, v 144 columns).
-// Logical column of element kk of lane half h: dump_col(kk, h) (the float4 quads of the two halves interleave).  Storage is
-// tile-blocked and lane-major: [tile = m / 32][quad pair q = kk / 4][lane = 32 h + (m % 32)][4 floats], so every store / load
-// instruction of the shade kernels moves 1 KB of contiguous memory (row-major rows gave 32-byte pieces 640 B apart and
-// 2.5 TB/s; this layout 1.88 -> 1.37 ms for the dumping forward).  Buffers hold ceil(M / 32) * 32 rows.
-__host__ __device__ constexpr int64_t dump_off(int64_t tile, int width, int q, int h, int j) {
-  return tile * (32 * (int64_t)width) + q * 256 + (h * 32 + j) * 4;
-}
-__host__ __device__ constexpr int dump_col(int kk, int h) { return (kk >> 2) * 8 + h * 4 + (kk & 3); }
-
-__host__ __device__ constexpr int app_channel_g(int kk, int h) {
-  return (kk / APP_HALF) * APP_C + (((kk % APP_HALF) % 12) / 4) * 16 + 4 * (h + 2 * ((kk % APP_HALF) / 12)) + (kk % 4);
-}
-
-// (fp32-MFMA kernel k_shade: lane half h owns float4 quads 2i+h)
-__host__ __device__ constexpr int app_channel(int kk, int h) {
-  return (kk / APP_HALF) * APP_C + ((kk % APP_HALF) / 4) * 8 + 4 * h + (kk % 4);
-}
-
-// reference MLP input column held by X register kk of lane half h (-1: zero weight)
-__device__ int x_channel(int kk, int h) {
-  if (kk < 5 * NSLOT) {
-    const int kind = kk % 5, r = kk / 5, f = 2 * r + h;
-    if (f >= APP_DIM) return -1;
-    const int pe0 = APP_DIM + 3;               // 30: sin block of the feature PE
-    const int pe1 = pe0 + 2 * APP_DIM;         // 84: cos block
-    switch (kind) {
-      case 0: return f;
-      case 1: return pe0 + 2 * f;
-      case 2: return pe0 + 2 * f + 1;
-      case 3: return pe1 + 2 * f;
-      default: return pe1 + 2 * f + 1;
-    }
-  }
-  if (kk < 5 * NSLOT + 8) {
-    const int t = (kk - 5 * NSLOT) + 8 * h;
-    // d0 d1 d2 | sin d0, sin 2d0, sin d1, sin 2d1, sin d2, sin 2d2 | cos ... | pad
-    return t < 3 ? APP_DIM + t : (t < 15 ? 138 + (t - 3) : -1);
-  }
-  return -1;
-}
-
-__global__ void k_pack_mlp(const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
-                           const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3,
-                           const float* __restrict__ basis_yin, const float* __restrict__ basis_yang,
-                           float* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= PACKED_FLOATS) return;
-  float v = 0.f;
-  if (idx < OFF_W2) {  // W1 fragments
-    const int j = idx & 3, lane = (idx >> 2) & 63, m = (idx >> 8) & 3, kk4 = idx >> 10;
-    const int ch = x_channel(kk4 * 4 + j, lane >> 5);
-    if (ch >= 0) v = w1[(m * 32 + (lane & 31)) * MLP_IN + ch];
-  } else if (idx < OFF_B1) {  // W2 fragments
-    const int e = idx - OFF_W2;
-    const int j = e & 3, lane = (e >> 2) & 63, m2 = (e >> 8) & 3, kk4 = e >> 10;
-    const int kk = kk4 * 4 + j;
-    v = w2[(m2 * 32 + (lane & 31)) * HID + (kk >> 4) * 32 + slot_row(kk & 15, lane >> 5)];
-  } else if (idx < OFF_W3) {  // biases of layers 1, 2 in accumulator layout
-    const int e = (idx - OFF_B1) & 127;
-    const float* b = (idx < OFF_B2) ? b1 : b2;
-    v = b[(e >> 5) * 32 + slot_row(e & 15, (e >> 4) & 1)];
-  } else if (idx < OFF_B3) {  // W3 in accumulator layout
-    const int e = idx - OFF_W3;
-    const int c = e & 3, r = (e >> 2) & 15, h = (e >> 6) & 1, m = e >> 7;
-    if (c < 3) v = w3[c * HID + m * 32 + slot_row(r, h)];
-  } else if (idx < OFF_BASIS) {
-    const int c = idx - OFF_B3;
-    if (c < 3) v = b3[c];
-  } else {  // basis fragments
-    const int e = idx - OFF_BASIS;
-    const int j = e & 3, lane = (e >> 2) & 63, kk4 = (e >> 8) % (KS_BASIS / 4), g = e / (KS_BASIS / 4 * 256);
-    const int i = lane & 31, h = lane >> 5, kk = kk4 * 4 + j;
-    const int rh = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3), f = 2 * r + rh;  // feature delivered to tile row i
-    if (r < NSLOT && f < APP_DIM) {
-      const int col = app_channel(kk, h);
-      v = (g ? basis_yang : basis_yin)[f * (3 * APP_C) + col];
-    }
-  }
-  out[idx] = v;
-}
-
-// ---- fp16-split ("f16x3") weight layout ------------------------------------------------------------------
-// Same regions/offsets as the fp32 blob, but the three matrix regions hold fp16 pairs: w = hi + lo with
-// hi = fp16(w), lo = fp16(w - hi) (22 significant bits).  Fragment order [k-step][m-tile][term hi|lo][lane][8 k]:
-// one ds_read_b128 / global_load_dwordx4 per (step, tile, term) per lane, conflict-free.  A lane's 8 k of a step
-// are its values 8*step .. 8*step+7 in the same per-half K order as the fp32 layout.
-constexpr int KH1 = KS1 / 8, KH2 = KS2 / 8, KHB = KS_BASIS / 8;
-constexpr int BASIS16_FLOATS_C = 2 * KHB * 2 * 64 * 4;  // third blob region (basis fragments for the fp16-table gather)
-
-__device__ inline void split_weight(float w, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)w;
-  lo = (_Float16)(w - (float)hi);
-}
-
-__global__ void k_pack_mlp_h(const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
-                             const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3,
-                             const float* __restrict__ basis_yin, const float* __restrict__ basis_yang,
-                             const float* __restrict__ f32_blob, float* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // one 32-bit slot = two fp16
-  if (idx >= PACKED_FLOATS) return;
-  if (idx >= OFF_B1 && idx < OFF_BASIS) { out[idx] = f32_blob[idx]; return; }  // biases, W3, b3 stay fp32
-  _Float16 pr[2];
-  for (int p = 0; p < 2; ++p) {
-    float w = 0.f;
-    int term;
-    if (idx < OFF_W2) {
-      const int hidx = (idx - OFF_W1) * 2 + p;
-      const int e = hidx & 7, lane = (hidx >> 3) & 63, step = hidx >> 12, mt = (hidx >> 10) & 3;
-      term = (hidx >> 9) & 1;
-      const int ch = x_channel(step * 8 + e, lane >> 5);
-      if (ch >= 0) w = w1[(mt * 32 + (lane & 31)) * MLP_IN + ch];
-    } else if (idx < OFF_B1) {
-      const int hidx = (idx - OFF_W2) * 2 + p;
-      const int e = hidx & 7, lane = (hidx >> 3) & 63, step = hidx >> 12, mt = (hidx >> 10) & 3;
-      term = (hidx >> 9) & 1;
-      const int kk = step * 8 + e;
-      w = w2[(mt * 32 + (lane & 31)) * HID + (kk >> 4) * 32 + slot_row(kk & 15, lane >> 5)];
-    } else {
-      const int hidx = (idx - OFF_BASIS) * 2 + p;
-      const int e = hidx & 7, lane = (hidx >> 3) & 63, sg = hidx >> 10;  // sg = g * KHB + step
-      term = (hidx >> 9) & 1;
-      const int g = sg / KHB, kk = (sg % KHB) * 8 + e;
-      const int i = lane & 31, h = lane >> 5;
-      const int rh = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3), f = 2 * r + rh;
-      if (r < NSLOT && f < APP_DIM) {
-        const int col = app_channel_g(kk, h);
-        w = (g ? basis_yang : basis_yin)[f * (3 * APP_C) + col];
-      }
-    }
-    _Float16 hi, lo;
-    split_weight(w, hi, lo);
-    pr[p] = term ? lo : hi;
-  }
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-  h2v v = {pr[0], pr[1]};
-  out[idx] = __builtin_bit_cast(float, v);
-}
-
-// basis fragments for the fp16-table gather: same [g][step][term][lane][8] order, columns follow app_channel_f16
-__host__ __device__ constexpr int app_channel_f16_fwd(int kk, int h) {
-  return (kk / APP_HALF) * APP_C + ((kk % APP_HALF) / 8) * 16 + 8 * h + (kk % 8);
-}
-
-__global__ void k_pack_basis16(const float* __restrict__ basis_yin, const float* __restrict__ basis_yang, float* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= 2 * KHB * 2 * 64 * 4) return;
-  _Float16 pr[2];
-  for (int p = 0; p < 2; ++p) {
-    const int hidx = idx * 2 + p;
-    const int e = hidx & 7, lane = (hidx >> 3) & 63, term = (hidx >> 9) & 1, sg = hidx >> 10;
-    const int g = sg / KHB, kk = (sg % KHB) * 8 + e;
-    const int i = lane & 31, h = lane >> 5;
-    const int rh = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3), f = 2 * r + rh;
-    float w = 0.f;
-    if (r < NSLOT && f < APP_DIM) w = (g ? basis_yang : basis_yin)[f * (3 * APP_C) + app_channel_f16_fwd(kk, h)];
-    _Float16 hi, lo;
-    split_weight(w, hi, lo);
-    pr[p] = term ? lo : hi;
-  }
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-  h2v v = {pr[0], pr[1]};
-  out[idx] = __builtin_bit_cast(float, v);
-}
-
-// ---- fp16 main term + fp8 correction terms ("f16f8") weight layout ----------------------------------------------------
-// w*x = w_hi*x_hi (one v_mfma_f32_32x32x16_f16 per k-step, as in f16x3) + [w_lo*x_hi + w_hi*x_lo] on the block-scaled fp8 path:
-// ONE v_mfma_scale_f32_32x32x64_f8f6f4 per PAIR of k-steps carries both correction terms (K = 64 = 2 terms x 2 steps x 8 values
-// x 2 lane halves), at ~1.9x the matrix-pipe time of one fp16 instruction instead of 4x.  The corrections are ~2^-11 of the main
-// term, so e4m3's 4 significant bits leave ~2^-16 relative error per product (measured: DESIGN.md 4.1, profiles/r02/precision_sweep.json).
-// Operand bytes of a lane (row i = lane & 31 of m-tile mt, half h = lane >> 5; probed layout: byte b = k offset b of the lane's
-// 32-wide K block, tools/fp8_layout_probe.hip):
-//   A: [0..7] e4m3(w_lo * 2^11) step 2p | [8..15] same, step 2p+1 | [16..23] e4m3(w_hi) step 2p | [24..31] e4m3(w_hi) step 2p+1
-//   B: [0..7] e4m3(x)           step 2p | [8..15] same, step 2p+1 | [16..23] e4m3(x_lo * 2^11) step 2p | [24..31] ..., step 2p+1
-// and the instruction's E8M0 block scale of A is 2^-11 (exponent byte 116), of B 2^0 (127).
-// Region layout (32-bit slots, same OFF_W1 / OFF_W2 extents as the other layouts, so the LDS image keeps its size):
-//   per layer: hi fragments [step][m-tile][lane][8 halves], then fp8 fragments [pair][m-tile][part 0|1][lane][16 bytes]
-constexpr int F8_HI1 = KH1 * 4 * 64 * 4;          // 32-bit slots of layer 1's hi part (10240)
-constexpr int F8_HI2 = KH2 * 4 * 64 * 4;          // layer 2 (8192)
-constexpr int F8_FLOATS = OFF_B1;                 // W1 + W2 regions only; biases / W3 come from the f16x3 blob
-
-__device__ inline uint32_t e4m3_byte(float v) {
-  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xffu;
-}
-
-__global__ void k_pack_mlp_f8(const float* __restrict__ w1, const float* __restrict__ w2, float* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // one 32-bit slot
-  if (idx >= F8_FLOATS) return;
-  const bool l2 = idx >= OFF_W2;
-  const int e0 = l2 ? idx - OFF_W2 : idx;
-  const int hi_slots = l2 ? F8_HI2 : F8_HI1;
-  auto weight = [&](int step, int e, int lane, int mt) -> float {
-    if (!l2) {
-      const int ch = x_channel(step * 8 + e, lane >> 5);
-      return ch >= 0 ? w1[(mt * 32 + (lane & 31)) * MLP_IN + ch] : 0.f;
-    }
-    const int kk = step * 8 + e;
-    return w2[(mt * 32 + (lane & 31)) * HID + (kk >> 4) * 32 + slot_row(kk & 15, lane >> 5)];
-  };
-  uint32_t word = 0;
-  if (e0 < hi_slots) {  // [step][mt][lane][8 halves]
-    _Float16 pr[2];
-    for (int p = 0; p < 2; ++p) {
-      const int hidx = e0 * 2 + p;
-      const int e = hidx & 7, lane = (hidx >> 3) & 63, mt = (hidx >> 9) & 3, step = hidx >> 11;
-      _Float16 hi, lo;
-      split_weight(weight(step, e, lane, mt), hi, lo);
-      pr[p] = hi;
-    }
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    h2v v = {pr[0], pr[1]};
-    word = __builtin_bit_cast(uint32_t, v);
-  } else {  // [pair][mt][part][lane][16 bytes]
-    for (int b = 0; b < 4; ++b) {
-      const int bidx = (e0 - hi_slots) * 4 + b;
-      const int byte = bidx & 15, lane = (bidx >> 4) & 63, part = (bidx >> 10) & 1, mt = (bidx >> 11) & 3, pair = bidx >> 13;
-      const int pos = part * 16 + byte;                    // byte of the 32-byte operand
-      const int step = 2 * pair + ((pos >> 3) & 1), e = pos & 7;
-      const float w = weight(step, e, lane, mt);
-      _Float16 hi, lo;
-      split_weight(w, hi, lo);
-      const float v = pos < 16 ? (w - (float)hi) * 2048.0f : (float)hi;
-      word |= e4m3_byte(v) << (8 * b);
-    }
-  }
-  out[idx] = __builtin_bit_cast(float, word);
-}
-
-// ---- fp16 main term + fp6 correction terms ("f16f6") weight layout ------------------------------------------------------------
-// Same split as f16f8, with the two correction terms on the fp6 (e2m3) path of v_mfma_scale_f32_32x32x64_f8f6f4, which runs at
-// 1.18x the time of one fp16 32x32x16 instruction where the fp8 path takes 2.0x, and whose operands one conversion instruction
-// produces for 32 values at a time (v_cvt_scalef32_pk32_fp6_f16 / v_cvt_scalef32_2xpk16_fp6_f32: 64 clk per 32 values against
-// 16 x ~10 clk on the fp8 path; tools/fp6_probe.hip, profiles/r04/fp6_probe.txt).  e2m3 spans 6 binades only, so every block of 32
-// K values of a lane carries its own power-of-two scale (the instruction's E8M0 block scale is per lane): static for the weights
-// (from the block's largest magnitude), dynamic for the activations (exponent of the largest |x| of the lane's 32 values).
-// A GROUP is 4 k-steps = 32 values of a lane half; per group and m-tile two fp6 MFMAs: term 0 = w_lo * x_hi, term 1 = w_hi * x_lo.
-// Element e of a lane's 192-bit operand sits at bits [6e, 6e + 6); it carries the lane's K value f6_value(layer, group, term, e):
-//   term 0 (B from pk32_fp6_f16 of the four steps' packed halves): value 32 g + e
-//   term 1 (B from 2xpk16_fp6_f32 of the residuals, which interleaves its two 16-value sources): even e -> 32 g + e / 2, odd e -> 32 g + 16 + e / 2
-//   layer 1's last group holds only steps 8, 9: both terms come from 2xpk16(values, zeros): even e -> 64 + e / 2, odd e -> none
-// Scale bytes: with eb = biased exponent of the block's largest |x| (clamped to >= 14) the conversions divide by 2^(eb - 129) (x) and
-// 2^(eb - 140) (residual, i.e. 2^-11 further down) and the MFMAs pass eb itself as B's block scale; the 2^-2 / 2^-13 that this
-// overstates is folded into A's static scale byte, which is biased(weight block scale) - 2 (term 0) / - 13 (term 1).
-// Image layout (32-bit slots; it replaces the first OFF_B1 slots of the LDS image, biases / W3 behind it stay where they are):
-//   F6I_HI1 / F6I_HI2: fp16 hi fragments [step][m-tile][lane][8 halves] of layers 1 / 2 (as f16f8)
-//   F6I_Q1 / F6I_Q2:   the fp6 operands [group][m-tile][quad 0..2][lane][4]: the two terms' 6 + 6 dwords of a lane as three 16-byte
-//                      pieces: term 0 dwords 0-3 | term 1 dwords 0-3 | term 0 dwords 4-5, term 1 dwords 4-5.  (Separate 16 + 8 byte
-//                      pieces per term made the compiler pair the 8-byte reads of neighbouring fragments and copy the halves apart,
-//                      +42 v_mov per tile; term 0's six dwords followed by term 1's, +81: it does not coalesce a 12-register tuple.)
-//   F6I_SC:            scale bytes [group (layer 1's three, then layer 2's two)][lane][2 dwords]: byte mt of dword t = block scale of
-//                      (term t, m-tile mt) - the MFMA's op_sel picks the byte
-// The kernel addresses LDS as `per-lane base + 16-bit immediate` with one opaque base per 64 KB window (f6_bases): left to itself
-// the compiler spends a v_add on every read beyond 64 KB (62 more per tile than f16f8).
-constexpr int G6_1 = 3, G6_2 = 2;                 // groups per layer
-constexpr int F6I_HI1 = 0, F6I_HI2 = F6I_HI1 + F8_HI1;
-constexpr int F6I_Q1 = F6I_HI2 + F8_HI2, F6I_Q2 = F6I_Q1 + G6_1 * 4 * 3 * 256;
-constexpr int F6I_SC = F6I_Q2 + G6_2 * 4 * 3 * 256;
-constexpr int F6I_END = F6I_SC + (G6_1 + G6_2) * 128;
-constexpr int F6_FLOATS = OFF_B1;
-static_assert(F6I_END <= F6_FLOATS, "f16f6 image must fit the W1 / W2 part of the LDS image");
-static_assert(F6I_SC * 4 < 3 * 65536, "16-byte-stride part of the f16f6 image: three 64 KB windows");
-
-__host__ __device__ constexpr int f6_value(int layer2, int grp, int term, int e) {
-  if (!layer2 && grp == G6_1 - 1) return (e & 1) ? -1 : 64 + (e >> 1);
-  if (term == 0) return 32 * grp + e;
-  return 32 * grp + ((e & 1) ? 16 + (e >> 1) : (e >> 1));
-}
-
-// e2m3 code of v (already divided by its block scale): round to nearest even, saturating at 7.5
-__device__ inline uint32_t e2m3_code(float v) {
-  const uint32_t s = v < 0.f ? 32u : 0u;
-  const float a = fminf(fabsf(v), 7.5f);
-  if (a < 1.0f) return s | (uint32_t)rintf(a * 8.0f);     // subnormal step 1/8; 8 = the code of 1.0
-  const int e = a < 2.0f ? 0 : (a < 4.0f ? 1 : 2);
-  int m = (int)rintf(ldexpf(a, 3 - e));                    // 8..16
-  int ee = e;
-  if (m == 16) { m = 8; ee = e + 1; }
-  if (ee > 2) return s | 31u;
-  return s | (uint32_t)(((ee + 1) << 3) | (m - 8));
-}
-
-__device__ inline float mlp_weight_k(const float* __restrict__ w1, const float* __restrict__ w2, bool l2, int k, int lane, int mt) {
-  if (!l2) {
-    const int ch = k < KS1 ? x_channel(k, lane >> 5) : -1;
-    return ch >= 0 ? w1[(mt * 32 + (lane & 31)) * MLP_IN + ch] : 0.f;
-  }
-  return w2[(mt * 32 + (lane & 31)) * HID + (k >> 4) * 32 + slot_row(k & 15, lane >> 5)];
-}
-
-// the fp16 hi fragments of both layers: one thread per 32-bit slot
-__global__ void k_pack_mlp_f6(const float* __restrict__ w1, const float* __restrict__ w2, float* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t* o = (uint32_t*)out;
-  const int n_hi = F8_HI1 + F8_HI2;
-  if (idx < n_hi) {  // [step][mt][lane][8 halves]
-    const bool l2 = idx >= F8_HI1;
-    const int e0 = l2 ? idx - F8_HI1 : idx;
-    _Float16 pr[2];
-    for (int p = 0; p < 2; ++p) {
-      const int hidx = e0 * 2 + p;
-      const int e = hidx & 7, lane = (hidx >> 3) & 63, mt = (hidx >> 9) & 3, step = hidx >> 11;
-      _Float16 hi, lo;
-      split_weight(mlp_weight_k(w1, w2, l2, step * 8 + e, lane, mt), hi, lo);
-      pr[p] = hi;
-    }
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    h2v v = {pr[0], pr[1]};
-    o[(l2 ? F6I_HI2 : F6I_HI1) + e0] = __builtin_bit_cast(uint32_t, v);
-  }
-}
-
-// the fp6 operands: one 32-lane group per (layer / group, m-tile, lane, term), lane e = element e (the one-thread-per-operand form took
-// 29 us - two dependent chains of 32 scattered weight reads per thread - on every training iteration, whose weights change every step)
-__global__ void k_pack_mlp_f6_frag(const float* __restrict__ w1, const float* __restrict__ w2, float* __restrict__ out) {
-  uint32_t* o = (uint32_t*)out;
-  const int item = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5), e = threadIdx.x & 31;
-  if (item >= (G6_1 + G6_2) * 4 * 64 * 2) return;
-  const int term = item & 1, lane = (item >> 1) & 63, mt = (item >> 7) & 3, gg = item >> 9;
-  const bool l2 = gg >= G6_1;
-  const int grp = l2 ? gg - G6_1 : gg;
-  const int k = f6_value(l2, grp, term, e);
-  float w = 0.f;
-  if (k >= 0) {
-    _Float16 hi, lo;
-    const float wf = mlp_weight_k(w1, w2, l2, k, lane, mt);
-    split_weight(wf, hi, lo);
-    w = term == 0 ? wf - (float)hi : (float)hi;   // term 0 carries the exact fp32 residual of the weight, term 1 a copy of its fp16 part
-  }
-  float amax = fabsf(w);
-#pragma unroll
-  for (int sh = 1; sh < 32; sh <<= 1) amax = fmaxf(amax, __shfl_xor(amax, sh, 32));
-  int E = amax > 0.f ? ilogbf(amax) : -100;
-  if (E < -100) E = -100;
-  if (ldexpf(amax, 2 - E) > 7.75f) E += 1;          // the largest element would saturate: one binade up
-  const float inv = ldexpf(1.0f, 2 - E);            // 1 / block scale, block scale = 2^(E - 2)
-  const uint32_t c = e2m3_code(w * inv);
-  const int bit = 6 * e, wi = bit >> 5, sh = bit & 31;
-  uint32_t mine = 0;                                // after the reduction lane d < 6 holds dword d of the 192-bit operand
-#pragma unroll
-  for (int d = 0; d < 6; ++d) {
-    uint32_t v = (d == wi ? c << sh : 0u) | ((d == wi + 1 && sh > 26) ? c >> (32 - sh) : 0u);
-#pragma unroll
-    for (int x = 1; x < 32; x <<= 1) v |= __shfl_xor(v, x, 32);
-    if (e == d) mine = v;
-  }
-  uint32_t* q = o + (l2 ? F6I_Q2 : F6I_Q1) + (grp * 4 + mt) * 768 + lane * 4;
-  if (e < 4) q[term * 256 + e] = mine;
-  else if (e < 6) q[512 + 2 * term + (e - 4)] = mine;
-  if (e == 0) {
-    const int byte = (E - 2) + 127 - (term == 0 ? 2 : 13);
-    ((uint8_t*)(o + F6I_SC + gg * 128))[lane * 8 + term * 4 + mt] = (uint8_t)(byte < 0 ? 0 : (byte > 254 ? 254 : byte));
-  }
-}
 
 enum { MODE_SHADE = 0, MODE_APP = 1, MODE_MLP = 2 };
 
@@ -717,15 +321,6 @@ __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
 // fp16 subnormals are honoured by the instruction on gfx950 (tools/mfma_probe.hip), which the small x_lo terms need.
 // 6 matrix-pipe cycles per K instead of 32.
 // =================================================================================================================
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define MFMAH(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
-struct HL {
-  h8 hi, lo;
-};
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // bit 16 (mt & 1) + r of word mt >> 1 is set iff unit (mt, r) of this lane is > 0 (relu'(0) = 0 like torch's threshold backward)
 __device__ __forceinline__ u32x2 relu_bits(const f32x16 (&H)[4]) {
@@ -735,34 +330,6 @@ __device__ __forceinline__ u32x2 relu_bits(const f32x16 (&H)[4]) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) b[mt >> 1] |= (H[mt][r] > 0.f ? 1u : 0u) << (16 * (mt & 1) + r);
   return b;
-}
-
-__device__ __forceinline__ void split_pair(float a, float b, bool keep, uint32_t& hi, uint32_t& lo) {
-  a = keep ? a : 0.f;
-  b = keep ? b : 0.f;
-  const auto hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-  hi = __builtin_bit_cast(uint32_t, hp);
-  // residuals a - hi, b - hi are exact; each is ONE v_fma_mix_f32 (hi * -1 + a) reading the half straight from the packed
-  // register: no v_cvt_f32_f16 back-conversion (VALU and MFMA time add up on this SIMD, tools/coissue_probe.hip).  The -1 is
-  // made opaque so that the fma survives to instruction selection (a literal -1 folds into convert + subtract); the
-  // instruction should come from the compiler rather than from inline asm, which its hazard recogniser cannot see into.
-  float neg1 = -1.0f;
-  asm("" : "+v"(neg1));
-  const float ra = __builtin_fmaf((float)hp[0], neg1, a), rb = __builtin_fmaf((float)hp[1], neg1, b);
-  lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-
-__device__ __forceinline__ HL split8(const float x[8], bool keep) {
-  u32x4 hi, lo;
-  uint32_t a, b;
-  split_pair(x[0], x[1], keep, a, b); hi.x = a; lo.x = b;
-  split_pair(x[2], x[3], keep, a, b); hi.y = a; lo.y = b;
-  split_pair(x[4], x[5], keep, a, b); hi.z = a; lo.z = b;
-  split_pair(x[6], x[7], keep, a, b); hi.w = a; lo.w = b;
-  HL o;
-  o.hi = __builtin_bit_cast(h8, hi);
-  o.lo = __builtin_bit_cast(h8, lo);
-  return o;
 }
 
 // ---- f16f8 arithmetic: main term in fp16, both correction terms in one block-scaled fp8 MFMA per pair of k-steps -------------
@@ -1339,7 +906,7 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   const float* blob = A.packed + PACKED_FLOATS;  // the f16x3 half of the packed blob
   if (MODE != MODE_APP) {
     const f32x4* src = (const f32x4*)blob;
-    const f32x4* src8 = (const f32x4*)(A.packed + 2 * PACKED_FLOATS + BASIS16_FLOATS_C + (P6 ? F8_FLOATS : 0));  // f16f8 / f16f6 layout of W1 / W2
+    const f32x4* src8 = (const f32x4*)(A.packed + 2 * PACKED_FLOATS + BASIS16_FLOATS + (P6 ? F8_FLOATS : 0));  // f16f8 / f16f6 layout of W1 / W2
     // The 150 KB image goes to LDS by the loads themselves (global_load_lds_dwordx4: a wave instruction moves 1 KB, no VGPRs), and
     // nobody waits for it here: the first tile's gather + basis phase reads no LDS, so the workgroup meets at a barrier in front of
     // its first MLP phase instead (`need_sync` below).  A launch has ~32 us of fixed cost at 4096 x 512 (tools/shade_scaling.py), of
@@ -1861,39 +1428,47 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   }
 }
 
-#include "ego_train.inc"
+// ---- host side: one function fills the common launch arguments, one picks the kernel instance --------------------------------
+ShadeArgs shade_args(const ego_scene* sc, int64_t M, int32_t S) {   // (the tables go in with the instance: launch_shade)
+  ShadeArgs a{};
+  a.c = make_coords(*sc); a.packed = sc->packed; a.M = M; a.S = S;
+  return a;
+}
 
-int check_shade_config(const ego_scene* sc, const char* who, bool need_tables, bool need_mlp) {
-  if (!sc) return ego_fail(EGO_E_BADARG, "%s: null scene", who);
-  if (sc->app_dim != APP_DIM) return ego_fail(EGO_E_UNSUPPORTED, "%s: app_dim %d (supported: 27)", who, sc->app_dim);
-  if (need_tables) {
-    if (sc->app.n_comp != APP_C) return ego_fail(EGO_E_UNSUPPORTED, "%s: appearance n_comp %d (supported: 48)", who, sc->app.n_comp);
-    for (int g = 0; g < 2; ++g)
-      for (int i = 0; i < 3; ++i)
-        if (!sc->app.plane[g][i] || !sc->app.line[g][i]) return ego_fail(EGO_E_BADARG, "%s: null appearance table", who);
-    if (sc->app.res[0] < 2 || sc->app.res[1] < 2 || sc->app.res[2] < 2) return ego_fail(EGO_E_BADARG, "%s: appearance resolution < 2", who);
-    if (!ego_field_is_compact(sc->app, 4))
-      return ego_fail(EGO_E_BADARG, "%s: the 12 appearance tables must lie within 4 GB of each other (allocate them from one buffer)", who);
+// PX = 0 f16x3, 1 f16f8, 2 f16f6 where the MLP runs for inference (MLP, SHADE, SHADE + FOLD, SHADE + COMPACT), 0 elsewhere
+template <int MODE, bool DUMP, bool FOLD, bool COMPACT, bool TAB16>
+void launch_shade_h(int32_t precision, const ShadeArgs& a, hipStream_t st) {
+  const unsigned grid = shade_grid(a.M);
+  if constexpr (MODE != MODE_APP && !DUMP) {
+    if (precision == EGO_PREC_F16F8) return k_shade_h<MODE, DUMP, TAB16, 1, FOLD, COMPACT><<<grid, 512, 0, st>>>(a);
+    if (precision == EGO_PREC_F16F6) return k_shade_h<MODE, DUMP, TAB16, 2, FOLD, COMPACT><<<grid, 512, 0, st>>>(a);
   }
-  if (need_mlp && (sc->mlp_in != MLP_IN || sc->mlp_hidden != HID || sc->view_pe != 2 || sc->fea_pe != 2))
-    return ego_fail(EGO_E_UNSUPPORTED, "%s: MLP_Fea config in=%d hidden=%d view_pe=%d fea_pe=%d (supported: 150/128/2/2)", who,
-                    sc->mlp_in, sc->mlp_hidden, sc->view_pe, sc->fea_pe);
-  if (!sc->packed) return ego_fail(EGO_E_BADARG, "%s: scene.packed is null (call ego_pack_mlp first)", who);
-  return EGO_OK;
+  k_shade_h<MODE, DUMP, TAB16, 0, FOLD, COMPACT><<<grid, 512, 0, st>>>(a);
 }
 
-int check_app16(const ego_scene* sc, const char* who) {
-  if (sc->app16.n_comp != APP_C) return ego_fail(EGO_E_BADARG, "%s: app_f16 is set but app16.n_comp is %d", who, sc->app16.n_comp);
-  for (int g = 0; g < 2; ++g)
-    for (int i = 0; i < 3; ++i)
-      if (!sc->app16.plane[g][i] || !sc->app16.line[g][i]) return ego_fail(EGO_E_BADARG, "%s: app_f16 is set but an app16 table is null", who);
-  return EGO_OK;
-}
-
-unsigned shade_grid(int64_t M) {
-  const int64_t tiles = (M + 31) >> 5;
-  const int64_t wgs = (tiles + 7) / 8;
-  return (unsigned)(wgs < 256 ? wgs : 256);  // persistent: one 8-wave workgroup per CU
+// The set of shade instances: the entry point fixes MODE / DUMP / FOLD / COMPACT, the scene's mlp_precision and app_f16 pick the rest.
+// k_shade (fp32 MFMA) and TAB16 (gather from the fp16 tables) exist where nothing is dumped or folded (their entry points refuse
+// EGO_PREC_F32 / app_f16), TAB16 only where tables are read.  `who` names the entry point in error texts, `label` the launch.
+template <int MODE, bool DUMP = false, bool FOLD = false, bool COMPACT = false>
+int launch_shade(const ego_scene* sc, ShadeArgs& a, const char* who, const char* label, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  if (MODE != MODE_MLP) a.F = make_field(sc->app);
+  if constexpr (!DUMP && !FOLD) {
+    if (sc->mlp_precision == EGO_PREC_F32) {
+      k_shade<MODE, COMPACT><<<shade_grid(a.M), 512, 0, st>>>(a);
+      return ego_launch_status(label);
+    }
+    if constexpr (MODE != MODE_MLP) {
+      if (sc->app_f16) {
+        if (int e = check_app16(sc, who)) return e;
+        a.F = make_field(sc->app16);
+        launch_shade_h<MODE, DUMP, FOLD, COMPACT, true>(sc->mlp_precision, a, st);
+        return ego_launch_status(label);
+      }
+    }
+  }
+  launch_shade_h<MODE, DUMP, FOLD, COMPACT, false>(sc->mlp_precision, a, st);
+  return ego_launch_status(label);
 }
 
 }  // namespace
@@ -1921,58 +1496,6 @@ int32_t ego_render_forward_folds(const ego_scene* sc, int64_t N, int32_t S) {
   if (f && f[0] == '0') return 0;
   if (!ego_can_fold_composite(sc, S)) return 0;
   return (f && f[0] == '1') || ego_fold_is_balanced(N, S) ? 1 : 0;
-}
-
-constexpr int BASIS16_FLOATS = 2 * KHB * 2 * 64 * 4;  // [2 g][9 steps][2 terms][64 lanes][8 halves]
-
-int64_t ego_packed_floats(void) { return 2 * (int64_t)PACKED_FLOATS + BASIS16_FLOATS + F8_FLOATS + F6_FLOATS; }
-
-int64_t ego_packed_floats_scene(const ego_scene* sc) {
-  if (!sc) return -1;
-  return ego_shape_is_tuned(sc) ? ego_packed_floats() : ego_generic_packed_floats(sc);
-}
-
-int ego_pack_mlp(const ego_scene* sc, float* packed_out, void* stream) { return ego_pack_mlp_for(sc, packed_out, 0, stream); }
-
-int64_t ego_packed_floats_compat(const ego_scene* sc) { return sc ? ego_generic_packed_floats(sc) : -1; }
-
-int ego_pack_mlp_compat(const ego_scene* sc, float* packed_out, void* stream) {
-  EGO_TRACE("ego_pack_mlp_compat");
-  EGO_REQUIRE(sc && packed_out, "pack_mlp_compat: null argument");
-  if (sc->head != EGO_HEAD_RGB)
-    for (int i = 0; i < 3; ++i) EGO_REQUIRE(sc->mlp_w[i] && sc->mlp_b[i], "pack_mlp_compat: null MLP weight");
-  EGO_REQUIRE(sc->basis[0] && sc->basis[1], "pack_mlp_compat: null basis matrix");
-  return ego_generic_pack(sc, packed_out, stream);
-}
-
-int ego_pack_mlp_for(const ego_scene* sc, float* packed_out, int32_t for_training, void* stream) {
-  EGO_TRACE("ego_pack_mlp_for");
-  EGO_REQUIRE(sc && packed_out, "pack_mlp: null argument");
-  if (sc->head != EGO_HEAD_RGB)   // RGBRender has no MLP (tensorBase.py:37-39): only the basis matrices are packed
-    for (int i = 0; i < 3; ++i) EGO_REQUIRE(sc->mlp_w[i] && sc->mlp_b[i], "pack_mlp: null MLP weight");
-  EGO_REQUIRE(sc->basis[0] && sc->basis[1], "pack_mlp: null basis matrix");
-  if (!ego_shape_is_tuned(sc)) return ego_generic_pack(sc, packed_out, stream);   // any other shape: the fp32 compatibility kernels' layout
-  k_pack_mlp<<<(PACKED_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_b[0], sc->mlp_w[1], sc->mlp_b[1],
-                                                                          sc->mlp_w[2], sc->mlp_b[2], sc->basis[0], sc->basis[1],
-                                                                          packed_out);
-  if (int e = ego_launch_status("k_pack_mlp")) return e;
-  k_pack_mlp_h<<<(PACKED_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_b[0], sc->mlp_w[1], sc->mlp_b[1],
-                                                                            sc->mlp_w[2], sc->mlp_b[2], sc->basis[0], sc->basis[1],
-                                                                            packed_out, packed_out + PACKED_FLOATS);
-  if (int e = ego_launch_status("k_pack_mlp_h")) return e;
-  k_pack_basis16<<<(BASIS16_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->basis[0], sc->basis[1], packed_out + 2 * PACKED_FLOATS);
-  if (int e = ego_launch_status("k_pack_basis16")) return e;
-  static_assert(BASIS16_FLOATS == BASIS16_FLOATS_C, "blob region sizes");
-  if (for_training) return EGO_OK;   // the f16f8 / f16f6 images below are read by the inference arithmetics only
-  k_pack_mlp_f8<<<(F8_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_w[1],
-                                                                          packed_out + 2 * PACKED_FLOATS + BASIS16_FLOATS);
-  if (int e = ego_launch_status("k_pack_mlp_f8")) return e;
-  float* f6 = packed_out + 2 * PACKED_FLOATS + BASIS16_FLOATS + F8_FLOATS;
-  if (const hipError_t err = hipMemsetAsync(f6, 0, sizeof(float) * F6_FLOATS, (hipStream_t)stream)) return (int)err;  // the gaps behind the blocks
-  k_pack_mlp_f6<<<(F8_HI1 + F8_HI2 + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_w[1], f6);
-  if (int e = ego_launch_status("k_pack_mlp_f6")) return e;
-  k_pack_mlp_f6_frag<<<((G6_1 + G6_2) * 4 * 64 * 2 + 7) / 8, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_w[1], f6);
-  return ego_launch_status("k_pack_mlp_f6_frag");
 }
 
 int ego_shade_kernel_info(int32_t precision, int32_t* out, int32_t n) {
@@ -2003,15 +1526,9 @@ int ego_app_feature(const ego_scene* sc, const float* c7n, int64_t M, float* out
   EGO_REQUIRE(c7n && out, "app_feature: null argument");
   if (sc && !ego_shape_is_tuned(sc)) return ego_generic_app_feature(sc, c7n, M, out, stream);
   if (int e = check_shade_config(sc, "app_feature", true, false)) return e;
-  ShadeArgs a{};
-  a.c = make_coords(*sc); a.F = make_field(sc->app); a.packed = sc->packed; a.c7n = c7n; a.out = out; a.M = M; a.S = 1;
-  if (sc->mlp_precision == EGO_PREC_F32) k_shade<MODE_APP><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->app_f16) {
-    if (int e = check_app16(sc, "app_feature")) return e;
-    a.F = make_field(sc->app16);
-    k_shade_h<MODE_APP, false, true><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  } else k_shade_h<MODE_APP><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_shade<APP>");
+  ShadeArgs a = shade_args(sc, M, 1);
+  a.c7n = c7n; a.out = out;
+  return launch_shade<MODE_APP>(sc, a, "app_feature", "k_shade<APP>", stream);
 }
 
 int ego_mlp_fea(const ego_scene* sc, const float* viewdirs, const float* feat, int64_t M, float* rgb, void* stream) {
@@ -2021,13 +1538,9 @@ int ego_mlp_fea(const ego_scene* sc, const float* viewdirs, const float* feat, i
   EGO_REQUIRE(viewdirs && feat && rgb, "mlp_fea: null argument");
   if (sc && !ego_shape_is_tuned(sc)) return ego_generic_mlp_fea(sc, viewdirs, feat, M, rgb, stream);
   if (int e = check_shade_config(sc, "mlp_fea", false, true)) return e;
-  ShadeArgs a{};
-  a.c = make_coords(*sc); a.packed = sc->packed; a.feat = feat; a.dirs = viewdirs; a.out = rgb; a.M = M; a.S = 1;
-  if (sc->mlp_precision == EGO_PREC_F32) k_shade<MODE_MLP><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_MLP, false, false, 1><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_MLP, false, false, 2><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  else k_shade_h<MODE_MLP><<<shade_grid(M), 512, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_shade<MLP>");
+  ShadeArgs a = shade_args(sc, M, 1);
+  a.feat = feat; a.dirs = viewdirs; a.out = rgb;
+  return launch_shade<MODE_MLP>(sc, a, "mlp_fea", "k_shade<MLP>", stream);
 }
 
 int ego_shade(const ego_scene* sc, const float* rays, const float* z, const float* coords, int64_t N, int32_t S, float* rgb,
@@ -2044,25 +1557,13 @@ int ego_shade(const ego_scene* sc, const float* rays, const float* z, const floa
   EGO_REQUIRE(sc->r_lut && sc->n_r_lut >= 2 && sc->n_r_lut <= LUT_MAX, "shade: r_lut missing or > 1024 entries");
   EGO_REQUIRE(coords || sc->mlp_precision == EGO_PREC_F32, "shade: coords (from ego_march_density) is required unless mlp_precision = EGO_PREC_F32");
   if (N == 0) return EGO_OK;
-  ShadeArgs a{};
-  a.c = make_coords(*sc); a.F = make_field(sc->app); a.packed = sc->packed; a.rays = rays; a.z = z; a.coords = coords; a.out = rgb; a.tile_active = tile_active;
-  a.M = N * (int64_t)S; a.S = S;
-  if (dump) {
-    EGO_REQUIRE(sc->mlp_precision != EGO_PREC_F32 && dump->h1 && dump->h2 && dump->relu_bits && dump->fe,   // (x and v are optional)
-                "shade: activation dumps need the fp16-split arithmetic (not EGO_PREC_F32) and non-null h1 / h2 / v / relu_bits / fe buffers (x is optional)");
-    a.dump_x = dump->x; a.dump_h1 = dump->h1; a.dump_h2 = dump->h2; a.dump_v = dump->v; a.dump_bits = dump->relu_bits; a.dump_fe = dump->fe;
-    k_shade_h<MODE_SHADE, true><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  } else if (sc->mlp_precision == EGO_PREC_F32) k_shade<MODE_SHADE><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->app_f16) {
-    if (int e = check_app16(sc, "shade")) return e;
-    a.F = make_field(sc->app16);
-    if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, true, 1><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-    else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, true, 2><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-    else k_shade_h<MODE_SHADE, false, true><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  } else if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, false, 1><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, false, 2><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  else k_shade_h<MODE_SHADE><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_shade<SHADE>");
+  ShadeArgs a = shade_args(sc, N * (int64_t)S, S);
+  a.rays = rays; a.z = z; a.coords = coords; a.out = rgb; a.tile_active = tile_active;
+  if (!dump) return launch_shade<MODE_SHADE>(sc, a, "shade", "k_shade<SHADE>", stream);
+  EGO_REQUIRE(sc->mlp_precision != EGO_PREC_F32 && dump->h1 && dump->h2 && dump->relu_bits && dump->fe,   // (x and v are optional)
+              "shade: activation dumps need the fp16-split arithmetic (not EGO_PREC_F32) and non-null h1 / h2 / v / relu_bits / fe buffers (x is optional)");
+  a.dump_x = dump->x; a.dump_h1 = dump->h1; a.dump_h2 = dump->h2; a.dump_v = dump->v; a.dump_bits = dump->relu_bits; a.dump_fe = dump->fe;
+  return launch_shade<MODE_SHADE, true>(sc, a, "shade", "k_shade<SHADE>", stream);
 }
 
 }  // extern "C"
@@ -2077,28 +1578,14 @@ int ego_shade_live(const ego_scene* sc, const float* rays, const float* z, const
   EGO_REQUIRE(sc && ego_shape_is_tuned(sc), "shade_live: tuned model shape only");
   if (int e = check_shade_config(sc, "shade_live", true, true)) return e;
   EGO_REQUIRE(sc->r_lut && sc->n_r_lut >= 2 && sc->n_r_lut <= LUT_MAX, "shade_live: r_lut missing or > 1024 entries");
-  ShadeArgs a{};
-  a.c = make_coords(*sc); a.F = make_field(sc->app); a.packed = sc->packed; a.rays = rays; a.z = z; a.coords = coords; a.out = rgb;
-  a.live = live; a.n_live = n_live;
-  a.M = N * (int64_t)S; a.S = S;
-  const unsigned grid = shade_grid(a.M);
-  if (sc->mlp_precision == EGO_PREC_F32) k_shade<MODE_SHADE, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->app_f16) {
-    if (int e = check_app16(sc, "shade_live")) return e;
-    a.F = make_field(sc->app16);
-    if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, true, 1, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-    else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, true, 2, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-    else k_shade_h<MODE_SHADE, false, true, 0, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-  } else if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, false, 1, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, false, 2, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-  else k_shade_h<MODE_SHADE, false, false, 0, false, true><<<grid, 512, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_shade<SHADE, live list>");
+  ShadeArgs a = shade_args(sc, N * (int64_t)S, S);
+  a.rays = rays; a.z = z; a.coords = coords; a.out = rgb; a.live = live; a.n_live = n_live;
+  return launch_shade<MODE_SHADE, false, false, true>(sc, a, "shade_live", "k_shade<SHADE, live list>", stream);
 }
 
-extern "C" {
-
-int ego_shade_composite(const ego_scene* sc, const float* rays, const float* z, const float* coords, const float* weight, const float* bg_weight,
-                        int64_t N, int32_t S, const uint8_t* tile_active, float* rgb_map, float* depth, float* bg_map, float* env_map, void* stream) {
+extern "C" int ego_shade_composite(const ego_scene* sc, const float* rays, const float* z, const float* coords, const float* weight,
+                                   const float* bg_weight, int64_t N, int32_t S, const uint8_t* tile_active, float* rgb_map, float* depth,
+                                   float* bg_map, float* env_map, void* stream) {
   EGO_TRACE("ego_shade_composite");
   EGO_REQUIRE(rays && z && coords && weight && rgb_map && N >= 0 && S >= 32 && (S & 31) == 0 && N * (int64_t)S < (1ll << 31),
               "shade_composite: null argument, S not a multiple of 32, or N*S >= 2^31");
@@ -2106,160 +1593,9 @@ int ego_shade_composite(const ego_scene* sc, const float* rays, const float* z, 
   if (int e = check_shade_config(sc, "shade_composite", true, true)) return e;
   EGO_REQUIRE(!sc->envmap || bg_weight, "shade_composite: envmap needs bg_weight");
   if (N == 0) return EGO_OK;
-  ShadeArgs a{};
-  a.c = make_coords(*sc); a.F = make_field(sc->app); a.packed = sc->packed; a.rays = rays; a.z = z; a.coords = coords; a.tile_active = tile_active;
+  ShadeArgs a = shade_args(sc, N * (int64_t)S, S);
+  a.rays = rays; a.z = z; a.coords = coords; a.tile_active = tile_active;
   a.comp_w = weight; a.comp_bg = bg_weight; a.envmap = sc->envmap; a.envmap_h = sc->envmap_h;
   a.rgb_map = rgb_map; a.depth = depth; a.bg_map = bg_map; a.env_map = env_map;
-  a.M = N * (int64_t)S; a.S = S;
-  if (sc->mlp_precision == EGO_PREC_F16F6) k_shade_h<MODE_SHADE, false, false, 2, true><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  else if (sc->mlp_precision == EGO_PREC_F16F8) k_shade_h<MODE_SHADE, false, false, 1, true><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  else k_shade_h<MODE_SHADE, false, false, 0, true><<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_shade<SHADE, composite>");
+  return launch_shade<MODE_SHADE, false, true>(sc, a, "shade_composite", "k_shade<SHADE, composite>", stream);
 }
-
-// ---- training step (backward) --------------------------------------------------------------------------------------
-int64_t ego_train_packed_floats(void) { return TRAIN_FLOATS; }
-
-int ego_pack_train(const ego_scene* sc, float* out, void* stream) {
-  EGO_TRACE("ego_pack_train");
-  EGO_REQUIRE(sc && out, "pack_train: null argument");
-  if (int e = check_shade_config(sc, "pack_train", true, true)) return e;
-  EGO_REQUIRE(sc->mlp_w[0] && sc->mlp_w[1] && sc->mlp_w[2] && sc->basis[0] && sc->basis[1], "pack_train: null weight");
-  k_pack_train<<<(TRAIN_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_w[1], sc->mlp_w[2], sc->basis[0],
-                                                                            sc->basis[1], out);
-  return ego_launch_status("k_pack_train");
-}
-
-int ego_train_layout(int32_t which, int32_t* out, int32_t n) {
-  EGO_REQUIRE(out, "train_layout: null output");
-  if (which == 0) {  // x dump column -> reference MLP input column (-1: padding)
-    EGO_REQUIRE(n == 2 * KS1, "train_layout(0): n must be 160");
-    for (int h = 0; h < 2; ++h)
-      for (int kk = 0; kk < KS1; ++kk) {
-        int ch = -1;
-        if (kk < 5 * NSLOT) {
-          const int kind = kk % 5, r = kk / 5, f = 2 * r + h;
-          if (f < APP_DIM) ch = kind == 0 ? f : (kind == 1 ? 30 + 2 * f : (kind == 2 ? 31 + 2 * f : (kind == 3 ? 84 + 2 * f : 85 + 2 * f)));
-        } else if (kk < 5 * NSLOT + 8) {
-          const int t = kk - 5 * NSLOT + 8 * h;
-          ch = t < 3 ? APP_DIM + t : (t < 15 ? 138 + (t - 3) : -1);
-        }
-        out[dump_col(kk, h)] = ch;
-      }
-  } else if (which == 1) {  // h1 / h2 / dh1 / dh2 dump column -> hidden unit
-    EGO_REQUIRE(n == HID, "train_layout(1): n must be 128");
-    for (int h = 0; h < 2; ++h)
-      for (int mt = 0; mt < 4; ++mt)
-        for (int r = 0; r < 16; ++r) out[dump_col(mt * 16 + r, h)] = mt * 32 + slot_row(r, h);
-  } else if (which == 2) {  // dfe column (within one grid's 32) -> feature (-1: padding)
-    EGO_REQUIRE(n == 32, "train_layout(2): n must be 32");
-    for (int h = 0; h < 2; ++h)
-      for (int r = 0; r < 16; ++r) out[h * 16 + r] = (r < NSLOT && 2 * r + h < APP_DIM) ? 2 * r + h : -1;
-  } else if (which == 3) {  // v dump column -> basis input column (0..143)
-    EGO_REQUIRE(n == 2 * KS_BASIS, "train_layout(3): n must be 144");
-    for (int h = 0; h < 2; ++h)
-      for (int kk = 0; kk < KS_BASIS; ++kk) out[dump_col(kk, h)] = app_channel_g(kk, h);
-  } else {
-    return ego_fail(EGO_E_BADARG, "train_layout: which must be 0..3");
-  }
-  return EGO_OK;
-}
-
-static GradField make_grad(const ego_vm_grad& g) {
-  GradField o;
-  for (int a = 0; a < 2; ++a)
-    for (int i = 0; i < 3; ++i) { o.plane[a][i] = g.plane[a][i]; o.line[a][i] = g.line[a][i]; }
-  return o;
-}
-
-static int check_grad(const ego_vm_grad* g, const char* who) {
-  if (!g) return ego_fail(EGO_E_BADARG, "%s: null gradient tables", who);
-  for (int a = 0; a < 2; ++a)
-    for (int i = 0; i < 3; ++i)
-      if (!g->plane[a][i] || !g->line[a][i]) return ego_fail(EGO_E_BADARG, "%s: null gradient table pointer", who);
-  return EGO_OK;
-}
-
-int ego_march_backward(const ego_scene* sc, const float* z, const float* alpha, int32_t alpha_stride, const float* weight,
-                       const float* sigma, const float* bg_weight, const float* rgb, const float* g_rgb, const float* g_alpha,
-                       const float* rgb_raw, const float* env_map, int64_t N, int32_t S, float* dc, float* dfeat, void* stream) {
-  EGO_TRACE("ego_march_backward");
-  EGO_REQUIRE(N >= 0 && S >= 2 && alpha_stride >= S, "march_backward: bad size");
-  if (N == 0) return EGO_OK;
-  EGO_REQUIRE(sc && z && alpha && weight && sigma && bg_weight && rgb && g_rgb && rgb_raw && dc && dfeat, "march_backward: null argument");
-  if (!sc->act_softplus) return ego_fail(EGO_E_UNSUPPORTED, "march_backward: only the softplus density activation is supported");
-  MarchBwdArgs a{};
-  a.z = z; a.alpha = alpha; a.g_alpha = g_alpha; a.astride = alpha_stride; a.weight = weight; a.sigma = sigma;
-  a.bg = bg_weight; a.rgb = rgb; a.g_rgb = g_rgb;
-  a.rgb_raw = rgb_raw; a.env = env_map; a.dc = dc; a.dfeat = dfeat; a.N = N; a.S = S; a.dscale = sc->distance_scale;
-  k_march_bwd<<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_march_bwd");
-}
-
-int ego_shade_backward(const ego_scene* sc, const float* train_packed, const float* coords, float* dc, const float* rgb,
-                       const ego_shade_dump* fwd, uint16_t* dh2, uint16_t* dh1, float* dh_scale, float* dfe, float* dv, float* dv_absmax, int64_t N,
-                       int32_t S, void* stream) {
-  EGO_TRACE("ego_shade_backward");
-  EGO_REQUIRE(N >= 0 && S >= 1 && N * (int64_t)S < (1ll << 31), "shade_backward: bad size");
-  if (N == 0) {
-    if (dv_absmax)
-      if (const hipError_t me = hipMemsetAsync(dv_absmax, 0, 4, (hipStream_t)stream)) return ego_fail((int)me, "shade_backward: hipMemsetAsync failed: %s", hipGetErrorString(me));
-    return EGO_OK;
-  }
-  EGO_REQUIRE(sc && train_packed && coords && dc && rgb && fwd && fwd->fe && fwd->relu_bits && dh2 && dh1 && dh_scale && dfe && (dv || dv_absmax),
-              "shade_backward: null argument");
-  EGO_REQUIRE((((uintptr_t)dh2 | (uintptr_t)dh1 | (uintptr_t)fwd->relu_bits | (uintptr_t)dv) & 15) == 0,
-              "shade_backward: dh2 / dh1 / dv / relu_bits must be 16-byte aligned");
-  if (int e = check_shade_config(sc, "shade_backward", true, true)) return e;
-  ShadeBwdArgs a{};
-  a.tpacked = train_packed; a.coords = coords; a.dc = dc; a.rgb = rgb;
-  a.fe = fwd->fe; a.bits = fwd->relu_bits; a.dh2 = dh2; a.dh1 = dh1; a.dh_scale = dh_scale; a.dfe = dfe; a.dv = dv; a.M = N * (int64_t)S;
-  a.dv_absmax = (uint32_t*)dv_absmax;
-  if (dv_absmax)
-    if (const hipError_t me = hipMemsetAsync(dv_absmax, 0, 4, (hipStream_t)stream)) return ego_fail((int)me, "shade_backward: hipMemsetAsync failed: %s", hipGetErrorString(me));
-  k_shade_bwd<<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_shade_bwd");
-}
-
-static int scatter_common(const ego_vm_field& f, const ego_vm_grad* g, const float* coords, const float* d, int64_t N, int32_t S,
-                          ScatterArgs* a, const char* who) {
-  if (!(N >= 0 && S >= 1)) return ego_fail(EGO_E_BADARG, "%s: bad size", who);
-  if (N == 0) return EGO_OK;
-  if (!coords || !d) return ego_fail(EGO_E_BADARG, "%s: null argument", who);
-  if (int e = check_grad(g, who)) return e;
-  a->F = make_field(f); a->G = make_grad(*g); a->coords = coords; a->d = d; a->N = N; a->S = S;
-  a->seg = 64;
-  a->gpr = (S + a->seg - 1) / a->seg;
-  return EGO_OK;
-}
-
-static dim3 scatter_blocks(const ScatterArgs& a) {
-  const int64_t groups = a.N * a.gpr;
-  return dim3((unsigned)((groups + 15) / 16), 3);  // 4 groups per wave, 4 waves per workgroup; y = plane
-}
-
-int ego_scatter_density(const ego_scene* sc, const ego_vm_grad* gdensity, const float* coords, const float* dfeat, int64_t N, int32_t S,
-                        void* stream) {
-  EGO_TRACE("ego_scatter_density");
-  EGO_REQUIRE(sc, "scatter_density: null scene");
-  if (sc->density.n_comp != 16) return ego_fail(EGO_E_UNSUPPORTED, "scatter_density: n_comp %d (supported: 16)", sc->density.n_comp);
-  ScatterArgs a{};
-  if (int e = scatter_common(sc->density, gdensity, coords, dfeat, N, S, &a, "scatter_density")) return e;
-  if (N == 0) return EGO_OK;
-  k_vm_scatter<16, true><<<scatter_blocks(a), 256, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_vm_scatter<16>");
-}
-
-int ego_scatter_app(const ego_scene* sc, const ego_vm_grad* gapp, const float* coords, const float* dv, int64_t N, int32_t S,
-                    void* stream) {
-  EGO_TRACE("ego_scatter_app");
-  EGO_REQUIRE(sc, "scatter_app: null scene");
-  if (sc->app.n_comp != APP_C) return ego_fail(EGO_E_UNSUPPORTED, "scatter_app: n_comp %d (supported: 48)", sc->app.n_comp);
-  ScatterArgs a{};
-  if (int e = scatter_common(sc->app, gapp, coords, dv, N, S, &a, "scatter_app")) return e;
-  if (N == 0) return EGO_OK;
-  k_vm_scatter<APP_C, false><<<scatter_blocks(a), 256, 0, (hipStream_t)stream>>>(a);
-  return ego_launch_status("k_vm_scatter<48>");
-}
-
-}  // extern "C"

@@ -1,8 +1,11 @@
-// Included inside ego_shade.hip's anonymous namespace: backward kernels of the training step.
+// libegonerf_hip.so: backward kernels of the training step and their entry points.
 //
 // Weight gradients are NOT reduced here: the kernels emit per-sample activation gradients in the same
 // lane-contiguous order as the forward dumps and the host layer turns them into dW with plain library GEMMs
 // (K = all samples of the step), then un-permutes the small result matrices (ego_train_layout tables).
+#include "ego_tuned.h"
+
+namespace {
 
 // ---- transposed fragments for the data-gradient chain (fp16-split, same [step][tile][term][lane][8] order) ------
 constexpr int T_W2T = 0;                                   // dH1 = W2^T dH2 : [8 steps][4 m-tiles]
@@ -582,3 +585,153 @@ __global__ __launch_bounds__(256) void k_vm_scatter(ScatterArgs A) {
   else if (blockIdx.y == 1) scatter_plane<C, DENS, 1>(A);
   else scatter_plane<C, DENS, 2>(A);
 }
+
+}  // namespace
+
+extern "C" {
+
+int64_t ego_train_packed_floats(void) { return TRAIN_FLOATS; }
+
+int ego_pack_train(const ego_scene* sc, float* out, void* stream) {
+  EGO_TRACE("ego_pack_train");
+  EGO_REQUIRE(sc && out, "pack_train: null argument");
+  if (int e = check_shade_config(sc, "pack_train", true, true)) return e;
+  EGO_REQUIRE(sc->mlp_w[0] && sc->mlp_w[1] && sc->mlp_w[2] && sc->basis[0] && sc->basis[1], "pack_train: null weight");
+  k_pack_train<<<(TRAIN_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(sc->mlp_w[0], sc->mlp_w[1], sc->mlp_w[2], sc->basis[0],
+                                                                            sc->basis[1], out);
+  return ego_launch_status("k_pack_train");
+}
+
+int ego_train_layout(int32_t which, int32_t* out, int32_t n) {
+  EGO_REQUIRE(out, "train_layout: null output");
+  if (which == 0) {  // x dump column -> reference MLP input column (-1: padding)
+    EGO_REQUIRE(n == 2 * KS1, "train_layout(0): n must be 160");
+    for (int h = 0; h < 2; ++h)
+      for (int kk = 0; kk < KS1; ++kk) {
+        int ch = -1;
+        if (kk < 5 * NSLOT) {
+          const int kind = kk % 5, r = kk / 5, f = 2 * r + h;
+          if (f < APP_DIM) ch = kind == 0 ? f : (kind == 1 ? 30 + 2 * f : (kind == 2 ? 31 + 2 * f : (kind == 3 ? 84 + 2 * f : 85 + 2 * f)));
+        } else if (kk < 5 * NSLOT + 8) {
+          const int t = kk - 5 * NSLOT + 8 * h;
+          ch = t < 3 ? APP_DIM + t : (t < 15 ? 138 + (t - 3) : -1);
+        }
+        out[dump_col(kk, h)] = ch;
+      }
+  } else if (which == 1) {  // h1 / h2 / dh1 / dh2 dump column -> hidden unit
+    EGO_REQUIRE(n == HID, "train_layout(1): n must be 128");
+    for (int h = 0; h < 2; ++h)
+      for (int mt = 0; mt < 4; ++mt)
+        for (int r = 0; r < 16; ++r) out[dump_col(mt * 16 + r, h)] = mt * 32 + slot_row(r, h);
+  } else if (which == 2) {  // dfe column (within one grid's 32) -> feature (-1: padding)
+    EGO_REQUIRE(n == 32, "train_layout(2): n must be 32");
+    for (int h = 0; h < 2; ++h)
+      for (int r = 0; r < 16; ++r) out[h * 16 + r] = (r < NSLOT && 2 * r + h < APP_DIM) ? 2 * r + h : -1;
+  } else if (which == 3) {  // v dump column -> basis input column (0..143)
+    EGO_REQUIRE(n == 2 * KS_BASIS, "train_layout(3): n must be 144");
+    for (int h = 0; h < 2; ++h)
+      for (int kk = 0; kk < KS_BASIS; ++kk) out[dump_col(kk, h)] = app_channel_g(kk, h);
+  } else {
+    return ego_fail(EGO_E_BADARG, "train_layout: which must be 0..3");
+  }
+  return EGO_OK;
+}
+
+static GradField make_grad(const ego_vm_grad& g) {
+  GradField o;
+  for (int a = 0; a < 2; ++a)
+    for (int i = 0; i < 3; ++i) { o.plane[a][i] = g.plane[a][i]; o.line[a][i] = g.line[a][i]; }
+  return o;
+}
+
+static int check_grad(const ego_vm_grad* g, const char* who) {
+  if (!g) return ego_fail(EGO_E_BADARG, "%s: null gradient tables", who);
+  for (int a = 0; a < 2; ++a)
+    for (int i = 0; i < 3; ++i)
+      if (!g->plane[a][i] || !g->line[a][i]) return ego_fail(EGO_E_BADARG, "%s: null gradient table pointer", who);
+  return EGO_OK;
+}
+
+int ego_march_backward(const ego_scene* sc, const float* z, const float* alpha, int32_t alpha_stride, const float* weight,
+                       const float* sigma, const float* bg_weight, const float* rgb, const float* g_rgb, const float* g_alpha,
+                       const float* rgb_raw, const float* env_map, int64_t N, int32_t S, float* dc, float* dfeat, void* stream) {
+  EGO_TRACE("ego_march_backward");
+  EGO_REQUIRE(N >= 0 && S >= 2 && alpha_stride >= S, "march_backward: bad size");
+  if (N == 0) return EGO_OK;
+  EGO_REQUIRE(sc && z && alpha && weight && sigma && bg_weight && rgb && g_rgb && rgb_raw && dc && dfeat, "march_backward: null argument");
+  if (!sc->act_softplus) return ego_fail(EGO_E_UNSUPPORTED, "march_backward: only the softplus density activation is supported");
+  MarchBwdArgs a{};
+  a.z = z; a.alpha = alpha; a.g_alpha = g_alpha; a.astride = alpha_stride; a.weight = weight; a.sigma = sigma;
+  a.bg = bg_weight; a.rgb = rgb; a.g_rgb = g_rgb;
+  a.rgb_raw = rgb_raw; a.env = env_map; a.dc = dc; a.dfeat = dfeat; a.N = N; a.S = S; a.dscale = sc->distance_scale;
+  k_march_bwd<<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(a);
+  return ego_launch_status("k_march_bwd");
+}
+
+int ego_shade_backward(const ego_scene* sc, const float* train_packed, const float* coords, float* dc, const float* rgb,
+                       const ego_shade_dump* fwd, uint16_t* dh2, uint16_t* dh1, float* dh_scale, float* dfe, float* dv, float* dv_absmax, int64_t N,
+                       int32_t S, void* stream) {
+  EGO_TRACE("ego_shade_backward");
+  EGO_REQUIRE(N >= 0 && S >= 1 && N * (int64_t)S < (1ll << 31), "shade_backward: bad size");
+  if (N == 0) {
+    if (dv_absmax)
+      if (const hipError_t me = hipMemsetAsync(dv_absmax, 0, 4, (hipStream_t)stream)) return ego_fail((int)me, "shade_backward: hipMemsetAsync failed: %s", hipGetErrorString(me));
+    return EGO_OK;
+  }
+  EGO_REQUIRE(sc && train_packed && coords && dc && rgb && fwd && fwd->fe && fwd->relu_bits && dh2 && dh1 && dh_scale && dfe && (dv || dv_absmax),
+              "shade_backward: null argument");
+  EGO_REQUIRE((((uintptr_t)dh2 | (uintptr_t)dh1 | (uintptr_t)fwd->relu_bits | (uintptr_t)dv) & 15) == 0,
+              "shade_backward: dh2 / dh1 / dv / relu_bits must be 16-byte aligned");
+  if (int e = check_shade_config(sc, "shade_backward", true, true)) return e;
+  ShadeBwdArgs a{};
+  a.tpacked = train_packed; a.coords = coords; a.dc = dc; a.rgb = rgb;
+  a.fe = fwd->fe; a.bits = fwd->relu_bits; a.dh2 = dh2; a.dh1 = dh1; a.dh_scale = dh_scale; a.dfe = dfe; a.dv = dv; a.M = N * (int64_t)S;
+  a.dv_absmax = (uint32_t*)dv_absmax;
+  if (dv_absmax)
+    if (const hipError_t me = hipMemsetAsync(dv_absmax, 0, 4, (hipStream_t)stream)) return ego_fail((int)me, "shade_backward: hipMemsetAsync failed: %s", hipGetErrorString(me));
+  k_shade_bwd<<<shade_grid(a.M), 512, 0, (hipStream_t)stream>>>(a);
+  return ego_launch_status("k_shade_bwd");
+}
+
+static int scatter_common(const ego_vm_field& f, const ego_vm_grad* g, const float* coords, const float* d, int64_t N, int32_t S,
+                          ScatterArgs* a, const char* who) {
+  if (!(N >= 0 && S >= 1)) return ego_fail(EGO_E_BADARG, "%s: bad size", who);
+  if (N == 0) return EGO_OK;
+  if (!coords || !d) return ego_fail(EGO_E_BADARG, "%s: null argument", who);
+  if (int e = check_grad(g, who)) return e;
+  a->F = make_field(f); a->G = make_grad(*g); a->coords = coords; a->d = d; a->N = N; a->S = S;
+  a->seg = 64;
+  a->gpr = (S + a->seg - 1) / a->seg;
+  return EGO_OK;
+}
+
+static dim3 scatter_blocks(const ScatterArgs& a) {
+  const int64_t groups = a.N * a.gpr;
+  return dim3((unsigned)((groups + 15) / 16), 3);  // 4 groups per wave, 4 waves per workgroup; y = plane
+}
+
+int ego_scatter_density(const ego_scene* sc, const ego_vm_grad* gdensity, const float* coords, const float* dfeat, int64_t N, int32_t S,
+                        void* stream) {
+  EGO_TRACE("ego_scatter_density");
+  EGO_REQUIRE(sc, "scatter_density: null scene");
+  if (sc->density.n_comp != 16) return ego_fail(EGO_E_UNSUPPORTED, "scatter_density: n_comp %d (supported: 16)", sc->density.n_comp);
+  ScatterArgs a{};
+  if (int e = scatter_common(sc->density, gdensity, coords, dfeat, N, S, &a, "scatter_density")) return e;
+  if (N == 0) return EGO_OK;
+  k_vm_scatter<16, true><<<scatter_blocks(a), 256, 0, (hipStream_t)stream>>>(a);
+  return ego_launch_status("k_vm_scatter<16>");
+}
+
+int ego_scatter_app(const ego_scene* sc, const ego_vm_grad* gapp, const float* coords, const float* dv, int64_t N, int32_t S,
+                    void* stream) {
+  EGO_TRACE("ego_scatter_app");
+  EGO_REQUIRE(sc, "scatter_app: null scene");
+  if (sc->app.n_comp != APP_C) return ego_fail(EGO_E_UNSUPPORTED, "scatter_app: n_comp %d (supported: 48)", sc->app.n_comp);
+  ScatterArgs a{};
+  if (int e = scatter_common(sc->app, gapp, coords, dv, N, S, &a, "scatter_app")) return e;
+  if (N == 0) return EGO_OK;
+  k_vm_scatter<APP_C, false><<<scatter_blocks(a), 256, 0, (hipStream_t)stream>>>(a);
+  return ego_launch_status("k_vm_scatter<48>");
+}
+
+}  // extern "C"

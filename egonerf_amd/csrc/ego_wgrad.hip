@@ -6,8 +6,7 @@
 // the rows in registers with three v_mfma_f32_32x32x16_bf16 per product (hi*hi + lo*hi + hi*lo: ~17 significand bits per
 // operand, rounded to nearest so the error does not accumulate over the 10^6 terms; compared at 2e-4).  A designated column of B can be replaced by ones, which
 // puts the bias gradient (the column sums of A) into the same pass.  One pass over the dumps, HBM-bound.
-#include "ego_device.h"
-#include "ego_host.h"
+#include "ego_tuned.h"
 
 namespace {
 
@@ -315,7 +314,6 @@ __device__ __forceinline__ u32x4 pack8_rn_w(const float x[8]) {
 // One k-step (compile-time STEP) of a sample's lane half hw, in two parts so that the loads travel while the previous step multiplies:
 // x_load = the (at most three) feature slots the step's eight values come from (fe_lane = the half's slot dump, &fe[(tile * 4) * 64 + lane]
 // as floats, quad q 256 floats further on); x_make = the eight values from them and the ray's direction, packed as the forward packs them.
-constexpr int NSLOT_W = 14;
 template <int STEP>
 __device__ __forceinline__ void x_load(const float* __restrict__ fe_lane, float f[3]) {
   constexpr int r_first = (STEP * 8) / 5;
@@ -323,7 +321,7 @@ __device__ __forceinline__ void x_load(const float* __restrict__ fe_lane, float 
   for (int k = 0; k < 3; ++k) {
     constexpr int dummy = 0; (void)dummy;
     const int r = r_first + k;
-    f[k] = (r < NSLOT_W && r * 5 <= STEP * 8 + 7) ? fe_lane[(r >> 2) * 256 + (r & 3)] : 0.f;
+    f[k] = (r < NSLOT && r * 5 <= STEP * 8 + 7) ? fe_lane[(r >> 2) * 256 + (r & 3)] : 0.f;
   }
 }
 template <int STEP>
@@ -332,7 +330,7 @@ __device__ __forceinline__ u32x4 x_make(const float f[3], const float dir[3], in
   float xs[8], s1[3], c1[3], s2[3], c2[3], vw[8];
 #pragma unroll
   for (int k = 0; k < 3; ++k)
-    if (r_first + k < NSLOT_W && (r_first + k) * 5 <= STEP * 8 + 7) sincos_x_2x_hw(f[k], s1[k], c1[k], s2[k], c2[k]);
+    if (r_first + k < NSLOT && (r_first + k) * 5 <= STEP * 8 + 7) sincos_x_2x_hw(f[k], s1[k], c1[k], s2[k], c2[k]);
   if (STEP >= 8) {   // the view values live in the last two steps
     float sa0, ca0, sb0, cb0, sa1, ca1, sb1, cb1, sa2, ca2, sb2, cb2;
     sincos_x_2x_hw(dir[0], sa0, ca0, sb0, cb0);
@@ -345,11 +343,11 @@ __device__ __forceinline__ u32x4 x_make(const float f[3], const float dir[3], in
   for (int e = 0; e < 8; ++e) {
     const int kk = STEP * 8 + e;
     float x;
-    if (kk < 5 * NSLOT_W) {
+    if (kk < 5 * NSLOT) {
       const int k = kk / 5 - r_first, kind = kk % 5;
       x = kind == 0 ? f[k] : (kind == 1 ? s1[k] : (kind == 2 ? s2[k] : (kind == 3 ? c1[k] : c2[k])));
-    } else if (kk < 5 * NSLOT_W + 8) {
-      x = vw[kk - 5 * NSLOT_W];
+    } else if (kk < 5 * NSLOT + 8) {
+      x = vw[kk - 5 * NSLOT];
     } else {
       x = 0.f;
     }

@@ -318,7 +318,7 @@ def mlp_k_matrix(w, layer2):
 
 
 def pack_mlp_f6(w):
-    """Fifth region of the packed blob (the f16f6 LDS image, csrc/ego_shade.hip): hi fragments of both layers, the fp6 operands
+    """Fifth region of the packed blob (the f16f6 LDS image, csrc/ego_tuned.h): hi fragments of both layers, the fp6 operands
     [group][m-tile][quad][lane][4] (quad t: term t's dwords 0-3; quad 2: term 0's dwords 4-5, term 1's dwords 4-5), scale bytes [group][lane][term][m-tile]."""
     out = np.zeros(F6_FLOATS, np.uint32)
     for layer2, hi0, q0, groups in ((False, F6I_HI1, F6I_Q1, G6_1), (True, F6I_HI2, F6I_Q2, G6_2)):

@@ -3,6 +3,8 @@ re-assemble its own device assembly with ONLY the packed fp32 instructions that 
 (`op_sel:[1,0,0]` / `[0,1]` / `[1,0]` without op_sel_hi) replaced by their two-instruction scalar equivalents - same registers,
 same schedule, same arithmetic (v_fma_f32 / v_mul_f32 round like the packed forms).  If the failing library fails and the patched
 one is clean in one GPU session, the instruction FORM is the trigger, not the register allocation or schedule around it.
+Only ego_shade.hip (the forward shade kernels, where the fault lives) goes through the assembly; every other source, ego_pack.hip and
+ego_train.hip included, is compiled as it is with the common flags.
 
   python tools/experiments/fault51_asm_patch.py <out_dir> [kernel-substring]
 writes <out_dir>/libvariant_f0.so (failing form, unpatched assembly through the same manual pipeline), libvariant_p1.so (replaced)

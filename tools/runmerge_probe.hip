@@ -1,4 +1,4 @@
-// micro-test of run_after / run_sum (egonerf_amd/csrc/ego_train.inc) against a CPU model
+// micro-test of run_after / run_sum (defined below; the scatter that used them is no longer in csrc/) against a CPU model
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
