@@ -19,6 +19,35 @@ import torch
 from . import _lib
 
 CAMERA_MODELS = {"erp": _lib.CAM_ERP, "pinhole": _lib.CAM_PINHOLE, "pinhole_blender": _lib.CAM_PINHOLE_BLENDER}
+EYES = {"centre": _lib.EYE_CENTRE, "left": _lib.EYE_LEFT, "right": _lib.EYE_RIGHT}
+MAX_SUPERSAMPLE = 4
+
+
+def _supersample(s) -> int:
+    if int(s) != s or not 1 <= int(s) <= MAX_SUPERSAMPLE:
+        raise ValueError(f"supersample {s!r}: expected an integer in 1..{MAX_SUPERSAMPLE}")
+    return int(s)
+
+
+def _fine(cam, ss: int):
+    """The camera of the s x s sub-pixel samples: focal length and centre scaled by s (the caller scales H and W)."""
+    code, fx, fy, cx, cy = cam
+    return code, fx * ss, fy * ss, cx * ss, cy * ss
+
+
+def _queue_rays(cam, H: int, W: int, normalize: bool, pose: torch.Tensor, first: int, count: int, eye: int, half_ipd: float, ss: int,
+                out: torch.Tensor) -> None:
+    """count * ss^2 rays of OUTPUT pixels [first, first + count) of the H x W frame into `out`, on the current stream.  The centre eye
+    at one sample per pixel is ego_camera_rays as before; everything else goes through ego_camera_rays_ex."""
+    lib = _lib.load()
+    if eye == _lib.EYE_CENTRE and ss == 1:
+        code, fx, fy, cx, cy = cam
+        _lib.check(lib.ego_camera_rays(code, H, W, fx, fy, cx, cy, int(normalize), pose.data_ptr(), first, count, out.data_ptr(),
+                                       _lib.stream_handle()), "ego_camera_rays")
+        return
+    code, fx, fy, cx, cy = _fine(cam, ss)
+    _lib.check(lib.ego_camera_rays_ex(code, H * ss, W * ss, fx, fy, cx, cy, int(normalize), pose.data_ptr(), first, count, eye, half_ipd, ss,
+                                      out.data_ptr(), _lib.stream_handle()), "ego_camera_rays_ex")
 
 
 def _camera_args(H: int, W: int, model: str, focal, center) -> Tuple[int, float, float, float, float]:
@@ -53,7 +82,8 @@ def _pose_on_device(c2w, device) -> torch.Tensor:
 
 
 def camera_rays(H: int, W: int, c2w, model: str = "erp", focal=None, center=None, normalize: bool = True, first: int = 0,
-                count: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                count: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None, eye: str = "centre", ipd: float = 0.0,
+                supersample: int = 1) -> torch.Tensor:
     """[count, 6] rays (origin, direction) of pixels [first, first + count) - row-major - of an H x W camera, generated on the device.
 
     model: "erp" (get_ray_directions_360, dataLoader/ray_utils.py:24-40; `normalize` as the ERP datasets do, the rows are bit-equal to
@@ -61,18 +91,29 @@ def camera_rays(H: int, W: int, c2w, model: str = "erp", focal=None, center=None
     get_rays (:85-113; pinhole directions are not normalised, as there).  focal: a number or (fx, fy), required for the pinhole models;
     center: (cx, cy), default (W / 2, H / 2).  c2w: a host array, or a [3][4] (or [4][4]) float32 DEVICE tensor, which is read by the
     kernel when it runs - a captured launch follows a pose that is overwritten between replays.  `out`: a [>= count, 6] float32 device
-    buffer to write into (its first `count` rows are returned)."""
-    code, fx, fy, cx, cy = _camera_args(H, W, model, focal, center)
+    buffer to write into (its first `count` rows are returned).
+
+    eye: "centre", or "left" / "right" (model="erp" only): the rays of one eye of an omnidirectional-stereo panorama - every pixel's
+    origin lies on the viewing circle of diameter `ipd` (scene units, the full distance between the eyes), `ipd / 2` to the left / right
+    of its horizontal viewing direction; the directions are the centre eye's.  supersample = s in 1..4: s x s rays per pixel, [count s^2,
+    6]: row p s^2 + a s + b is pixel (row s + a, col s + b) of the (s H) x (s W) camera with focal length and centre scaled by s, the
+    order `finish_frame(supersample=s)` averages.  H, W, focal, center, first and count stay those of the OUTPUT frame."""
+    cam = _camera_args(H, W, model, focal, center)
+    if eye not in EYES:
+        raise ValueError(f"eye {eye!r}: expected one of {sorted(EYES)}")
+    ss = _supersample(supersample)
+    if not float(ipd) >= 0.0:
+        raise ValueError("camera_rays: ipd must be >= 0")
     count = H * W - first if count is None else count
+    n = max(count, 0) * ss * ss
     if out is None:
-        out = torch.empty(max(count, 0), 6, device=device, dtype=torch.float32)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 6 and out.shape[0] >= count):
-        raise ValueError("camera_rays: `out` must be a contiguous float32 device tensor [>= count, 6]")
+        out = torch.empty(n, 6, device=device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 6 and out.shape[0] >= n):
+        raise ValueError("camera_rays: `out` must be a contiguous float32 device tensor [>= count * supersample^2, 6]")
     with torch.cuda.device(out.device):
         pose = _pose_on_device(c2w, out.device)
-        _lib.check(_lib.load().ego_camera_rays(code, H, W, fx, fy, cx, cy, int(bool(normalize)), pose.data_ptr(), first, count, out.data_ptr(),
-                                               _lib.stream_handle()), "ego_camera_rays")
-    return out[:count]
+        _queue_rays(cam, H, W, bool(normalize), pose, first, count, EYES[eye], float(ipd) / 2, ss, out)
+    return out[:n]
 
 
 def depth_range(near_far) -> Tuple[np.float32, np.float32]:
@@ -112,15 +153,27 @@ def _shapes(H: int, W: int, with_palette: bool, side_by_side: bool) -> List[Tupl
     return [(H, W, 3), (H, W, 3) if with_palette else (H, W)]
 
 
-def _finish(rgb, depth, first, H, W, mi, den, palette, side_by_side, bufs) -> None:
+def frame_shapes(H: int, W: int, with_palette: bool, side_by_side: bool, stereo: Optional[str] = None) -> List[Tuple[int, ...]]:
+    """The shapes of a frame's products: one eye's images, or with stereo="top_bottom" the left eye's on top of the right eye's."""
+    eyes = 1 if stereo is None else 2
+    return [(eyes * s[0],) + tuple(s[1:]) for s in _shapes(H, W, with_palette, side_by_side)]
+
+
+def _finish(rgb, depth, first, H, W, mi, den, palette, side_by_side, bufs, ss: int = 1, offsets=(0, 0)) -> None:
+    """Queues the finish (ss == 1) or resolve-and-finish kernel for rgb.shape[0] / ss^2 pixels from `first` on of an H x W image that
+    begins `offsets[k]` bytes into bufs[k] (the second eye of a stereo frame)."""
     lib = _lib.load()
-    _lib.check(lib.ego_finish_frame(rgb.data_ptr(), depth.data_ptr(), first, rgb.shape[0], H, W, float(mi), float(den), _lib.ptr(palette),
-                                    int(bool(side_by_side)), bufs[0].data_ptr(), bufs[1].data_ptr() if len(bufs) > 1 else None,
-                                    _lib.stream_handle()), "ego_finish_frame")
+    out = [b.data_ptr() + o for b, o in zip(bufs, offsets)] + [None]
+    if ss == 1:
+        _lib.check(lib.ego_finish_frame(rgb.data_ptr(), depth.data_ptr(), first, rgb.shape[0], H, W, float(mi), float(den), _lib.ptr(palette),
+                                        int(bool(side_by_side)), out[0], out[1], _lib.stream_handle()), "ego_finish_frame")
+    else:
+        _lib.check(lib.ego_resolve_frame(rgb.data_ptr(), depth.data_ptr(), first, rgb.shape[0] // (ss * ss), H, W, ss, float(mi), float(den),
+                                         _lib.ptr(palette), int(bool(side_by_side)), out[0], out[1], _lib.stream_handle()), "ego_resolve_frame")
 
 
 @torch.no_grad()
-def finish_frame(rgb: torch.Tensor, depth: torch.Tensor, near_far, palette=None, side_by_side: bool = False, out=None):
+def finish_frame(rgb: torch.Tensor, depth: torch.Tensor, near_far, palette=None, side_by_side: bool = False, out=None, supersample: int = 1):
     """The frame products of renderer.py:227-240: float32 device `rgb` [H, W, 3] (or [n, 3]) and `depth` [H, W] (or [n]) ->
     (rgb8, depth8) uint8, or the one `rgbd` image [H, 2 W, 3] with side_by_side=True (np.concatenate((rgb8, depth8), axis=1)).
 
@@ -132,15 +185,24 @@ def finish_frame(rgb: torch.Tensor, depth: torch.Tensor, near_far, palette=None,
         palette = cv2.applyColorMap(np.arange(256, dtype=np.uint8), cv2.COLORMAP_JET).reshape(256, 3)
 
     out: the tensor(s) to write into, of the returned shapes: device memory or PINNED host memory (the kernel writes mapped host
-    memory directly; synchronise the stream before reading it)."""
+    memory directly; synchronise the stream before reading it).
+
+    supersample = s in 2..4: `rgb` [H, W, s^2, 3] (or [n s^2, 3]) and `depth` [H, W, s^2] (or [n s^2]) hold s x s samples per pixel in
+    `camera_rays(supersample=s)`'s order; clamp(rgb, 0, 1) and nan_to_num(depth) are summed per pixel in float32, in sample order,
+    divided by float32(s^2) and then quantised as above, in one kernel."""
     if not (rgb.is_cuda and depth.is_cuda):
         raise ValueError("finish_frame: rgb and depth must be device tensors (the HIP path has no CPU fallback)")
+    ss = _supersample(supersample)
     flat = rgb.dim() == 2
-    H, W = (1, rgb.shape[0]) if flat else (rgb.shape[0], rgb.shape[1])
+    if flat and rgb.shape[0] % (ss * ss):
+        raise ValueError(f"finish_frame: {rgb.shape[0]} colours are not whole groups of {ss * ss} samples")
+    H, W = (1, rgb.shape[0] // (ss * ss)) if flat else (rgb.shape[0], rgb.shape[1])
     rgb = rgb.reshape(-1, 3).contiguous().float()
     depth = depth.reshape(-1).contiguous().float()
     if depth.shape[0] != rgb.shape[0]:
         raise ValueError(f"finish_frame: {rgb.shape[0]} colours but {depth.shape[0]} depths")
+    if rgb.shape[0] != H * W * ss * ss:
+        raise ValueError(f"finish_frame: supersample={ss} needs rgb [H, W, {ss * ss}, 3] or [n * {ss * ss}, 3]")
     with torch.cuda.device(rgb.device):
         pal = _palette_on_device(palette, rgb.device)
         if side_by_side and pal is None:
@@ -156,7 +218,7 @@ def finish_frame(rgb: torch.Tensor, depth: torch.Tensor, near_far, palette=None,
             if len(bufs) != len(shapes):
                 raise ValueError(f"finish_frame: `out` must hold {len(shapes)} tensor(s)")
         mi, den = depth_range(near_far)
-        _finish(rgb, depth, 0, H, W, mi, den, pal, side_by_side, bufs)
+        _finish(rgb, depth, 0, H, W, mi, den, pal, side_by_side, bufs, ss)
     if flat and out is None and not side_by_side:
         bufs = [b.view(s[1:]) for b, s in zip(bufs, shapes)]   # [n, 3] in, [n, 3] / [n] out
     return bufs[0] if side_by_side else tuple(bufs)
@@ -176,14 +238,30 @@ class FrameRenderer:
     graph=True captures the whole frame once (torch.cuda.graph, on a single stream: no side stream, no parallel branches) and replays
     it per pose; it needs exp_sampling=True (the other schedule inspects device values on the host).  The capture fixes shapes and the
     scene's tables: re-create the object after `upsample_volume_grid` or a change of the alpha mask (`updateAlphaMask`,
-    `use_alpha_mask`), the rule GraphedTrainStep documents for shapes."""
+    `use_alpha_mask`), the rule GraphedTrainStep documents for shapes.
+
+    stereo="top_bottom" (camera="erp", ipd > 0 in scene units): an omnidirectional-stereo panorama for a headset player - the left
+    eye's image on top of the right eye's in ONE image, so every product doubles in height ([2 H, W, 3], [2 H, W], `rgbd` [2 H, 2 W, 3]).
+    The two eyes are rendered one after the other from the one device pose (`camera_rays(eye=...)`); each is a whole image, so the
+    kernels of the second eye get the same buffers at an offset.  supersample = s in 1..4: s x s rays per pixel, averaged before the
+    bytes are formed (`finish_frame(supersample=s)`); a chunk is still `chunk` PIXELS, i.e. chunk s^2 rays per render call."""
 
     def __init__(self, model, H: int, W: int, camera: str = "erp", focal=None, center=None, chunk: int = 16384, palette=None,
-                 side_by_side: bool = False, graph: bool = False, near_far=None, normalize: bool = True, **render_kwargs):
+                 side_by_side: bool = False, graph: bool = False, near_far=None, normalize: bool = True, stereo: Optional[str] = None,
+                 ipd: float = 0.0, supersample: int = 1, **render_kwargs):
         self.model, self.H, self.W, self.chunk = model, int(H), int(W), int(chunk)
         if self.chunk < 1 or self.H < 1 or self.W < 1:
             raise ValueError("FrameRenderer: H, W and chunk must be positive")
         self.cam = _camera_args(self.H, self.W, camera, focal, center)
+        self.ss = _supersample(supersample)
+        if stereo not in (None, "top_bottom"):
+            raise ValueError(f"FrameRenderer: stereo {stereo!r}: expected None or 'top_bottom'")
+        if stereo is not None and self.cam[0] != _lib.CAM_ERP:
+            raise ValueError("FrameRenderer: a stereo panorama needs camera='erp'")
+        if stereo is not None and not float(ipd) > 0.0:
+            raise ValueError("FrameRenderer: a stereo panorama needs ipd > 0 (the distance between the eyes, in scene units)")
+        self.stereo, self.half_ipd = stereo, float(ipd) / 2
+        self.eyes = (_lib.EYE_CENTRE,) if stereo is None else (_lib.EYE_LEFT, _lib.EYE_RIGHT)
         if self.cam[0] != _lib.CAM_ERP and (self.cam[1] == 0.0 or self.cam[2] == 0.0):
             raise ValueError("FrameRenderer: a pinhole camera needs `focal`")
         self.normalize, self.side_by_side = bool(normalize), bool(side_by_side)
@@ -199,9 +277,10 @@ class FrameRenderer:
             self.palette = _palette_on_device(palette, self.device)
             if self.side_by_side and self.palette is None:
                 raise ValueError("FrameRenderer: the side-by-side layout needs a palette")
-            self.shapes = _shapes(self.H, self.W, self.palette is not None, self.side_by_side)
+            self._eye_shapes = _shapes(self.H, self.W, self.palette is not None, self.side_by_side)   # one eye's images
+            self.shapes = frame_shapes(self.H, self.W, self.palette is not None, self.side_by_side, stereo)
             self._pose = torch.zeros(12, device=self.device, dtype=torch.float32)
-            self._rays = torch.empty(min(self.chunk, self.H * self.W), 6, device=self.device, dtype=torch.float32)
+            self._rays = torch.empty(min(self.chunk, self.H * self.W) * self.ss ** 2, 6, device=self.device, dtype=torch.float32)
             self._graph, self._static = None, None
             if graph:
                 self._capture()
@@ -230,16 +309,16 @@ class FrameRenderer:
         self._pose.copy_(stage, non_blocking=True)
 
     def _queue_chunks(self, bufs) -> None:
-        """rays -> render -> finish for every chunk of the frame, on the current stream, from the pose in self._pose into `bufs`."""
-        lib, n = _lib.load(), self.H * self.W
-        code, fx, fy, cx, cy = self.cam
-        for first in range(0, n, self.chunk):
-            count = min(self.chunk, n - first)
-            rays = self._rays[:count]
-            _lib.check(lib.ego_camera_rays(code, self.H, self.W, fx, fy, cx, cy, int(self.normalize), self._pose.data_ptr(), first, count,
-                                           rays.data_ptr(), _lib.stream_handle()), "ego_camera_rays")
-            rgb, depth = self.model(rays, need_alpha=False, **self.kw)[:2]
-            _finish(rgb, depth, first, self.H, self.W, self.mi, self.den, self.palette, self.side_by_side, bufs)
+        """rays -> render -> finish for every chunk of every eye's image, on the current stream, from the pose in self._pose into `bufs`."""
+        n, s2 = self.H * self.W, self.ss ** 2
+        for k, eye in enumerate(self.eyes):
+            offsets = [k * int(np.prod(s)) for s in self._eye_shapes]   # the k-th whole image of each buffer
+            for first in range(0, n, self.chunk):
+                count = min(self.chunk, n - first)
+                rays = self._rays[:count * s2]
+                _queue_rays(self.cam, self.H, self.W, self.normalize, self._pose, first, count, eye, self.half_ipd, self.ss, rays)
+                rgb, depth = self.model(rays, need_alpha=False, **self.kw)[:2]
+                _finish(rgb, depth, first, self.H, self.W, self.mi, self.den, self.palette, self.side_by_side, bufs, self.ss, offsets)
 
     def _capture(self) -> None:
         self._static = self._alloc(pinned=False)
@@ -329,8 +408,9 @@ def evaluation_path(test_dataset, model, c2ws, renderer=None, savePath=None, N_v
     ([H, 2 W, 3] uint8: colour | depth colours, renderer.py:239); with `savePath` writes `{prtx}NNN.png` and `rgbd/{prtx}NNN.png` (PIL).
 
     `img_wh` and `near_far` - and `focal` (and `center`, if it has one) for camera="pinhole" / "pinhole_blender" - come from
-    `test_dataset`.  frame_kwargs go to FrameRenderer (camera, palette, chunk, graph, n_coarse, n_fine, resampling, ...); N_samples > 0
-    is n_coarse unless that is given.  `renderer`: a FrameRenderer to use as it is; anything else (the reference passes its chunk-loop
+    `test_dataset`.  frame_kwargs go to FrameRenderer (camera, palette, chunk, graph, stereo, ipd, supersample, n_coarse, n_fine,
+    resampling, ...); N_samples > 0 is n_coarse unless that is given.  With stereo="top_bottom" the frames and both PNGs are twice as
+    tall: [2 H, 2 W, 3], the left eye's rows above the right eye's.  `renderer`: a FrameRenderer to use as it is; anything else (the reference passes its chunk-loop
     function here) is ignored.  The two mp4 files of renderer.py:242-243 are NOT written (imageio is not a dependency; a warning says
     so).  ndc_ray=True raises NotImplementedError as EgoNeRF.forward does; white_bg, N_vis and compute_extra_metrics are accepted and
     unused, as in the reference."""

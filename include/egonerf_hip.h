@@ -14,7 +14,9 @@
  *   ego_ray_batch_sample    SimpleSampler / ThetaImportanceSampler.nextids   sampler.py:4-38 (device generator, not numpy's stream)
  *   ego_camera_rays         get_ray_directions{,_blender,_360} + get_rays   dataLoader/ray_utils.py:24-113 (pose in device memory)
  *   ego_finish_frame        clamp, * 255, uint8; visualize_depth_numpy; rgbd   renderer.py:227-240, :141-174, utils.py:14-27
- *   ego_sample_ray_exp      EgoNeRF.sample_ray_exp                models/EgoNeRF.py:56-87
+ *   ego_camera_rays_ex      the same with the eyes of an omnidirectional-stereo panorama and s x s rays per pixel (no counterpart)
+ *   ego_resolve_frame       ego_finish_frame of the average of s x s samples per pixel (no counterpart)
+ *   ego_sample_ray_exp      EgoNeRF.sample_ray_exp              models/EgoNeRF.py:56-87
  *   ego_from_cartesian      YinYangSphericalCoords.from_cartesian  models/coordinates.py:468-498
  *   ego_normalize_coord     YinYangSphericalCoords.normalize_coord models/coordinates.py:442-466 (+ :110-131)
  *   ego_density_feature     EgoNeRF.compute_densityfeature         models/EgoNeRF.py:291-347
@@ -259,6 +261,32 @@ int ego_camera_rays(int32_t model, int32_t H, int32_t W, float fx, float fy, flo
  * near 0); a NaN colour likewise becomes 0. */
 int ego_finish_frame(const float* rgb, const float* depth, int64_t first, int64_t count, int32_t H, int32_t W, float mi, float den,
                      const uint8_t* palette, int32_t side_by_side, uint8_t* rgb8, uint8_t* depth8, void* stream);
+
+/* ---- stereo panoramas and supersampled frames (csrc/ego_camera.hip; append-only additions, EGO_ABI_VERSION stays 17) ---- */
+enum { EGO_EYE_CENTRE = 0, EGO_EYE_LEFT = 1, EGO_EYE_RIGHT = 2 };
+
+/* ego_camera_rays with an eye and ss x ss rays per output pixel (ss = 1..4).
+ * H, W, fx, fy, cx, cy describe the FINE camera (the host scales an output frame's size, focal length and centre by ss); first and count
+ * address OUTPUT pixels of the (H / ss) x (W / ss) frame, and count ss^2 rays are written: ray p ss^2 + a ss + b is fine pixel
+ * (row ss + a, col ss + b) of output pixel first + p = row (W / ss) + col.  The samples of a pixel are contiguous, so any chunk of output
+ * pixels resolves on its own (ego_resolve_frame).  Every ray has the bits ego_camera_rays writes for that fine pixel.
+ * eye: EGO_EYE_LEFT / EGO_EYE_RIGHT need EGO_CAM_ERP and give the rays of an omnidirectional-stereo panorama.  In the panorama's camera
+ *   space (x right, y up, z backward; get_ray_directions_360) pixel column col has phi = (1 - 2 (col + 0.5) / W) pi and the horizontal viewing
+ *   direction (-sin phi, 0, -cos phi); the eye sits at o_cam = +-half_ipd (cos phi, 0, -sin phi), + for the right eye (forward x up), and
+ *   o = R o_cam + t = (o_cam.x R_r0 + o_cam.z R_r2) + t_r per row r, float32, every operation rounded on its own.  The direction is the
+ *   centre eye's, bit for bit.  The offset is not tapered toward the poles.  With eye == EGO_EYE_CENTRE or half_ipd == 0 the origin is t.
+ * count == 0 is a no-op; ss outside 1..4, H or W not divisible by ss, an eye other than the centre with a pinhole camera, a negative or
+ * non-finite half_ipd and everything ego_camera_rays refuses return EGO_E_BADARG before anything is queued. */
+int ego_camera_rays_ex(int32_t model, int32_t H, int32_t W, float fx, float fy, float cx, float cy, int32_t normalize, const float* c2w,
+                       int64_t first, int64_t count, int32_t eye, float half_ipd, int32_t ss, float* rays, void* stream);
+
+/* ego_finish_frame for ss x ss samples per pixel: rgb [count ss^2][3], depth [count ss^2] in ego_camera_rays_ex's order; H, W, first, count
+ * and the images are the OUTPUT frame's.  Per pixel: colour = (sum over its samples, in order, of clamp(rgb, 0, 1)) / float(ss^2), depth =
+ * (sum of nan_to_num(depth)) / float(ss^2) - float32 sums, one true division - then ego_finish_frame's arithmetic, saturation, palette and
+ * layouts.  With ss == 1 the bytes are ego_finish_frame's.  One thread per output pixel; whole words are written where ego_finish_frame
+ * writes them. */
+int ego_resolve_frame(const float* rgb, const float* depth, int64_t first, int64_t count, int32_t H, int32_t W, int32_t ss, float mi,
+                      float den, const uint8_t* palette, int32_t side_by_side, uint8_t* rgb8, uint8_t* depth8, void* stream);
 
 int ego_from_cartesian(const ego_scene* sc, const float* xyz, int64_t M, float* c7, void* stream);
 int ego_normalize_coord(const ego_scene* sc, const float* c7, int64_t M, float* c7n, void* stream);
