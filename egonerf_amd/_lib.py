@@ -91,6 +91,7 @@ class RayBankStruct(C.Structure):
 BATCH_SIMPLE, BATCH_THETA = 0, 1   # EGO_BATCH_* of include/egonerf_hip.h
 CAM_ERP, CAM_PINHOLE, CAM_PINHOLE_BLENDER = 0, 1, 2   # EGO_CAM_*
 EYE_CENTRE, EYE_LEFT, EYE_RIGHT = 0, 1, 2   # EGO_EYE_*
+MSI_F32, MSI_F16 = 0, 1   # EGO_MSI_*
 
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SP = C.POINTER(Scene)
@@ -117,6 +118,8 @@ PROTOTYPES = {
     "ego_finish_frame": (C.c_int, [P, P, I64, I64, I32, I32, F32, F32, P, I32, P, P, P]),
     "ego_camera_rays_ex": (C.c_int, [I32, I32, I32, F32, F32, F32, F32, I32, P, I64, I64, I32, F32, I32, P, P]),
     "ego_resolve_frame": (C.c_int, [P, P, I64, I64, I32, I32, I32, F32, F32, P, I32, P, P, P]),
+    "ego_msi_layers": (C.c_int, [P, P, I32, P, I64, I32, P, I32, I64, I64, I32, P, P]),
+    "ego_msi_render": (C.c_int, [P, I64, F32, F32, F32, P, I32, I32, I32, I32, P, P, P, P, P]),
     "ego_copy_out": (C.c_int, [I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), I32, P]),
     "ego_density_feature_backward_workspace_bytes": (I64, [SP, I64, I32]),
     "ego_density_feature_backward": (C.c_int, [SP, P, I64, I32, P, C.POINTER(VmGrad), P, I64, P]),

@@ -288,6 +288,35 @@ int ego_camera_rays_ex(int32_t model, int32_t H, int32_t W, float fx, float fy, 
 int ego_resolve_frame(const float* rgb, const float* depth, int64_t first, int64_t count, int32_t H, int32_t W, int32_t ss, float mi,
                       float den, const uint8_t* palette, int32_t side_by_side, uint8_t* rgb8, uint8_t* depth8, void* stream);
 
+/* ---- multi-sphere images (csrc/ego_msi.hip; append-only additions, EGO_ABI_VERSION stays 17) ----
+ * A scene baked into L concentric shells of PREMULTIPLIED RGBA around a centre, each an Hm x Wm equirectangular image, and views composited
+ * from the shells alone.  A texel is four values (r, g, b, a) of one type: */
+enum { EGO_MSI_F32 = 0 /* float32, 16 B per texel */, EGO_MSI_F16 = 1 /* IEEE half, 8 B per texel */ };
+
+/* Per-sample results of N rays -> per-layer premultiplied RGBA.  z [N][S] ascending along every ray (ego_march_density's z_out), alpha
+ * [N][alpha_stride] (the march's alpha; alpha_stride 0 = S), rgb [N][S][3] (ego_shade's per-sample colours), bounds [L + 1] ascending, dev.
+ * Layer k owns the samples with bounds[k] <= z < bounds[k + 1]; samples outside [bounds[0], bounds[L]) belong to no layer.  Per ray and
+ * layer, in sample order, from t = 1: C += (t * alpha_i) * rgb_i, t *= (1 - alpha_i); then A = 1 - t - float32, every operation rounded on
+ * its own.  (C.r, C.g, C.b, A) goes to texel first + n of layer k of `layers` [L][texels][4] (texels = Hm Wm; aligned to one texel), as
+ * float32 or rounded to the nearest half: one 16-byte or 8-byte store.  A layer without samples writes zeros.  N == 0 is a no-op; bad sizes,
+ * an unknown texel type or a window [first, first + N) outside the image return EGO_E_BADARG before anything is queued. */
+int ego_msi_layers(const float* z, const float* alpha, int32_t alpha_stride, const float* rgb, int64_t N, int32_t S, const float* bounds,
+                   int32_t L, int64_t first, int64_t texels, int32_t texel_type, void* layers, void* stream);
+
+/* Playback: rays [N][6] (origin, direction; 8-byte aligned: what ego_camera_rays writes) -> rgb [N][3], depth [N] float32, what
+ * ego_finish_frame / ego_resolve_frame consume.  (cx, cy, cz) the centre, radii [L] ascending (dev), layers [L][Hm][Wm][4] of texel_type,
+ * background [Hm][Wm][4] of the same type or NULL.  The direction is normalised first, d = dir / |dir| (exact when |dir| is exactly 1; the
+ * pinhole cameras do not normalise their rays).  Per ray, with p = o - c, b = p.d, T = 1, for k = 0 .. L - 1: skip the layer
+ * if radii[k] <= |p| (the eye is not inside it); t_k = -b + sqrt(b b - p.p + R_k R_k); u = (p + t_k d) / R_k; theta = asin(clamp(u.y, -1, 1)),
+ * phi = atan2(-u.x, -u.z) - the inverse of the EGO_CAM_ERP mapping under an identity pose; row = (1 - 2 theta / pi) Hm / 2 - 0.5,
+ * col = (1 - phi / pi) Wm / 2 - 0.5; a bilinear tap (C, A) whose columns wrap modulo Wm and whose rows clamp to [0, Hm - 1];
+ * rgb += T C, depth += (T A) (t_k / |dir|) - the GIVEN ray's parameter, as a model reports it - T *= (1 - A).  After the last layer
+ * rgb += T * (the background's tap in direction d; its alpha is ignored and taken as 1).  Every layer is visited (no early exit), nothing
+ * is clamped; float32 without contraction throughout.  N == 0 is a no-op; bad sizes, an unknown texel type, a NaN centre or misaligned
+ * pointers return EGO_E_BADARG before anything is queued. */
+int ego_msi_render(const float* rays, int64_t N, float cx, float cy, float cz, const float* radii, int32_t L, int32_t Hm, int32_t Wm,
+                   int32_t texel_type, const void* layers, const void* background, float* rgb, float* depth, void* stream);
+
 int ego_from_cartesian(const ego_scene* sc, const float* xyz, int64_t M, float* c7, void* stream);
 int ego_normalize_coord(const ego_scene* sc, const float* c7, int64_t M, float* c7n, void* stream);
 
