@@ -1126,22 +1126,17 @@ int ego_density_feature(const ego_scene* sc, const float* c7n, int64_t M, int32_
   EGO_REQUIRE(sc && c7n && out, "density_feature: null argument");
   const ego_vm_field& f = coarse ? sc->density_coarse : sc->density;
   if (int e = check_field(f, "density_feature")) return e;
-  if (f.n_comp == 16)
-    k_density_feature<16><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else if (f.n_comp == 8)
-    k_density_feature<8><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else if (f.n_comp == 4)
-    k_density_feature<4><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else if (f.n_comp == 12)
-    k_density_feature<12><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else if (f.n_comp == 24)
-    k_density_feature<24><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else if (f.n_comp == 32)
-    k_density_feature<32><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else if (f.n_comp == 48)
-    k_density_feature<48><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out);
-  else
-    return ego_fail(EGO_E_UNSUPPORTED, "density_feature: n_comp %d (supported: 4, 8, 12, 16, 24, 32, 48)", f.n_comp);
+  // one instance per component count of the any-shape envelope (multiples of 4 up to 48: what the march, the scatters and the
+  // backward of this op take), the count a compile-time number so that a tap's C / 4 loads unroll
+  switch (f.n_comp) {
+#define EGO_DENSITY_FEATURE_CASE(C) \
+    case C: k_density_feature<C><<<nblk(M, 256), 256, 0, (hipStream_t)stream>>>(make_field(f), c7n, M, out); break;
+    EGO_DENSITY_FEATURE_CASE(4) EGO_DENSITY_FEATURE_CASE(8) EGO_DENSITY_FEATURE_CASE(12) EGO_DENSITY_FEATURE_CASE(16)
+    EGO_DENSITY_FEATURE_CASE(20) EGO_DENSITY_FEATURE_CASE(24) EGO_DENSITY_FEATURE_CASE(28) EGO_DENSITY_FEATURE_CASE(32)
+    EGO_DENSITY_FEATURE_CASE(36) EGO_DENSITY_FEATURE_CASE(40) EGO_DENSITY_FEATURE_CASE(44) EGO_DENSITY_FEATURE_CASE(48)
+#undef EGO_DENSITY_FEATURE_CASE
+    default: return ego_fail(EGO_E_UNSUPPORTED, "density_feature: n_comp %d (supported: multiples of 4 up to 48)", f.n_comp);
+  }
   return ego_launch_status("k_density_feature");
 }
 

@@ -802,6 +802,70 @@ def capture_shapes_grad():
     save_split("shapes_grad", fx)
 
 
+SHAPE_CORNERS = {   # two corners of the any-shape kernels' envelope (tests/test_hip_shape_corners.py::CORNERS holds all seven; keep in step)
+    "max_encoding": dict(density_n_comp=(48, 48, 48), app_n_comp=(48, 48, 48), app_dim=32, featureC=64, view_pe=8, fea_pe=8, use_envmap=True),
+    "one_feature": dict(density_n_comp=(4, 4, 4), app_n_comp=(44, 44, 44), app_dim=1, featureC=128, view_pe=0, fea_pe=8),
+}
+
+
+def corner_stage_inputs(cfg, M=257):
+    """[M,7] coordinates drawn like capture_shapes' (uniform in +-1.3, grid flag from a seventh uniform) with a few rows moved exactly onto
+    -1, +1 and onto lattice planes, and [M,3] unit directions.  tests/test_hip_shape_corners.py::stage_inputs restates this."""
+    u = torch.from_numpy(synth.hash_uniform(98, 0, M * 7).reshape(M, 7).astype(np.float32))
+    q = u * 2.6 - 1.3
+    q[:, 6] = (u[:, 6] > 0.5).float()
+    node = lambda axis, k: -1.0 + 2.0 * k / (cfg.grid[axis] - 1)
+    for row, g in ((5, 0), (70, 1)):   # one sample of each grid per special value, in two different 64-sample units
+        b = 3 * g
+        q[row, 6], q[row, b:b + 3] = g, -1.0
+        q[row + 1, 6], q[row + 1, b:b + 3] = g, 1.0
+        q[row + 2, 6], q[row + 2, b:b + 3] = g, torch.tensor([node(0, 3), node(1, 4), node(2, 7)])
+        q[row + 3, 6], q[row + 3, b] = g, node(0, 1)
+    dirs = torch.nn.functional.normalize(torch.from_numpy(synth.hash_uniform(97, 0, M * 3).reshape(M, 3).astype(np.float32)) * 2 - 1, dim=-1)
+    return q, dirs
+
+
+def corner_train_inputs(N=67):
+    """The pinned is_train noise and the MSE targets of the corner tests: three draws of one seeded torch.Generator."""
+    g = torch.Generator().manual_seed(5)
+    return torch.rand(N, 16, generator=g), torch.rand(N, 16, generator=g), torch.rand(N, 3, generator=g)
+
+
+def capture_shape_corners():
+    """capture_shapes + capture_shapes_grad at two corners of the supported envelope (app_dim 32 with eight frequencies of both encodings:
+    595 MLP inputs; app_dim 1 on 4 / 44 components): stage ops on 257 coordinates, both renders (67 rays), and the MSE gradients of five
+    tensors through the is_train render with pinned noise.  Pins the ORACLE there; its float64 run is what the HIP kernels are compared with."""
+    fx = {}
+    for name, kw in SHAPE_CORNERS.items():
+        cfg = synth.SceneConfig(n_voxel=20 ** 3, envmap_res_H=16, **kw)
+        weights = synth.make_weights(cfg, seed=11)
+        model, coords = build_reference(cfg, weights)
+        rays = torch.from_numpy(synth.make_rays(67, seed=5))
+        q, dirs = corner_stage_inputs(cfg)
+        af = model.compute_appfeature(q)
+        fx.update({f"{name}/coords": np_(q), f"{name}/dirs": np_(dirs), f"{name}/density": np_(model.compute_densityfeature(q)),
+                   f"{name}/density_coarse": np_(model.compute_coarse_densityfeature(q)), f"{name}/app": np_(af),
+                   f"{name}/rgb_samples": np_(model.renderModule(q, dirs, af))})
+        o = run_forward(model, rays, n_coarse=24, n_fine=0, resampling=False)
+        fx.update({f"{name}/nr_rgb": np_(o[0]), f"{name}/nr_depth": np_(o[1]), f"{name}/nr_alpha": np_(o[4])})
+        o = run_forward(model, rays, n_coarse=16, n_fine=16, resampling=True, use_coarse_sample=True)
+        fx.update({f"{name}/rs_rgb": np_(o[0]), f"{name}/rs_depth": np_(o[1])})
+        model.train()
+        jit, uu, gt = corner_train_inputs()
+        model.zero_grad()
+        with patched_rand([jit], [uu]):
+            o = run_forward(model, rays, n_coarse=16, n_fine=16, resampling=True, use_coarse_sample=True, is_train=True)
+        loss = torch.mean((o[0] - gt) ** 2)
+        loss.backward()
+        fx.update({f"{name}/jitter": np_(jit), f"{name}/u": np_(uu), f"{name}/gt": np_(gt), f"{name}/rgb": np_(o[0]),
+                   f"{name}/loss": np.float32(loss.item())})
+        grads = dict(model.named_parameters())
+        for k in ("density_plane_yin.0", "app_line_yang.2", "basis_mat_yin.weight", "renderModule.mlp.0.weight", "renderModule.mlp.4.bias"):
+            fx[f"{name}/grad/{k}"] = np_(grads[k].grad)
+    fx["seed_weights"], fx["seed_rays"] = 11, 5
+    save_split("shape_corners", fx)
+
+
 HEADS = {   # the other appearance heads EgoNeRF.forward runs with (tensorBase.py:186-200); `fea_pe` is what opt.py passes, MLPRender ignores it
     "mlp_head": dict(shadingMode="MLP", app_dim=27, view_pe=2, fea_pe=2, featureC=128),
     "mlp_head_small": dict(shadingMode="MLP", density_n_comp=(8, 8, 8), app_n_comp=(24, 24, 24), app_dim=12, view_pe=6, fea_pe=6, featureC=64),
@@ -853,7 +917,7 @@ def capture_heads():
 
 if __name__ == "__main__":
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["tiny", "stages", "full", "alpha_mask", "checkpoint", "ours_checkpoint", "train_extras", "metrics", "plainexp", "sh", "uniform", "ricoh", "envmap_full", "ws", "skip", "omniblender", "shapes", "shapes_grad", "heads"]
+    which = sys.argv[1:] or ["tiny", "stages", "full", "alpha_mask", "checkpoint", "ours_checkpoint", "train_extras", "metrics", "plainexp", "sh", "uniform", "ricoh", "envmap_full", "ws", "skip", "omniblender", "shapes", "shapes_grad", "heads", "shape_corners"]
     for name in which:
         globals()["capture_" + name]()
         print("captured", name)
