@@ -92,6 +92,7 @@ BATCH_SIMPLE, BATCH_THETA = 0, 1   # EGO_BATCH_* of include/egonerf_hip.h
 CAM_ERP, CAM_PINHOLE, CAM_PINHOLE_BLENDER = 0, 1, 2   # EGO_CAM_*
 EYE_CENTRE, EYE_LEFT, EYE_RIGHT = 0, 1, 2   # EGO_EYE_*
 MSI_F32, MSI_F16 = 0, 1   # EGO_MSI_*
+DIST_LINEAR, DIST_LOG, DIST_DISPARITY = 0, 1, 2   # EGO_DIST_*
 
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SP = C.POINTER(Scene)
@@ -177,6 +178,7 @@ PROTOTYPES = {
     "ego_l1_table": (C.c_int, [P, I64, F32, P, P, P]),
     "ego_line_ortho": (C.c_int, [P, I32, I32, F32, P, P, P]),
     "ego_ray_entropy": (C.c_int, [P, I64, I32, I32, P, P, P]),
+    "ego_ray_distortion": (C.c_int, [P, I32, P, I64, I32, F32, F32, I32, P, P, P]),
     "ego_resample_table": (C.c_int, [P, I32, I32, I32, P, P, I32, I32, P, P]),
     "ego_adam_step": (C.c_int, [C.POINTER(AdamTensor), I32, F32, F32, F32, I32, P]),
     "ego_adam_step_graph": (C.c_int, [C.POINTER(AdamTensor), I32, F32, F32, F32, C.c_double, P, P]),

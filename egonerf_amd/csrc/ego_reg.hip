@@ -1,6 +1,7 @@
 // Training-step table ops of the EgoNeRF path that sit next to the render (train.py:245-330): the TV / L1 / ortho
-// regularisers with their gradients fused into the same pass, the ray-entropy loss, coarse-to-fine table resampling and
-// a multi-tensor Adam.  All tables are channel-last ([H][W][C] fp32), all kernels are HBM-bound streaming passes.
+// regularisers with their gradients fused into the same pass, the ray-entropy loss, the distortion regulariser (per ray, through
+// alpha like the entropy), coarse-to-fine table resampling and a multi-tensor Adam.  All tables are channel-last ([H][W][C] fp32),
+// all kernels are HBM-bound streaming passes.
 #include "ego_device.h"
 #include "ego_host.h"
 
@@ -118,6 +119,162 @@ __global__ __launch_bounds__(256) void k_ray_entropy(const float* __restrict__ a
   if (lane == 0 && value) atomicAdd(value, (double)ent * (double)invN);
 }
 
+// ---- Distortion regulariser (Mip-NeRF 360's, in the point-sampled form used with voxel-grid NeRFs; not in the reference) ----
+// One ray with samples z_0 <= ... <= z_{S-1}.  Sample i covers [z_i, z_{i+1}], z_S = z_{S-1} + (z_{S-1} - z_{S-2}): the render's own
+// quadrature (dist = diff(z), last repeated, EgoNeRF.py:517-518).  The S + 1 ends go through a monotone map to s in [0, 1]:
+//   linear     s = (z - near) / (far - near)
+//   log        s = log(max(z, near) / near) / log(far / near)            (the exponential schedule has equal widths here)
+//   disparity  s = (1 / near - 1 / max(z, near)) / (1 / near - 1 / far)
+// m_i = (s_i + s_{i+1}) / 2, delta_i = s_{i+1} - s_i (ties in z give delta = 0), and with the render's weights (tensorBase.py:22-27)
+// w_i = alpha_i T_i, T_i = prod_{j<i} (1 - alpha_j + 1e-10):
+//   loss = (1 / N) sum_rays [ sum_i sum_j w_i w_j |m_i - m_j| + (1 / 3) sum_i w_i^2 delta_i ]
+// z is a constant (the fine z is detached, EgoNeRF.py:534); alpha is the only differentiable input.
+//
+// O(S): m ascends, so with W_{<i} = sum_{j<i} w_j, WM_{<i} = sum_{j<i} w_j m_j (and the same sums over j > i)
+//   double sum = 2 sum_i w_i (m_i W_{<i} - WM_{<i})
+//   G_i = dL / dw_i = 2 [ m_i (W_{<i} - W_{>i}) - (WM_{<i} - WM_{>i}) ] + (2 / 3) w_i delta_i
+//   R_{S-1} = 0, R_i = G_{i+1} alpha_{i+1} + (1 - alpha_{i+1} + 1e-10) R_{i+1}            (k_raw2alpha_bwd's recurrence: no division,
+//   g_alpha_i = T_i (G_i - R_i) / N                                                         so alpha = 1 is harmless)
+// The differences of the running sums cancel when a ray's mass sits in neighbouring samples, so W, WM, m and delta are carried in
+// float64 (w m is the product of two float32 values, exact in float64); T, the map and the R recurrence stay float32.
+//
+// One wave per ray, 64 samples per pass (lane = sample), wave scans with a carry between the passes.  The forward sweep produces T,
+// the running sums, their totals and the value; with a gradient it parks T_i in g_alpha[i].  The reverse sweep re-reads alpha, z
+// (cache) and the parked T, forms the sums over j >= i by a reverse scan, G, and R by a reverse scan of the affine maps
+// x -> (1 - alpha_i + 1e-10) x + G_i alpha_i, and overwrites g_alpha.  Every sum has a fixed order: the gradient is bit-reproducible.
+struct DistMap {
+  int space;
+  float near_, scale;  // scale = 1 / (far - near), 1 / log(far / near), 1 / (1 / near - 1 / far): rounded once from float64
+};
+
+__device__ __forceinline__ float dist_map(float z, const DistMap& g) {
+  if (g.space == EGO_DIST_LINEAR) return (z - g.near_) * g.scale;
+  const float zc = fmaxf(z, g.near_);
+  if (g.space == EGO_DIST_LOG) return logf(zc / g.near_) * g.scale;
+  return (1.f / g.near_ - 1.f / zc) * g.scale;
+}
+
+struct DistSample {
+  float a, f;       // alpha_i, 1 - alpha_i + 1e-10 (0 and 1 beyond the ray's end: the identities of every scan below)
+  double m, delta;
+};
+
+__device__ __forceinline__ DistSample dist_sample(const float* __restrict__ a_row, const float* __restrict__ z_row, float z_end, int i, int S,
+                                                  const DistMap& g) {
+  DistSample o;
+  o.a = i < S ? a_row[i] : 0.f;
+  o.f = __fadd_rn(__fsub_rn(1.f, o.a), 1e-10f);
+  const double s0 = (double)dist_map(i < S ? z_row[i] : z_end, g), s1 = (double)dist_map(i + 1 < S ? z_row[i + 1] : z_end, g);
+  o.m = 0.5 * (s0 + s1);
+  o.delta = s1 - s0;
+  return o;
+}
+
+// wave64 inclusive sums in lane order (scan_add: over lanes <= lane, rscan_add: over lanes >= lane), float64
+__device__ __forceinline__ double wave_scan_add(double v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+__device__ __forceinline__ double wave_rscan_add(double v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_down(v, d, 64);
+    if (lane + d < 64) v += o;
+  }
+  return v;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// One ray by one wave (all 64 lanes run every scan) -> the ray's term of the value; with g_row, the ray's gradient row is written.
+__device__ __forceinline__ double dist_ray(const float* __restrict__ a_row, const float* __restrict__ z_row, float* __restrict__ g_row, int64_t N,
+                                           int S, int stride, const DistMap& map, int lane) {
+  const float z_end = z_row[S - 1] + (z_row[S - 1] - z_row[S - 2]);
+  const int passes = (S + 63) >> 6;
+
+  float cT = 1.f;               // carries: T, W_{<i}, WM_{<i} at the pass's first sample
+  double cW = 0.0, cWM = 0.0, part = 0.0;
+  for (int p = 0; p < passes; ++p) {
+    const int i = p * 64 + lane;
+    const DistSample s = dist_sample(a_row, z_row, z_end, i, S, map);
+    const float prod = wave_scan_mul(s.f, lane);
+    float before = __shfl_up(prod, 1, 64);
+    if (lane == 0) before = 1.f;
+    const float T = cT * before;
+    cT *= __shfl(prod, 63, 64);
+    const double w = (double)(s.a * T), wm = w * s.m;
+    const double W = cW + wave_scan_add(w, lane), WM = cWM + wave_scan_add(wm, lane);   // over j <= i
+    part += 2.0 * w * (s.m * (W - w) - (WM - wm)) + w * w * s.delta / 3.0;
+    cW = __shfl(W, 63, 64);
+    cWM = __shfl(WM, 63, 64);
+    if (g_row && i < S) g_row[i] = T;
+  }
+  // The ray's term, rounded to a multiple of 2^-51.  With z in [near, far] the mapped ends stay within [0, 2] (z_S <= 2 far) and
+  // sum w <= 1, so a ray's term is at most s_S - s_0 <= 2 and so is the total: below 4, up to which every sum of such multiples - a
+  // block's, and the adds into the zeroed `value` - is exact.  The result then does not depend on the order in which the blocks arrive
+  // (value-only, joint and repeated calls return the same bits); the rounding costs at most N 2^-52 absolute.
+  const double invN = 1.0 / (double)N;
+  const double term = rint(wave_sum_f64(part) * invN * 0x1p51) * 0x1p-51;
+  if (!g_row) return term;
+
+  const double Wt = cW, WMt = cWM;
+  double cGeW = 0.0, cGeWM = 0.0;   // carries: the sums over the samples behind the pass, and R at the pass's last sample
+  float cR = 0.f;
+  for (int p = passes - 1; p >= 0; --p) {
+    const int i = p * 64 + lane;
+    const DistSample s = dist_sample(a_row, z_row, z_end, i, S, map);
+    const float T = i < S ? g_row[i] : 0.f;
+    const double w = (double)(s.a * T), wm = w * s.m;
+    const double geW = cGeW + wave_rscan_add(w, lane), geWM = cGeWM + wave_rscan_add(wm, lane);   // over j >= i
+    const double G64 = 2.0 * (s.m * ((Wt - geW) - (geW - w)) - ((WMt - geWM) - (geWM - wm))) + (2.0 / 3.0) * w * s.delta;
+    cGeW = __shfl(geW, 0, 64);
+    cGeWM = __shfl(geWM, 0, 64);
+    const float G = (float)G64;
+    // lane i: the map R_i -> R_{i-1}; after the scan the composition of the maps of lanes i .. 63
+    float A = s.f, B = G * s.a;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float Ao = __shfl_down(A, d, 64), Bo = __shfl_down(B, d, 64);
+      if (lane + d < 64) {
+        B = fmaf(A, Bo, B);
+        A *= Ao;
+      }
+    }
+    const float R_before = fmaf(A, cR, B);   // R_{i-1}
+    float R = __shfl_down(R_before, 1, 64);
+    if (lane == 63) R = cR;
+    cR = __shfl(R_before, 0, 64);
+    if (i < S) g_row[i] = T * (G - R) * (float)invN;
+  }
+  for (int c = S + lane; c < stride; c += 64) g_row[c] = 0.f;
+  return term;
+}
+
+// Four rays per block.  The adds into `value` all hit one address and serialise (12.5 ns each, measured: what the entropy kernel's
+// time consists of), so the block's four terms are summed first and added once.
+__global__ __launch_bounds__(256) void k_ray_distortion(const float* __restrict__ alpha, int stride, const float* __restrict__ z, int64_t N,
+                                                        int S, DistMap map, double* __restrict__ value, float* __restrict__ g_alpha) {
+  __shared__ double terms[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t ray = (int64_t)blockIdx.x * 4 + wave;
+  double term = 0.0;
+  if (ray < N)   // wave-uniform
+    term = dist_ray(alpha + ray * stride, z + ray * S, g_alpha ? g_alpha + ray * stride : nullptr, N, S, stride, map, lane);
+  if (!value) return;
+  if (lane == 0) terms[wave] = term;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(value, (terms[0] + terms[1]) + (terms[2] + terms[3]));
+}
+
 // coordinates.py:27-39 / :226-266: bilinear (align_corners, zero padding) resample of a channel-last table at per-axis
 // normalised coordinates xs [W2], ys [H2]
 __global__ void k_resample_table(const float* __restrict__ src, int C, int H, int W, const float* __restrict__ xs,
@@ -227,6 +384,22 @@ int ego_ray_entropy(const float* alpha, int64_t N, int32_t S, int32_t stride, do
   EGO_REQUIRE(alpha && (value || g_alpha), "ray_entropy: null argument");
   k_ray_entropy<<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(alpha, N, S, stride, value, g_alpha);
   return ego_launch_status("k_ray_entropy");
+}
+
+int ego_ray_distortion(const float* alpha, int32_t alpha_stride, const float* z, int64_t N, int32_t S, float near_, float far_, int32_t space,
+                       double* value, float* g_alpha, void* stream) {
+  EGO_TRACE("ego_ray_distortion");
+  EGO_REQUIRE(N >= 0 && (N + 3) / 4 <= INT32_MAX && S >= 2 && alpha_stride >= S, "ray_distortion: bad size (S >= 2, alpha_stride >= S)");
+  EGO_REQUIRE(space == EGO_DIST_LINEAR || space == EGO_DIST_LOG || space == EGO_DIST_DISPARITY, "ray_distortion: unknown space");
+  EGO_REQUIRE(far_ > near_ && far_ < INFINITY && near_ > -INFINITY, "ray_distortion: needs finite near < far");
+  EGO_REQUIRE(space == EGO_DIST_LINEAR || near_ > 0.f, "ray_distortion: the log and disparity spaces need near > 0");
+  if (N == 0) return EGO_OK;
+  EGO_REQUIRE(alpha && z && (value || g_alpha), "ray_distortion: null argument");
+  const double n = (double)near_, f = (double)far_;
+  const double span = space == EGO_DIST_LINEAR ? f - n : space == EGO_DIST_LOG ? log(f / n) : 1.0 / n - 1.0 / f;
+  const DistMap map{space, near_, (float)(1.0 / span)};
+  k_ray_distortion<<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(alpha, alpha_stride, z, N, S, map, value, g_alpha);
+  return ego_launch_status("k_ray_distortion");
 }
 
 int ego_resample_table(const float* src, int32_t C, int32_t H, int32_t W, const float* xs, const float* ys, int32_t H2, int32_t W2,

@@ -5,6 +5,7 @@ the stored gradient (scaled by the incoming one) back in backward, so `total_los
     utils.py:155-171   TVLoss                       -> TVLoss
     utils.py:175-183   ray_entropy_loss             -> ray_entropy_loss
     EgoNeRF.py:189-228 vector_comp_diffs, density_L1, TV_loss_density / TV_loss_app  (methods of model.EgoNeRF call in here)
+    (not in the reference) Mip-NeRF 360's distortion regulariser                    -> distortion_loss
 """
 from __future__ import annotations
 
@@ -107,3 +108,49 @@ def ray_entropy_loss(alpha: torch.Tensor) -> torch.Tensor:
     """utils.py:175-183: mean over rays of the entropy (bits) of alpha / (sum alpha + 1e-10); alpha [N, S(+1)] as returned
     by EgoNeRF.forward (the envmap's trailing ones column included, like the reference)."""
     return _RayEntropy.apply(alpha)
+
+
+_DIST_SPACES = {"linear": _lib.DIST_LINEAR, "log": _lib.DIST_LOG, "disparity": _lib.DIST_DISPARITY}
+
+
+class _RayDistortion(torch.autograd.Function):
+    @staticmethod
+    @_lib.device_guard
+    def forward(ctx, alpha: torch.Tensor, z: torch.Tensor, near: float, far: float, space: int):
+        lib, st = _lib.load(), _lib.stream_handle()
+        a = alpha.detach()
+        if a.dtype != torch.float32 or not a.is_contiguous():
+            a = a.float().contiguous()
+        N, S = z.shape
+        value = torch.zeros(1, dtype=torch.float64, device=a.device)
+        g = torch.empty_like(a) if alpha.requires_grad else None
+        _lib.check(lib.ego_ray_distortion(a.data_ptr(), a.shape[1], z.data_ptr(), N, S, near, far, space, value.data_ptr(), _lib.ptr(g), st),
+                   "ego_ray_distortion")
+        ctx.g = g
+        return value.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g = ctx.g
+        ctx.g = None
+        return (None if g is None else g * g_out), None, None, None, None
+
+
+def distortion_loss(alpha: torch.Tensor, z: torch.Tensor, near_far: Sequence[float], space: str = "log") -> torch.Tensor:
+    """Mip-NeRF 360's distortion regulariser in its point-sampled form (not in the reference): the mean over rays of
+    sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i, with the render's weights w and the midpoints m / widths delta of the
+    samples' intervals [z_i, z_{i+1}] mapped to [0, 1] by `space` ("linear", "log": equal widths for the exponential schedule,
+    "disparity"); csrc/ego_reg.hip states the formula and its O(S) form.  alpha [N, S] or [N, S + 1] as returned by EgoNeRF.forward
+    (an envmap's trailing ones column takes no part and gets a zero gradient); z [N, S] float32, the samples' distances of the SAME
+    render: `model.last_train_z`.  z is a constant, alpha the only differentiable input."""
+    if space not in _DIST_SPACES:
+        raise ValueError(f"distortion_loss: space must be one of {sorted(_DIST_SPACES)}, not {space!r}")
+    near, far = float(near_far[0]), float(near_far[1])
+    if not far > near or (space != "linear" and not near > 0.0):
+        raise ValueError(f"distortion_loss: needs near < far, and near > 0 for the {space!r} space (near_far = {near}, {far})")
+    if alpha.dim() != 2 or z.dim() != 2 or alpha.shape[0] != z.shape[0] or alpha.shape[1] - z.shape[1] not in (0, 1) or z.shape[1] < 2:
+        raise RuntimeError(f"distortion_loss: alpha {tuple(alpha.shape)} and z {tuple(z.shape)} must be [N, S] or [N, S + 1] and [N, S], S >= 2")
+    if z.dtype != torch.float32 or z.device != alpha.device:
+        raise RuntimeError("distortion_loss: z must be a float32 tensor on alpha's device")
+    _require_cuda(alpha, "distortion_loss")
+    return _RayDistortion.apply(alpha, z.detach().contiguous(), near, far, _DIST_SPACES[space])

@@ -387,6 +387,9 @@ class EgoNeRF(TensorBase):
         self._packed = None
         self._packed_versions = None
         self._sched_cache = {}
+        # The sample distances [N, S] of the latest TRAINING render (train.render_train: the march's own buffer, no gradient): what
+        # losses.distortion_loss needs next to the returned alpha.  Eval renders leave it alone.
+        self.last_train_z = None
         self._mlp_precision = "f16f6"   # inference default; differentiable calls always use the three-term fp16 split
         # Differentiable calls of the tuned head keep the activations that only feed the weight-gradient products (x, h1, h2, dh1, dh2)
         # as halves (~2^-12 relative per operand against the reference's fp32 autograd, nothing above 65504).  True (or

@@ -431,6 +431,7 @@ class RenderFunction(torch.autograd.Function):
         S = _lib.sample_count(opts["n_coarse"], opts["n_fine"], opts["resampling"], opts["use_coarse_sample"])
         plan = _plan_step(model, sc, N, S)
         b = _march(plan, sc, model, rays, opts)
+        model.last_train_z = b["z"]   # the 5-tuple has no place for it; losses.distortion_loss reads it right after the render
         rgb = _empty(dev, N, S, 3)
         sort_ws = _sort(plan, sc, b["coords"])
         sc = _head_scene(sc, plan, pack=True)
@@ -520,7 +521,8 @@ class EnvRadianceFunction(torch.autograd.Function):
 
 def render_train(model, rays, n_coarse, n_fine=0, resampling=False, use_coarse_sample=True, jitter: Optional[torch.Tensor] = None,
                  u: Optional[torch.Tensor] = None, z_coarse: Optional[torch.Tensor] = None):
-    """Differentiable EgoNeRF.forward (is_train semantics) -> (rgb_map, depth, bg_map|None, env_map|None, alpha)."""
+    """Differentiable EgoNeRF.forward (is_train semantics) -> (rgb_map, depth, bg_map|None, env_map|None, alpha).  The samples' distances
+    [N, S] stay on the model as `model.last_train_z` (the march's own buffer, no gradient): losses.distortion_loss takes them."""
     opts = dict(n_coarse=int(n_coarse), n_fine=int(n_fine), resampling=bool(resampling), use_coarse_sample=bool(use_coarse_sample),
                 jitter=jitter, u=u, z_coarse=z_coarse)
     params = differentiable_params(model)
@@ -583,6 +585,9 @@ class GraphedTrainStep:
     capture.  A `loss_fn` whose fourth parameter is named `sched` / `schedule` (or any loss_fn with `schedule_aware=True`) receives `self.schedule` (a TrainSchedule: device-side iteration counter advanced
     inside the graph) and writes e.g. `sched.decayed(TV_weight_density, lr_factor, active_before=iter_ignore_TV) * model.TV_loss_density(tv)`;
     tests/test_hip_train_graph.py::test_graphed_step_with_decaying_regulariser_weights pins that against the eager loop.
+    The ray-entropy term is `ray_entropy_loss(alpha) * w`.  The distortion term also needs the samples' distances, which the 5-tuple
+    does not carry: every training render leaves them on the model, and the loss_fn reads them right after the render,
+    `distortion_loss(alpha, model.last_train_z, model.near_far) * w` (tests/test_hip_distortion.py pins it against the eager loop).
 
     `batch_source` (a DeviceSimpleSampler / DeviceThetaImportanceSampler of egonerf_amd.sampler over a RayBank): the batch is drawn
     INSIDE the graph - the iteration starts with the source's one launch writing indices, rays and colours into the static buffers

@@ -613,6 +613,21 @@ int ego_line_ortho(const float* line, int32_t C, int32_t n, float scale, double*
 /* utils.py:175-183 ray_entropy_loss over alpha [N][S] (row stride `stride`): value += mean_ray H(alpha / (sum alpha + 1e-10)),
  * g_alpha (same stride, WRITTEN) = d value / d alpha. */
 int ego_ray_entropy(const float* alpha, int64_t N, int32_t S, int32_t stride, double* value, float* g_alpha, void* stream);
+/* Distortion regulariser (Mip-NeRF 360, point-sampled form; not in the reference; append-only addition, EGO_ABI_VERSION stays 17).
+ * Sample i of a ray covers [z_i, z_{i+1}] (z_S = z_{S-1} + (z_{S-1} - z_{S-2}): the render's quadrature); the ends are mapped to
+ * s in [0, 1] by `space`, m_i and delta_i are the mapped interval's midpoint and width, w_i = alpha_i prod_{j<i} (1 - alpha_j + 1e-10):
+ *   value += (1 / N) sum_rays [ sum_i sum_j w_i w_j |m_i - m_j| + (1 / 3) sum_i w_i^2 delta_i ]
+ * in O(S) per ray (csrc/ego_reg.hip states the algebra).  alpha [N][alpha_stride] (the first S columns are used: an envmap's trailing
+ * ones column does not enter), z [N][S] ascending per ray and constant.  `value`: float64 device scalar zeroed by the caller, or NULL;
+ * each ray's term is rounded to a multiple of 2^-51 (at most N 2^-52 absolute in all), which makes the adds exact and the result
+ * independent of the order in which the rays arrive.  g_alpha [N][alpha_stride] or NULL: WRITTEN, d value / d alpha,
+ * columns at or beyond S as 0, bit-reproducible; it must not overlap alpha.  Requires S >= 2, alpha_stride >= S, finite near_ < far_,
+ * near_ > 0 for the log and disparity spaces, a known space, non-null alpha and z, and value or g_alpha; N == 0 is a no-op.  One
+ * launch, no allocation, no synchronisation. */
+enum { EGO_DIST_LINEAR = 0 /* (z - near) / (far - near) */, EGO_DIST_LOG = 1 /* log(max(z, near) / near) / log(far / near) */,
+       EGO_DIST_DISPARITY = 2 /* (1 / near - 1 / max(z, near)) / (1 / near - 1 / far) */ };
+int ego_ray_distortion(const float* alpha, int32_t alpha_stride, const float* z, int64_t N, int32_t S, float near_, float far_, int32_t space,
+                       double* value, float* g_alpha, void* stream);
 /* coordinates.py:27-39 and :226-266 (up_sampling_VM): bilinear, align_corners=True, zero-padded resample of a table at
  * per-axis normalised positions xs [W2], ys [H2] (device) -> dst [H2][W2][C]. */
 int ego_resample_table(const float* src, int32_t C, int32_t H, int32_t W, const float* xs, const float* ys, int32_t H2, int32_t W2,
