@@ -1,20 +1,15 @@
-// libegonerf_hip.so, part 9: the table-gradient scatter without atomics - bit-reproducible (SURVEY 5 "sorted-segment mode", VERDICT r04
-// item 3).  Backward of F.grid_sample in compute_densityfeature / compute_appfeature (models/EgoNeRF.py:291-347, :349-413) under
+// libegonerf_hip.so, part 9: the table-gradient scatter without atomics - bit-reproducible (SURVEY 5 "sorted-segment mode").
+// Backward of F.grid_sample in compute_densityfeature / compute_appfeature (models/EgoNeRF.py:291-347, :349-413) under
 // train.py:312-314, for the tuned table shapes (16 density / 48 appearance components).
 //
 // k_vm_scatter (ego_train.hip) walks rays and sends one float-atomic line per (cell run, tap): ~16 M atomic line requests per 8192 x 256
-// step at the L2's ~21 G/s plus ~0.95 ms of cell bookkeeping, and a sum whose order changes from run to run.  Here the step's samples are
-// binned by texel CELL once (three stable LSD radix sorts of 18-bit keys, 9 bits per pass, all three sorts in the same launches:
-// k_radix_hist / k_radix_scan / k_radix_scatter below), and every gradient texel is then written exactly once from sums taken in a
-// fixed order:
+// step at the L2's ~21 G/s plus ~0.95 ms of cell bookkeeping, and a sum whose order changes from run to run.  Here the samples arrive
+// binned by texel cell (ego_scatter_sort.hip: permutations, cell starts, step lists; layout in ego_sorted_geom.h), and every gradient
+// texel is written exactly once from sums taken in a fixed order.  No zero fill of the gradient tables is needed, no atomics on global
+// memory, and two runs return the same bits.  This file holds the scatters, in two forms:
 //
-//   ego_scatter_sort      : coords -> three permutations + cell start offsets (needs only the forward's coordinates: it runs on the side
-//                           stream next to the dumping shade forward, and both fields share it)
-//       sort 0: key (grid, phi cell, r cell)     -> cells of plane 1 (x = r, y = phi), ranges of line 0 (phi)
-//       sort 1: key (grid, r cell, theta cell)   -> cells of plane 0 (x = r, y = theta), ranges of line 2 (r)
-//       sort 2: key (grid, theta cell, phi cell) -> cells of plane 2 (x = theta, y = phi), ranges of line 1 (theta)
-//     a cell = the unclamped west tap index + 1 (0 .. n); a sample whose two taps of an axis are both out of range has no gradient
-//     through that axis and sorts behind everything else
+// The two-pass form (EGO_SORTED_WALK=0; its line kernels also serve, under the walk, every line whose window does not fit the LDS, and
+// all lines with EGO_SORTED_LINES=separate; the whole form serves batches above 2^30 dv elements):
 //   k_sorted_plane        : one 16-lane group per cell (lane = channel of a 64-byte line, as in k_vm_scatter), four cells per wave: the
 //                           cell's samples (contiguous, in ascending sample order: the sort is stable) are added in that order into four
 //                           corner sums in registers, which go to a cell buffer
@@ -22,516 +17,29 @@
 //   k_sorted_line         : a line cell holds thousands of samples: fixed 256-sample sub-blocks of its range, one wave each -> partial sums
 //   k_sorted_line_final   : texel = its two cells' partials, added in sub-block order
 //
-// No zero fill of the gradient tables is needed (every texel is written), no atomics, and two runs return the same bits.
-//
-// Round 6: ONE pass over the gradient activations.  The line kernels above read every sample's d a second time
-// (1.2 GB of dv in another random order) plus four random co-plane taps per sample: 0.68 ms and 4.6 GB of fetches per step.  A plane
-// cell's samples all use the SAME four plane texels, so the line gradient of the plane's own line (the THIRD axis, the one that is not
-// in the sort key) costs four multiply-adds per sample next to the plane's - but its samples land in arbitrary line texels, so the sums
-// cannot be taken in a fixed order.  They are taken in an order-INDEPENDENT arithmetic instead: every contribution is converted to a
-// 64-bit fixed-point integer (one power-of-two unit per table, derived from max |d| x max |plane texel|, both computed on the device:
-// >= 40 bits below the largest possible contribution - an fp32 sum keeps 24) and added with integer LDS atomics into a per-workgroup
-// table of the line; integer addition is associative, so any order gives the same bits.  k_sorted_walk = the plane walk + those
-// four multiply-adds + two ds_add_u64 per channel lane and sample; k_fused_line_final adds the workgroups' tables and converts once.
-// Lines too long for the LDS are cut into BLOCKS by the sort keys (a workgroup's table holds one block's window), so every line rides
-// along on every shipped grid; the separate line kernels stay as the fall-back (EGO_SORTED_LINES=separate forces them for every line,
-// EGO_SORTED_WALK=0 the whole round-5 form).  Late in the round the appearance walk also took the basis gradient along (BAS: it holds
-// plane value x line value, one bf16 MFMA per iteration multiplies it with the sample's feature-slot gradients): no v dump, no d(basis) pass.
+// The walk (the default): ONE pass over the gradient activations.  The line kernels read every sample's d a second time (1.2 GB of dv in
+// another random order) plus four random co-plane taps per sample: 0.68 ms and 4.6 GB of fetches per step.  A plane cell's samples all
+// use the SAME four plane texels, so the line gradient of the plane's own line (the THIRD axis, the one that is not in the sort key)
+// costs four multiply-adds per sample next to the plane's - but its samples land in arbitrary line texels, so the sums cannot be taken
+// in a fixed order.  They are taken in an order-INDEPENDENT arithmetic instead: every contribution is converted to a 64-bit fixed-point
+// integer (one power-of-two unit per table, derived from max |d| x max |plane texel|, both computed on the device: k_fx_absmax /
+// k_fx_setup; >= 40 bits below the largest possible contribution - an fp32 sum keeps 24) and added with integer LDS atomics into a
+// per-workgroup table of the line; integer addition is associative, so any order gives the same bits.
+//   k_sorted_walk         : the plane walk + those four multiply-adds + two ds_add_u64 per channel lane and sample.  Lines too long for
+//                           the LDS are cut into BLOCKS by the sort keys (a workgroup's table holds one block's window).  The appearance
+//                           walk can take the basis gradient along (BAS: it holds plane value x line value, one bf16 MFMA per iteration
+//                           multiplies it with the sample's feature-slot gradients): no v dump, no d(basis) pass
+//   k_basis_reduce        : adds the waves' shares of d(basis)
+//   k_fused_line_final    : adds the workgroups' line tables and converts once
+// -DEGO_WALK_PROF (variants.h) adds clock counters to the walk and two debug entry points that read them.
 
 #include "ego_device.h"
 #include "ego_host.h"
+#include "ego_sorted_geom.h"
 #include <atomic>
 #include <stdlib.h>
 
 namespace {
-
-constexpr int SUB = 256;       // samples per line sub-block
-constexpr int RBITS = 9, RADIX = 1 << RBITS, RTILE = 4096;   // radix sort: digit bits, buckets, elements per workgroup tile (256 threads x 16)
-constexpr int CMAX = 48;       // channels of the widest field (appearance)
-constexpr int FUSED_MAX_WG = 320;   // workgroups of a fused launch (one per CU: 256 on MI355X; room for a larger part)
-
-// sort s: major / minor axis of its key (0 r, 1 theta, 2 phi), the plane whose cells it bins and the line whose ranges it bins
-__host__ __device__ constexpr int sort_major(int s) { return s == 0 ? 2 : s == 1 ? 0 : 1; }
-__host__ __device__ constexpr int sort_minor(int s) { return s == 0 ? 0 : s == 1 ? 1 : 2; }
-__host__ __device__ constexpr int sort_plane(int s) { return s == 0 ? 1 : s == 1 ? 0 : 2; }
-__host__ __device__ constexpr int sort_line(int s) { return s == 0 ? 0 : s == 1 ? 2 : 1; }
-
-struct SortGeom {
-  int32_t res[3];      // N_r, N_theta, N_phi
-  int64_t M;
-  uint32_t K[3];       // keys per sort = 2 (n_major + 1) (n_minor + 1); key K = "no gradient through this pair of axes"
-  uint32_t LC[3];      // line cells per sort = 2 (n_major + 1)
-  uint32_t nsub_max;   // upper bound of the line sub-blocks of one sort
-  int bits;            // key bits (covers max K)
-  // byte offsets into the workspace
-  int64_t perm[3], start[3], suboff[3], scratch, total;
-  int64_t stepsum[3], steps[3];   // the walk's step list (round 6): per cell the number of 16-sample steps before it; the steps themselves
-  int64_t costsum[3];             // per cell the COST of the steps before it (what the walk is dealt by)
-  // line blocks (round 6): sort s's key carries, above its two plane axes, the BLOCK of the sample's cell along the third axis (nb[s]
-  // blocks of bs[s] cells), so that a workgroup of the walk needs only one block's texels of the fused line in LDS
-  uint32_t nb[3], bs[3], kc[3];   // kc = cells of one (grid, block): (n_major + 1) (n_minor + 1)
-  int64_t step_cap[3];            // entries of steps[s]
-  // sort-phase view of the scratch region
-  int64_t keys_in[3], k1[3], v1[3], k2[3], hist[3], scanpart[3];
-  uint32_t nblocks;    // radix tiles (RTILE elements each)
-  int passes;          // ceil(bits / 9)
-  // scatter-phase view of the scratch region
-  int64_t cellbuf[3], linepart[3];
-  int64_t fx, fpart;   // fused form: the fixed-point scale block, the per-workgroup integer line tables
-  int64_t bpart;       // the walk's per-wave shares of d(basis): [FUSED_MAX_WG x WALK_NW_BAS][6][64][4] floats
-  int64_t fpart_stride;   // entries (8 bytes each) per workgroup table
-  bool dense_cells;    // cell buffer indexed by cell (K <= M) or by the cell's first sorted position (K > M: at most M cells hold samples)
-  uint32_t cell_slots[3];
-};
-
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-// ---- launch plan of the walk --------------------------------------------------------------------------------------------------------
-// Sort s serves plane sort_plane(s) AND the line of the axis that is not in its key (line index sort_plane(s)).  A workgroup keeps ONE
-// line block's window of that line's integer table for ONE grid in LDS: (bs + 1) x C x 8 bytes beside the waves' records; the sort keys
-// carry the block (line_blocks / make_geom: the headline grid [150, 172, 516] needs 1 / 1 / 3 blocks for theta / phi / r at C = 48 -
-// the r line alone would be 198 KB).  Only a line whose block window does not fit even in WALK_MAX_BLOCKS blocks keeps the two-pass form.
-constexpr int FUSED_LDS_LIMIT = 160 * 1024 - 1024;
-constexpr int WALK_MAX_BLOCKS = 16, WALK_MAX_SEG = 6 * WALK_MAX_BLOCKS;   // line blocks per sort; (sort, grid, block) segments of a launch
-constexpr int WALK_NW_APP = 12, WALK_NW_DENS = 16, WALK_NW_BAS = 8;   // waves per workgroup: 144+ VGPRs at 48 channels (three waves per SIMD), ~110 at 16
-struct FusedPlan {
-  int nw;
-  bool do_line[3];   // per sort
-  int entries_max;   // 8-byte table entries per workgroup (0: no fused line at all)
-  int lds_bytes;
-};
-__host__ __device__ constexpr int fused_line_axis(int s) { return 2 - (s == 0 ? 1 : s == 1 ? 0 : 2); }   // vm_line_ax(sort_plane(s))
-inline int walk_wave_bytes(int C) { return 12 * 64 * 4 + (C / 16) * 4 * 64 * 4; }   // sizeof(WalkLds<C / 16>)
-
-// the round-5 form (lockstep plane kernel + line kernels) stays reachable for A/B: EGO_SORTED_WALK=0; EGO_SORTED_LINES=separate keeps the
-// two-pass LINES under the walk's planes.  Both are read per call: a sort and the scatters that use it must see the same values.
-bool walk_wanted() {
-  const char* e = getenv("EGO_SORTED_WALK");
-  return !(e && e[0] == '0');
-}
-bool lines_separate() {
-  const char* e = getenv("EGO_SORTED_LINES");
-  return e && e[0] == 's';
-}
-
-// blocks of the third axis (n texels, n + 1 cells): the fewest whose window of bs + 1 texels x 48 channels x 8 bytes fits the LDS
-// beside the 48-channel walk's wave records (the 16-channel walk has more room)
-inline void line_blocks(int n, uint32_t* nb, uint32_t* bs) {
-  const int room = FUSED_LDS_LIMIT - WALK_NW_APP * walk_wave_bytes(CMAX) - 1024;
-  uint32_t k = 1;
-  while (k < WALK_MAX_BLOCKS && ((int64_t)((n + 1 + k - 1) / k) + 1) * CMAX * 8 > room) ++k;
-  *nb = k; *bs = (uint32_t)(n + 1 + k - 1) / k;
-}
-
-SortGeom make_geom(const int32_t res[3], int64_t M) {
-  SortGeom G{};
-  G.M = M;
-  uint32_t kmax = 0, lcmax = 0;
-  for (int a = 0; a < 3; ++a) G.res[a] = res[a];
-  bool blocked = walk_wanted() && !lines_separate();
-  if (blocked) {   // all or nothing: a line that does not fit even in WALK_MAX_BLOCKS blocks needs the two-pass kernels, which read the plain key layout
-    const int room = FUSED_LDS_LIMIT - WALK_NW_APP * walk_wave_bytes(CMAX) - 1024;
-    for (int s = 0; s < 3; ++s) {
-      uint32_t nb_, bs_;
-      line_blocks(res[fused_line_axis(s)], &nb_, &bs_);
-      if ((int64_t)(bs_ + 1) * CMAX * 8 > room) blocked = false;
-    }
-  }
-  for (int s = 0; s < 3; ++s) {
-    const uint32_t nmaj = (uint32_t)res[sort_major(s)] + 1, nmin = (uint32_t)res[sort_minor(s)] + 1;
-    G.nb[s] = 1; G.bs[s] = (uint32_t)res[fused_line_axis(s)] + 1;
-    if (blocked) line_blocks(res[fused_line_axis(s)], &G.nb[s], &G.bs[s]);
-    G.kc[s] = nmaj * nmin;
-    G.K[s] = 2u * G.nb[s] * nmaj * nmin;
-    G.LC[s] = 2u * nmaj;
-    kmax = G.K[s] > kmax ? G.K[s] : kmax;
-    lcmax = G.LC[s] > lcmax ? G.LC[s] : lcmax;
-  }
-  G.bits = 1;
-  while ((1ull << G.bits) <= kmax) ++G.bits;      // keys 0 .. K inclusive
-  G.nsub_max = (uint32_t)(M / SUB) + lcmax + 1;
-  int64_t o = 0;
-  for (int s = 0; s < 3; ++s) { G.perm[s] = o; o = align256(o + 4 * M); }
-  for (int s = 0; s < 3; ++s) { G.start[s] = o; o = align256(o + 4 * ((int64_t)G.K[s] + 2)); }
-  for (int s = 0; s < 3; ++s) { G.suboff[s] = o; o = align256(o + 4 * ((int64_t)G.LC[s] + 1)); }
-  for (int s = 0; s < 3; ++s) { G.stepsum[s] = o; o = align256(o + 4 * ((int64_t)G.K[s] + 2)); }
-  for (int s = 0; s < 3; ++s) { G.costsum[s] = o; o = align256(o + 4 * ((int64_t)G.K[s] + 2)); }
-  for (int s = 0; s < 3; ++s) {
-    // a cell of n samples takes ceil(n / 16) steps: at most M / 16 + one per cell that holds samples
-    G.step_cap[s] = M / 16 + (M < (int64_t)G.K[s] ? M : (int64_t)G.K[s]) + 1;
-    G.steps[s] = o; o = align256(o + 16 * G.step_cap[s]);
-  }
-  G.scratch = o;
-  // sort phase
-  int64_t a = o;
-  G.passes = (G.bits + RBITS - 1) / RBITS;
-  G.nblocks = (uint32_t)((M + RTILE - 1) / RTILE);
-  for (int s = 0; s < 3; ++s) { G.keys_in[s] = a; a = align256(a + 4 * M); }
-  for (int s = 0; s < 3; ++s) { G.k1[s] = a; a = align256(a + 4 * M); }
-  for (int s = 0; s < 3; ++s) { G.v1[s] = a; a = align256(a + 4 * M); }
-  for (int s = 0; s < 3; ++s) { G.k2[s] = a; a = align256(a + 4 * M); }
-  for (int s = 0; s < 3; ++s) { G.hist[s] = a; a = align256(a + 4 * ((int64_t)RADIX * G.nblocks + RADIX)); }   // + the digit totals
-  for (int s = 0; s < 3; ++s) { G.scanpart[s] = a; a = align256(a + 4 * 2 * ((int64_t)G.K[s] / 4096 + 2)); }   // k_step_scan's per-workgroup totals (steps, cost)
-  // scatter phase
-  int64_t b = o;
-  // cell buffer: only cells that hold samples are ever written or read - at most min(K, M) of them (K x 4 x 48 floats was
-  // 1.2 GB on the [300, 346, 1036] grid whatever the batch)
-  G.dense_cells = (int64_t)kmax <= M;
-  for (int s = 0; s < 3; ++s) {
-    G.cell_slots[s] = G.dense_cells ? G.K[s] : (uint32_t)M;   // sparse: slot = the cell's first sorted position (< M, distinct per non-empty cell)
-    G.cellbuf[s] = b; b = align256(b + 4 * (int64_t)G.cell_slots[s] * 4 * CMAX);
-  }
-  for (int s = 0; s < 3; ++s) { G.linepart[s] = b; b = align256(b + 4 * (int64_t)G.nsub_max * 2 * CMAX); }
-  // fused form (shares the line-partial region's place in time, not its bytes: both forms are sized so that either can run)
-  G.fx = b; b = align256(b + 256 + 4 * 7 * 128 + 4 * (WALK_MAX_SEG + 1));   // FxScale + k_fx_absmax's per-workgroup maxima + the walk's deal
-  {
-    // a workgroup's line table: one block's window of the third axis (bs + 1 texels) x the widest field's channels
-    int64_t emax = 0;
-    for (int s = 0; s < 3; ++s) {
-      const int64_t e = (int64_t)(G.bs[s] + 1) * CMAX;
-      const int room = FUSED_LDS_LIMIT - WALK_NW_APP * walk_wave_bytes(CMAX) - 1024;
-      if (e * 8 <= room && e > emax) emax = e;
-    }
-    G.fpart_stride = emax;
-    G.fpart = b; b = align256(b + 8 * G.fpart_stride * FUSED_MAX_WG);
-  }
-  G.bpart = b; b = align256(b + (int64_t)FUSED_MAX_WG * WALK_NW_BAS * 6 * 256 * 4);
-  G.total = a > b ? a : b;
-  return G;
-}
-
-// which lines the walk of a C-channel field takes along: a sort's line rides along when one block's window of it fits the LDS
-inline FusedPlan fused_plan(const SortGeom& G, int C) {
-  FusedPlan P{};
-  P.nw = C > 16 ? WALK_NW_APP : WALK_NW_DENS;
-  const int fixed = P.nw * walk_wave_bytes(C) + 1024;   // + the deal table
-  const int room = FUSED_LDS_LIMIT - fixed;
-  for (int s = 0; s < 3; ++s) {
-    const int64_t bytes = (int64_t)(G.bs[s] + 1) * C * 8;
-    P.do_line[s] = !lines_separate() && bytes <= room;
-    if (P.do_line[s] && (int)(bytes / 8) > P.entries_max) P.entries_max = (int)(bytes / 8);
-  }
-  P.lds_bytes = fixed + P.entries_max * 8;
-  return P;
-}
-
-// the unclamped west tap index + 1 (0 .. n) with lin_setup's arithmetic, or -1 when both taps are out of range
-__device__ __forceinline__ int cell_of(float xhat, int n) {
-  const float ix = __fmul_rn(__fadd_rn(xhat, 1.0f), 0.5f * (float)(n - 1));
-  const float flc = fminf(fmaxf(floorf(ix), -2.0f), (float)n);
-  const int i0 = (int)flc;
-  return (i0 < -1 || i0 > n - 1) ? -1 : i0 + 1;
-}
-
-struct KeyArgs {
-  uint32_t K[3], nb[3], bs[3];
-};
-// key of sort s = ((grid * nb + block of the third axis' cell) * (n_major + 1) + major cell) * (n_minor + 1) + minor cell; a sample
-// without a gradient through the third axis (both taps out of range: its line weights are 0) goes to block 0
-__global__ void k_sort_keys(const float* __restrict__ coords, int64_t M, int nr, int nth, int nph, KeyArgs A,
-                            uint32_t* __restrict__ k0, uint32_t* __restrict__ k1, uint32_t* __restrict__ k2) {
-  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= M) return;
-  const f32x4 cc = ((const f32x4*)coords)[m];
-  const uint32_t g = cc.w != 0.f ? 1u : 0u;
-  const int cr = cell_of(cc.x, nr), cth = cell_of(cc.y, nth), cph = cell_of(cc.z, nph);
-  const uint32_t b0 = cth < 0 ? 0u : (uint32_t)cth / A.bs[0], b1 = cph < 0 ? 0u : (uint32_t)cph / A.bs[1], b2 = cr < 0 ? 0u : (uint32_t)cr / A.bs[2];
-  k0[m] = (cph < 0 || cr < 0) ? A.K[0] : ((g * A.nb[0] + b0) * (uint32_t)(nph + 1) + (uint32_t)cph) * (uint32_t)(nr + 1) + (uint32_t)cr;
-  k1[m] = (cr < 0 || cth < 0) ? A.K[1] : ((g * A.nb[1] + b1) * (uint32_t)(nr + 1) + (uint32_t)cr) * (uint32_t)(nth + 1) + (uint32_t)cth;
-  k2[m] = (cth < 0 || cph < 0) ? A.K[2] : ((g * A.nb[2] + b2) * (uint32_t)(nth + 1) + (uint32_t)cth) * (uint32_t)(nph + 1) + (uint32_t)cph;
-}
-
-// ---- stable LSD radix sort of (key, sample index), 9 bits per pass, the three sorts side by side (blockIdx.y) -----------------------
-// Plain kernels (no look-back between workgroups, no library state): the whole sort is graph-capturable and bit-reproducible.  A pass =
-//   k_radix_hist    : per 4096-element tile, the digit histogram (LDS integer atomics) -> hist[digit][tile]
-//   k_radix_scan    : per digit, exclusive scan of its per-tile counts + the digit's total (the digit bases are a 512-value scan that every
-//                     scatter workgroup does for itself): where each tile's run of each digit starts
-//   k_radix_scatter : the tile again: every element's rank among the EARLIER elements of its digit (wave w owns elements [1024 w, 1024 w +
-//                     1024) of the tile and walks them 64 at a time in order; inside an iteration the equal-digit lanes are found with 9
-//                     ballots) -> stable position -> (key, value) stored
-struct RadixArgs {
-  const uint32_t* kin[3];
-  const uint32_t* vin[3];    // nullptr: the value is the element's index (first pass)
-  uint32_t* kout[3];
-  uint32_t* vout[3];
-  uint32_t* hist[3];
-  uint32_t* dsum[3];         // [RADIX] per-digit totals of the pass
-  int64_t M;
-  uint32_t nblocks;
-  int shift;
-};
-
-__global__ __launch_bounds__(256) void k_radix_hist(RadixArgs A) {
-  __shared__ uint32_t h[RADIX];
-  const int s = blockIdx.y, t = threadIdx.x;
-  for (int i = t; i < RADIX; i += 256) h[i] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * RTILE;
-#pragma unroll 4
-  for (int j = 0; j < RTILE / 256; ++j) {
-    const int64_t idx = base + j * 256 + t;
-    if (idx < A.M) atomicAdd(&h[(A.kin[s][idx] >> A.shift) & (RADIX - 1)], 1u);
-  }
-  __syncthreads();
-  for (int i = t; i < RADIX; i += 256) A.hist[s][(int64_t)i * A.nblocks + blockIdx.x] = h[i];
-}
-
-// exclusive scan of a workgroup's 256 values (one per thread); returns the thread's prefix, *total = the sum
-__device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* wsum /* [4] shared */, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += u;
-  }
-  __syncthreads();   // wsum may still be read from a previous call
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  for (int w = 0; w < wv; ++w) before += wsum[w];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return before + inc - v;
-}
-
-// one workgroup per (digit, sort): in-place exclusive scan of the digit's per-tile counts; the digit's total goes to dsum[digit]
-// (k_radix_scatter turns the 512 totals into digit bases itself)
-__global__ __launch_bounds__(256) void k_radix_scan(RadixArgs A) {
-  __shared__ uint32_t wsum[4];
-  uint32_t* h = A.hist[blockIdx.y] + (int64_t)blockIdx.x * A.nblocks;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < A.nblocks; base += 256) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < A.nblocks ? h[i] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_excl_scan256(v, wsum, &total);
-    if (i < A.nblocks) h[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) A.dsum[blockIdx.y][blockIdx.x] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_radix_scatter(RadixArgs A) {
-  __shared__ uint32_t wcnt[4][RADIX];
-  __shared__ uint32_t lbase[RADIX], gbase[RADIX];   // where a digit's run starts inside the sorted tile / in the output
-  __shared__ uint32_t skey[RTILE], sval[RTILE];     // the tile in sorted order: the output is then written in runs, not element by element
-  __shared__ uint32_t wsum[4];
-  const int s = blockIdx.y, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  for (int i = t; i < 4 * RADIX; i += 256) (&wcnt[0][0])[i] = 0;
-  __syncthreads();
-  const int64_t tbase = (int64_t)blockIdx.x * RTILE, wbase = tbase + w * (RTILE / 4);
-  uint32_t key[RTILE / 256];
-#pragma unroll
-  for (int it = 0; it < RTILE / 256; ++it) {
-    const int64_t idx = wbase + it * 64 + lane;
-    key[it] = idx < A.M ? A.kin[s][idx] : 0u;
-    if (idx < A.M) atomicAdd(&wcnt[w][(key[it] >> A.shift) & (RADIX - 1)], 1u);
-  }
-  __syncthreads();
-  {   // two digits per thread (2 t, 2 t + 1): the tile's digit starts, and the digit bases from the 512 digit totals of the pass
-    const uint32_t c0 = wcnt[0][2 * t] + wcnt[1][2 * t] + wcnt[2][2 * t] + wcnt[3][2 * t];
-    const uint32_t c1 = wcnt[0][2 * t + 1] + wcnt[1][2 * t + 1] + wcnt[2][2 * t + 1] + wcnt[3][2 * t + 1];
-    uint32_t total;
-    const uint32_t ex = block_excl_scan256(c0 + c1, wsum, &total);
-    lbase[2 * t] = ex; lbase[2 * t + 1] = ex + c0;
-    const uint32_t d0 = A.dsum[s][2 * t], d1 = A.dsum[s][2 * t + 1];
-    const uint32_t exg = block_excl_scan256(d0 + d1, wsum, &total);
-    gbase[2 * t] = exg + A.hist[s][(int64_t)(2 * t) * A.nblocks + blockIdx.x];
-    gbase[2 * t + 1] = exg + d0 + A.hist[s][(int64_t)(2 * t + 1) * A.nblocks + blockIdx.x];
-  }
-  __syncthreads();
-  for (int d = t; d < RADIX; d += 256) {   // counts -> where wave w's run of digit d starts in the sorted tile
-    uint32_t run = lbase[d];
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) { const uint32_t c = wcnt[ww][d]; wcnt[ww][d] = run; run += c; }
-  }
-  __syncthreads();
-  const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-#pragma unroll
-  for (int it = 0; it < RTILE / 256; ++it) {
-    const int64_t idx = wbase + it * 64 + lane;
-    const bool ok = idx < A.M;
-    const uint32_t d = (key[it] >> A.shift) & (RADIX - 1);
-    unsigned long long m = __ballot(ok);
-#pragma unroll
-    for (int b = 0; b < RBITS; ++b) {
-      const unsigned long long bal = __ballot(ok && ((d >> b) & 1u));
-      m &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const uint32_t rank = (uint32_t)__popcll(m & lt);
-    uint32_t off = 0;
-    if (ok) off = wcnt[w][d];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (ok && rank == 0) wcnt[w][d] = off + (uint32_t)__popcll(m);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (ok) {
-      skey[off + rank] = key[it];
-      sval[off + rank] = A.vin[s] ? A.vin[s][idx] : (uint32_t)idx;
-    }
-  }
-  __syncthreads();
-  const int n_tile = (int)(A.M - tbase < RTILE ? A.M - tbase : RTILE);
-  for (int i = t; i < n_tile; i += 256) {
-    const uint32_t k = skey[i], d = (k >> A.shift) & (RADIX - 1);
-    const uint32_t pos = gbase[d] + ((uint32_t)i - lbase[d]);
-    A.kout[s][pos] = k;
-    A.vout[s][pos] = sval[i];
-  }
-}
-
-// start[k] = first sorted position whose key is >= k, k = 0 .. K + 1 (start[K] = the number of samples with a gradient)
-struct StartArgs {
-  const uint32_t* sorted[3];
-  uint32_t* start[3];
-  uint32_t* suboff[3];
-  uint32_t* stepsum[3];
-  uint32_t* costsum[3];
-  uint4* steps[3];
-  uint32_t* scanpart[3];   // k_step_scan's per-workgroup totals
-  uint32_t K[3], LC[3], nmin1[3];
-  int64_t M;
-};
-
-__global__ void k_cell_starts(StartArgs A) {
-  const uint32_t* __restrict__ sorted = A.sorted[blockIdx.y];
-  uint32_t* __restrict__ start = A.start[blockIdx.y];
-  const uint32_t K = A.K[blockIdx.y];
-  const int64_t M = A.M;
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > K + 1) return;
-  int64_t lo = 0, hi = M;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (sorted[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  start[k] = (uint32_t)lo;
-}
-
-// suboff[lc] = number of 256-sample sub-blocks of the line cells before lc (exclusive scan; suboff[LC] = total); one workgroup
-__global__ __launch_bounds__(1024) void k_line_suboff(StartArgs A) {
-  const uint32_t* __restrict__ start = A.start[blockIdx.y];
-  uint32_t* __restrict__ suboff = A.suboff[blockIdx.y];
-  const uint32_t LC = A.LC[blockIdx.y], nmin1 = A.nmin1[blockIdx.y];
-  __shared__ uint32_t wsum[16];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < LC; base += 1024) {
-    const uint32_t lc = base + t;
-    uint32_t n = 0;
-    if (lc < LC) n = (start[(lc + 1) * nmin1] - start[lc * nmin1] + SUB - 1) / SUB;
-    uint32_t inc = n;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t v = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += v;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wv; ++w) before += wsum[w];
-    uint32_t all = 0;
-    for (int w = 0; w < 16; ++w) all += wsum[w];
-    if (lc < LC) suboff[lc] = carry + before + inc - n;
-    carry += all;
-    __syncthreads();
-  }
-  if (t == 0) suboff[LC] = carry;
-}
-
-// ---- the walk's step list -------------------------------------------------------------------------------------------------------------
-// A STEP = up to 16 consecutive sorted samples of one cell (what a 16-lane group of k_sorted_walk handles at a time).
-// stepsum[k] = number of steps of the cells before k (k = 0 .. K; the cells of grid 0 come first), one workgroup per sort;
-// steps[j] = {first sorted position, cell, samples | first step of its cell << 8 | last << 9, 0}.  With the list the walk is dealt in
-// EQUAL numbers of steps per group, whatever the cells' sizes - a first version that dealt cells in chunks had its slowest wave at 3.5 x
-// the mean (tools/sorted_probe.py PROBE_PROF on a -DEGO_WALK_PROF build).
-// cost of a cell's steps: a step = its fixed part (prefetches, set-up, record: 0.6 of an iteration's time, measured with
-// -DEGO_WALK_PROF: 3.2 k against 5.3 k clocks in the 48-channel walk) + ceil(samples / 4) stage-2 iterations (U = 4 samples per group)
-__device__ __forceinline__ uint32_t cell_cost(uint32_t n) {   // in fifths of an iteration: a step's fixed part = 3, an iteration = 5
-  const uint32_t full = n / 16u, r = n % 16u;
-  return full * 23u + (r ? 3u + 5u * ((r + 3u) / 4u) : 0u);
-}
-
-// stepsum / costsum = exclusive prefix sums over the sort's cells, in three launches: per 4096-cell workgroup the local prefixes + its
-// total (PHASE 0), the totals' scan by one workgroup (1), the offsets added (2).  blockIdx.y = 0 steps, 1 cost; z = sort.  (A
-// single-workgroup loop took 0.1 ms.)
-template <int PHASE>
-__global__ __launch_bounds__(1024) void k_step_scan(StartArgs A) {
-  const int s = blockIdx.z;
-  const uint32_t* __restrict__ start = A.start[s];
-  const bool cost = blockIdx.y == 1;
-  uint32_t* __restrict__ out = cost ? A.costsum[s] : A.stepsum[s];
-  uint32_t* __restrict__ part = A.scanpart[s] + (cost ? (A.K[s] / 4096u + 2u) : 0u);
-  const uint32_t K = A.K[s], nblk = (K + 4095u) / 4096u;
-  __shared__ uint32_t wsum[16];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (PHASE == 1) {   // one workgroup: exclusive scan of the workgroup totals, the grand total behind them
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nblk; base += 1024) {
-      const uint32_t i = base + (uint32_t)t;
-      const uint32_t v = i < nblk ? part[i] : 0u;
-      uint32_t inc = v;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(inc, d, 64); if (lane >= d) inc += u; }
-      if (lane == 63) wsum[wv] = inc;
-      __syncthreads();
-      uint32_t before = 0, all = 0;
-      for (int w = 0; w < 16; ++w) { if (w < wv) before += wsum[w]; all += wsum[w]; }
-      if (i < nblk) part[i] = carry + before + inc - v;
-      carry += all;
-      __syncthreads();
-    }
-    if (t == 0) { out[K] = carry; out[K + 1] = carry; }
-    return;
-  }
-  if (blockIdx.x >= nblk) return;
-  const uint32_t k0 = blockIdx.x * 4096u + 4u * (uint32_t)t;
-  if (PHASE == 2) {
-    const uint32_t off = part[blockIdx.x];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (k0 + i < K) out[k0 + i] += off;
-    return;
-  }
-  uint32_t n[4], own = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t k = k0 + i;
-    const uint32_t ns = k < K ? start[k + 1] - start[k] : 0u;
-    n[i] = cost ? cell_cost(ns) : (ns + 15u) / 16u;
-    own += n[i];
-  }
-  uint32_t inc = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(inc, d, 64); if (lane >= d) inc += u; }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (int w = 0; w < 16; ++w) { if (w < wv) before += wsum[w]; all += wsum[w]; }
-  uint32_t run = before + inc - own;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (k0 + i < K) out[k0 + i] = run;
-    run += n[i];
-  }
-  if (t == 0) part[blockIdx.x] = all;
-}
-
-__global__ void k_step_fill(StartArgs A) {
-  const int s = blockIdx.y;
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= A.K[s]) return;
-  const uint32_t c = k;
-  const uint32_t a = A.start[s][c], n = A.start[s][c + 1] - a;
-  if (!n) return;
-  uint4* out = A.steps[s] + A.stepsum[s][k];
-  const uint32_t nb = (n + 15u) / 16u;
-  for (uint32_t b = 0; b < nb; ++b) {
-    const uint32_t cnt = min(16u, n - 16u * b);
-    out[b] = uint4{a + 16u * b, c, cnt | (b == 0 ? 256u : 0u) | (b + 1 == nb ? 512u : 0u), 0u};
-  }
-}
 
 struct GradTables {
   float* plane[2][3];
@@ -1659,25 +1167,33 @@ int fill_args(const ego_vm_field& f, const ego_vm_grad* grad, const float* coord
   return EGO_OK;
 }
 
-template <int C, bool DENS>
-int launch_sorted(const SortedArgs& a, const SortGeom& G, hipStream_t st) {
-  uint32_t kmax = 0;
+// workgroups (256 threads) of the _final launches: k_sorted_plane_final has one thread per (texel, 4 channels), k_sorted_line_final and
+// k_fused_line_final one per (texel, channel); blockIdx.y selects the sort, so one launch must cover the largest plane and the largest
+// line.  Both maxima run over all three axes - which sort serves which plane or line does not enter.
+struct FinalGrids {
+  unsigned plane, line;
+};
+inline FinalGrids final_grids(const SortGeom& G, int C) {
   int64_t texmax = 0, linemax = 0;
-  for (int s = 0; s < 3; ++s) {
-    kmax = G.K[s] > kmax ? G.K[s] : kmax;
-    const int I = sort_plane(s);
-    const int64_t tex = (int64_t)2 * G.res[I == 2 ? 1 : 0] * G.res[I == 0 ? 1 : 2] * (C / 4);   // plane I: x axis, y axis (vm_plane_x / _y)
+  for (int i = 0; i < 3; ++i) {
+    const int64_t tex = (int64_t)2 * G.res[i == 2 ? 1 : 0] * G.res[i == 0 ? 1 : 2] * (C / 4);   // plane i: x axis, y axis (vm_plane_x / _y)
     texmax = tex > texmax ? tex : texmax;
-    const int64_t ln = (int64_t)2 * G.res[sort_major(s)] * C;
+    const int64_t ln = (int64_t)2 * G.res[i] * C;
     linemax = ln > linemax ? ln : linemax;
   }
-  k_sorted_plane<C, DENS><<<dim3((kmax + 15) / 16, 3), 256, 0, st>>>(a);   // 4 cells per wave, 4 waves per workgroup
+  return FinalGrids{(unsigned)((texmax + 255) / 256), (unsigned)((linemax + 255) / 256)};
+}
+
+template <int C, bool DENS>
+int launch_sorted(const SortedArgs& a, const SortGeom& G, hipStream_t st) {
+  const FinalGrids FG = final_grids(G, C);
+  k_sorted_plane<C, DENS><<<dim3((G.kmax + 15) / 16, 3), 256, 0, st>>>(a);   // 4 cells per wave, 4 waves per workgroup
   if (int e = ego_launch_status("k_sorted_plane")) return e;
   k_sorted_line<C, DENS><<<dim3((G.nsub_max + 3) / 4, 3), 256, 0, st>>>(a);
   if (int e = ego_launch_status("k_sorted_line")) return e;
-  k_sorted_plane_final<C><<<dim3((unsigned)((texmax + 255) / 256), 3), 256, 0, st>>>(a);
+  k_sorted_plane_final<C><<<dim3(FG.plane, 3), 256, 0, st>>>(a);
   if (int e = ego_launch_status("k_sorted_plane_final")) return e;
-  k_sorted_line_final<C><<<dim3((unsigned)((linemax + 255) / 256), 3), 256, 0, st>>>(a);
+  k_sorted_line_final<C><<<dim3(FG.line, 3), 256, 0, st>>>(a);
   return ego_launch_status("k_sorted_line_final");
 }
 
@@ -1770,22 +1286,15 @@ int launch_walk(SortedArgs a, const SortGeom& G, char* base, int64_t M, const fl
     k_sorted_line<C, DENS><<<dim3((G.nsub_max + 3) / 4, 3), 256, 0, st>>>(a);
     if (int e = ego_launch_status("k_sorted_line")) return e;
   }
-  int64_t texmax = 0, linemax = 0;
-  for (int s = 0; s < 3; ++s) {
-    const int I = sort_plane(s);
-    const int64_t tex = (int64_t)2 * G.res[I == 2 ? 1 : 0] * G.res[I == 0 ? 1 : 2] * (C / 4);
-    texmax = tex > texmax ? tex : texmax;
-    const int64_t ln = (int64_t)2 * G.res[s] * C;
-    linemax = ln > linemax ? ln : linemax;
-  }
-  k_sorted_plane_final<C><<<dim3((unsigned)((texmax + 255) / 256), 3), 256, 0, st>>>(a);
+  const FinalGrids FG = final_grids(G, C);
+  k_sorted_plane_final<C><<<dim3(FG.plane, 3), 256, 0, st>>>(a);
   if (int e = ego_launch_status("k_sorted_plane_final")) return e;
   if (mask) {
-    k_sorted_line_final<C><<<dim3((unsigned)((linemax + 255) / 256), 3), 256, 0, st>>>(a);
+    k_sorted_line_final<C><<<dim3(FG.line, 3), 256, 0, st>>>(a);
     if (int e = ego_launch_status("k_sorted_line_final")) return e;
   }
   if (any_line) {
-    k_fused_line_final<C><<<dim3((unsigned)((linemax + 255) / 256), 3), 256, 0, st>>>(F);
+    k_fused_line_final<C><<<dim3(FG.line, 3), 256, 0, st>>>(F);
     if (int e = ego_launch_status("k_fused_line_final")) return e;
   }
   return EGO_OK;
@@ -1805,14 +1314,6 @@ int zero_tables(const ego_vm_field& f, const ego_vm_grad* grad, int C, hipStream
   return EGO_OK;
 }
 
-int check_sizes(const ego_scene* sc, int64_t N, int32_t S, const char* who) {
-  if (!sc) return ego_fail(EGO_E_BADARG, "%s: null scene", who);
-  if (!(N >= 0 && S >= 1 && N * (int64_t)S < (1ll << 31))) return ego_fail(EGO_E_BADARG, "%s: bad size (N * S must be below 2^31)", who);
-  for (int a = 0; a < 3; ++a)
-    if (sc->density.res[a] < 2 || sc->density.res[a] > 4096) return ego_fail(EGO_E_BADARG, "%s: table resolution out of range [2, 4096]", who);
-  return EGO_OK;
-}
-
 }  // namespace
 
 #ifdef EGO_WALK_PROF
@@ -1824,87 +1325,10 @@ extern "C" int ego_debug_walk_prof(unsigned long long* out16) {   // experiment 
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_walk_span), sp, 32) != hipSuccess) return -1;
   return hipMemcpyToSymbol(HIP_SYMBOL(g_walk_prof), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
-#endif
-
-#ifdef EGO_WALK_PROF
 extern "C" int ego_debug_walk_waves(uint32_t* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_walk_wave), 4096 * 16) == hipSuccess ? 0 : -1; }
 #endif
 
 extern "C" {
-
-int64_t ego_scatter_sorted_workspace_bytes(const ego_scene* sc, int64_t N, int32_t S) {
-  if (check_sizes(sc, N, S, "scatter_sorted_workspace_bytes")) return -1;
-  return make_geom(sc->density.res, N * (int64_t)S > 0 ? N * (int64_t)S : 1).total;
-}
-
-int ego_scatter_sort(const ego_scene* sc, const float* coords, int64_t N, int32_t S, void* workspace, int64_t workspace_bytes, void* stream) {
-  EGO_TRACE("ego_scatter_sort");
-  if (int e = check_sizes(sc, N, S, "scatter_sort")) return e;
-  if (N == 0) return EGO_OK;
-  EGO_REQUIRE(coords && workspace && ((uintptr_t)workspace & 255) == 0, "scatter_sort: null argument or workspace not 256-byte aligned");
-  for (int a = 0; a < 3; ++a)
-    EGO_REQUIRE(sc->app.res[a] == sc->density.res[a], "scatter_sort: the density and appearance fields must share one resolution (they do: EgoNeRF.py:102-122)");
-  const int64_t M = N * (int64_t)S;
-  const SortGeom G = make_geom(sc->density.res, M);
-  if (workspace_bytes < G.total) return ego_fail(EGO_E_BADARG, "scatter_sort: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)G.total);
-  hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  uint32_t* kin[3] = {(uint32_t*)(base + G.keys_in[0]), (uint32_t*)(base + G.keys_in[1]), (uint32_t*)(base + G.keys_in[2])};
-  KeyArgs ka{};
-  for (int s = 0; s < 3; ++s) { ka.K[s] = G.K[s]; ka.nb[s] = G.nb[s]; ka.bs[s] = G.bs[s]; }
-  k_sort_keys<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(coords, M, G.res[0], G.res[1], G.res[2], ka, kin[0], kin[1], kin[2]);
-  if (int e = ego_launch_status("k_sort_keys")) return e;
-  // LSD passes ping-pong between (k1, v1) and (k2, perm); the last pass lands in (k2, perm)
-  for (int p = 0; p < G.passes; ++p) {
-    RadixArgs r{};
-    const bool to2 = ((G.passes - 1 - p) & 1) == 0;
-    for (int s = 0; s < 3; ++s) {
-      r.kin[s] = p == 0 ? kin[s] : (const uint32_t*)(base + (to2 ? G.k1[s] : G.k2[s]));
-      r.vin[s] = p == 0 ? nullptr : (const uint32_t*)(base + (to2 ? G.v1[s] : G.perm[s]));
-      r.kout[s] = (uint32_t*)(base + (to2 ? G.k2[s] : G.k1[s]));
-      r.vout[s] = (uint32_t*)(base + (to2 ? G.perm[s] : G.v1[s]));
-      r.hist[s] = (uint32_t*)(base + G.hist[s]);
-      r.dsum[s] = r.hist[s] + (int64_t)RADIX * G.nblocks;
-    }
-    r.M = M; r.nblocks = G.nblocks; r.shift = p * RBITS;
-    k_radix_hist<<<dim3(G.nblocks, 3), 256, 0, st>>>(r);
-    if (int e = ego_launch_status("k_radix_hist")) return e;
-    k_radix_scan<<<dim3(RADIX, 3), 256, 0, st>>>(r);
-    if (int e = ego_launch_status("k_radix_scan")) return e;
-    k_radix_scatter<<<dim3(G.nblocks, 3), 256, 0, st>>>(r);
-    if (int e = ego_launch_status("k_radix_scatter")) return e;
-  }
-  StartArgs sa{};
-  uint32_t kmax = 0;
-  for (int s = 0; s < 3; ++s) {
-    sa.sorted[s] = (const uint32_t*)(base + G.k2[s]);
-    sa.start[s] = (uint32_t*)(base + G.start[s]);
-    sa.suboff[s] = (uint32_t*)(base + G.suboff[s]);
-    sa.stepsum[s] = (uint32_t*)(base + G.stepsum[s]);
-    sa.costsum[s] = (uint32_t*)(base + G.costsum[s]);
-    sa.steps[s] = (uint4*)(base + G.steps[s]);
-    sa.K[s] = G.K[s]; sa.LC[s] = G.LC[s]; sa.nmin1[s] = (uint32_t)G.res[sort_minor(s)] + 1;
-    kmax = G.K[s] > kmax ? G.K[s] : kmax;
-  }
-  sa.M = M;
-  k_cell_starts<<<dim3((kmax + 2 + 255) / 256, 3), 256, 0, st>>>(sa);
-  if (int e = ego_launch_status("k_cell_starts")) return e;
-  k_line_suboff<<<dim3(1, 3), 1024, 0, st>>>(sa);
-  if (int e = ego_launch_status("k_line_suboff")) return e;
-  for (int s = 0; s < 3; ++s) sa.scanpart[s] = (uint32_t*)(base + G.scanpart[s]);
-  {
-    const unsigned nblk = (kmax + 4095) / 4096;
-    k_step_scan<0><<<dim3(nblk, 2, 3), 1024, 0, st>>>(sa);
-    if (int e = ego_launch_status("k_step_scan<0>")) return e;
-    k_step_scan<1><<<dim3(1, 2, 3), 1024, 0, st>>>(sa);
-    if (int e = ego_launch_status("k_step_scan<1>")) return e;
-    k_step_scan<2><<<dim3(nblk, 2, 3), 1024, 0, st>>>(sa);
-    if (int e = ego_launch_status("k_step_scan<2>")) return e;
-  }
-  k_step_fill<<<dim3((kmax + 255) / 256, 3), 256, 0, st>>>(sa);
-  if (int e = ego_launch_status("k_step_fill")) return e;
-  return EGO_OK;
-}
 
 int ego_scatter_density_sorted(const ego_scene* sc, const ego_vm_grad* gdensity, const float* coords, const float* dfeat, int64_t N, int32_t S,
                                void* workspace, int64_t workspace_bytes, void* stream) {

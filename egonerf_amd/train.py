@@ -153,7 +153,7 @@ def _generic_head_sorted_app(model, sort_ws, M: int) -> bool:
     """A head of another shape over 48-component appearance tables: ego_shade_backward_generic writes the blocked dv and the sorted walk
     scatters it (the step's sort exists whenever the density field has its tuned shape; sort_ws: its workspace, or True for "it will").
     Also what lets the tuned head's walk take dfe.  EGO_SORTED_WALK is read here and nowhere else, once per step when the step is planned
-    (not at import: the library reads it per call too, csrc/ego_scatter_sorted.hip::walk_wanted, and the two must agree)."""
+    (not at import: the library reads it per call too, csrc/ego_sorted_geom.h::walk_wanted, and the two must agree)."""
     return sort_ws is not None and _env_on("EGO_SORTED_WALK", "1") and model.app_n_comp[0] == 48 and (M + 31) // 32 * 32 * 144 < 2 ** 30
 
 
@@ -252,7 +252,7 @@ def _march(plan: StepPlan, sc, model, rays, opts) -> dict:
 
 def _sort(plan: StepPlan, sc, coords) -> Optional[torch.Tensor]:
     """The step's samples binned by texel cell once, from the coordinates the march just wrote - on the side stream, next to the dumping
-    shade forward - so that the backward's two scatters write every gradient texel once, in a fixed order (csrc/ego_scatter_sorted.hip)."""
+    shade forward - so that the backward's two scatters write every gradient texel once, in a fixed order (csrc/ego_scatter_sort.hip)."""
     if not plan.sorts:
         return None
     lib, N, S = _lib.load(), plan.N, plan.S

@@ -499,7 +499,7 @@ int ego_scatter_density(const ego_scene* sc, const ego_vm_grad* gdensity, const 
 int ego_scatter_app(const ego_scene* sc, const ego_vm_grad* gapp, const float* coords, const float* dv, int64_t N, int32_t S,
                     void* stream);
 
-/* ---- the same table gradients without atomics: bit-reproducible (csrc/ego_scatter_sorted.hip) ----
+/* ---- the same table gradients without atomics: bit-reproducible (the sort: csrc/ego_scatter_sort.hip; the scatters: csrc/ego_scatter_sorted.hip) ----
  * ego_scatter_density / ego_scatter_app add with float atomics: their sums depend on the order the hardware serves them.  The three
  * entry points below bin the step's samples by texel cell once (three stable radix sorts of the forward's coordinates; both fields share
  * them) and then write every gradient texel exactly once from sums taken in a fixed order: two calls return the same bits, no zero fill

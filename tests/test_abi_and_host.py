@@ -367,7 +367,7 @@ def test_roctx_switch_loads_and_is_off_by_default():
 
 
 def test_sorted_scatter_argument_validation_needs_no_gpu():
-    """ego_scatter_sorted_workspace_bytes / ego_scatter_sort refuse bad arguments before touching the device (csrc/ego_scatter_sorted.hip)."""
+    """ego_scatter_sorted_workspace_bytes / ego_scatter_sort refuse bad arguments before touching the device (csrc/ego_scatter_sort.hip, csrc/ego_sorted_geom.h)."""
     lib = _lib.load()
     sc = _lib.new_scene()
     assert lib.ego_scatter_sorted_workspace_bytes(None, 4, 4) == -1
@@ -385,3 +385,55 @@ def test_sorted_scatter_argument_validation_needs_no_gpu():
     sc.app.res[:] = [150, 172, 500]
     assert lib.ego_scatter_sort(ctypes.byref(sc), 256, 4, 4, 256, 1 << 40, None) == -1 and b"one resolution" in lib.ego_last_error()
     assert lib.ego_weight_grad_partial_floats() == 1024 * 128 * 160
+
+
+# ego_scatter_sorted_workspace_bytes of the library before the sort and the geometry left ego_scatter_sorted.hip, per grid for the
+# batches (N, S) = (8192, 256), (48, 32), (1, 1): blocked and unblocked key layouts, dense and sparse cell buffers, a line that does not
+# fit the walk ([8, 8, 4096]) and a grid whose blocked layout is refused ([8, 700, 3700])
+_SORTED_WS_BATCHES = ((8192, 256), (48, 32), (1, 1))
+_SORTED_WS_BYTES = {
+    (150, 172, 516): (470647040, 47860224, 44220672),
+    (300, 346, 1036): (3055684608, 92251904, 88612352),
+    (10, 12, 34): (135331328, 21836800, 20269056),
+    (2, 2, 2): (135277824, 16308992, 16239872),
+    (8, 8, 4096): (184865536, 31831040, 28213504),
+    (8, 8, 700): (136006400, 43047168, 39421952),
+    (8, 700, 3700): (4996299264, 92387328, 88747776),
+    (64, 64, 2000): (563446784, 58688000, 55048448),
+}
+# the same with EGO_SORTED_LINES=separate, and with EGO_SORTED_WALK=0 (no line blocks in the keys), for the first two batches
+_SORTED_WS_BYTES_PLAIN = {
+    (150, 172, 516): (387471104, 46606080),
+    (10, 12, 34): (135331328, 21836800),
+    (8, 700, 3700): (4996299264, 92387328),
+}
+
+
+def test_sorted_scatter_workspace_layout_is_pinned():
+    """The workspace size is the end of the layout that the sort (csrc/ego_scatter_sort.hip) and the scatters (csrc/ego_scatter_sorted.hip)
+    share through csrc/ego_sorted_geom.h: every sizing branch of make_geom must give the bytes it gave before the split."""
+    lib = _lib.load()
+
+    def table(grids, batches):
+        out = {}
+        for res in grids:
+            sc = _lib.new_scene()
+            sc.density.res[:] = list(res)
+            sc.app.res[:] = list(res)
+            out[res] = tuple(lib.ego_scatter_sorted_workspace_bytes(ctypes.byref(sc), n, s) for n, s in batches)
+        return out
+
+    switches = ("EGO_SORTED_LINES", "EGO_SORTED_WALK")
+    saved = {k: os.environ.pop(k, None) for k in switches}
+    try:
+        assert table(_SORTED_WS_BYTES, _SORTED_WS_BATCHES) == _SORTED_WS_BYTES
+        for key, value in (("EGO_SORTED_LINES", "separate"), ("EGO_SORTED_WALK", "0")):   # read per call
+            os.environ[key] = value
+            try:
+                assert table(_SORTED_WS_BYTES_PLAIN, _SORTED_WS_BATCHES[:2]) == _SORTED_WS_BYTES_PLAIN, key
+            finally:
+                del os.environ[key]
+    finally:
+        for k, v in saved.items():
+            if v is not None:
+                os.environ[k] = v
