@@ -127,8 +127,6 @@ __global__ __launch_bounds__(256) void k_ray_batch_sample(BankArgs b, int mode, 
   if (rays || rgb) gather_row(b, id, i, rays, rgb);
 }
 
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
 // shared argument checks; `what` names the entry point in the message
 int check_bank(const ego_ray_bank* bank, bool need_images, const char* what, BankArgs* out) {
   if (!bank) return ego_fail(EGO_E_BADARG, "%s: null bank", what);

@@ -261,8 +261,6 @@ __global__ __launch_bounds__(256) void k_resolve_frame(ResolveArgs r) {
   }
 }
 
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
 }  // namespace
 
 extern "C" {

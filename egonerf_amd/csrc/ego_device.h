@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/egonerf_hip.h"
+#include "ego_host.h"   // ego_fail, for check_field
 
 #define EGO_WAVE 64
 
@@ -72,6 +73,18 @@ __host__ inline bool ego_field_is_compact(const ego_vm_field& f, int elem_bytes)
   return hi - lo < ((uintptr_t)1 << 32);
 }
 
+// what every forward gather of a density field asks of it (the entry points of ego_stages.hip and ego_march.hip)
+__host__ inline int check_field(const ego_vm_field& f, const char* what) {
+  for (int g = 0; g < 2; ++g)
+    for (int i = 0; i < 3; ++i)
+      if (!f.plane[g][i] || !f.line[g][i]) return ego_fail(EGO_E_BADARG, "%s: null table pointer", what);
+  if (f.res[0] < 2 || f.res[1] < 2 || f.res[2] < 2) return ego_fail(EGO_E_BADARG, "%s: resolution < 2", what);
+  if (!ego_field_is_compact(f, 4))
+    return ego_fail(EGO_E_BADARG, "%s: the 12 tables of a field must lie within 4 GB of each other (allocate them from one buffer): "
+                                  "the gathers address taps as base + 32-bit offset", what);
+  return EGO_OK;
+}
+
 __host__ inline DevCoords make_coords(const ego_scene& s, bool fine_pass = false) {
   DevCoords c;
   c.cx = s.center[0]; c.cy = s.center[1]; c.cz = s.center[2];
@@ -80,6 +93,19 @@ __host__ inline DevCoords make_coords(const ego_scene& s, bool fine_pass = false
   c.r_lut = s.r_lut; c.n_lut = s.n_r_lut; c.n_r = s.n_r;
   if (fine_pass && s.r_lut_fine) { c.r_lut = s.r_lut_fine; c.n_lut = s.n_r_lut_fine; c.n_r = s.n_r_fine; }
   return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row A  — sample schedule -> points      models/EgoNeRF.py:56-87
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float sched_z(const float* __restrict__ r_sched, const float* __restrict__ jitter,
+                                         int64_t ray, int s, int S, float near_) {
+  float r = r_sched[s];
+  if (jitter) {
+    const float step = (s < S - 1) ? __fsub_rn(r_sched[s + 1], r) : __fsub_rn(r, r_sched[S - 2]);
+    r = __fadd_rn(r, __fmul_rn(step, jitter[ray * S + s]));
+  }
+  return __fadd_rn(near_, r);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -182,6 +208,52 @@ __device__ __forceinline__ constexpr int vm_plane_y(int i) { return i == 0 ? 1 :
 __device__ __forceinline__ constexpr int vm_line_ax(int i) { return 2 - i; }
 
 // ---------------------------------------------------------------------------------------------
+// Row M — occupancy lookup: trilinear F.grid_sample (align_corners, zeros) on a {0,1} volume [N_phi][N_theta][N_r]
+// models/EgoNeRF.py:11-24
+// ---------------------------------------------------------------------------------------------
+struct DevOcc {
+  const uint8_t* vol;  // [2][res2][res1][res0] or null
+  int32_t res[3];
+  const uint8_t* cell; // optional [2][res2-1][res1-1][res0-1]: OR of the 8 corner voxels of every cell (ego_scene.occ_cell)
+};
+
+__device__ __forceinline__ float occ_sample(const DevOcc& O, int g, float a_r, float a_th, float a_ph) {
+  const Lin1 X = lin_setup(a_r, O.res[0]), Y = lin_setup(a_th, O.res[1]), Z = lin_setup(a_ph, O.res[2]);
+  const uint8_t* V = O.vol + (int64_t)g * O.res[0] * O.res[1] * O.res[2];
+  float v = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int ix = (k & 1) ? X.i1 : X.i0, iy = (k & 2) ? Y.i1 : Y.i0, iz = (k & 4) ? Z.i1 : Z.i0;
+    const float w = ((k & 1) ? X.w1 : X.w0) * ((k & 2) ? Y.w1 : Y.w0) * ((k & 4) ? Z.w1 : Z.w0);
+    v += w * (float)V[((int64_t)iz * O.res[1] + iy) * O.res[0] + ix];
+  }
+  return v;
+}
+
+// "mask value > 0" (tensorBase.py:464-478) for the march: a sample strictly inside a cell (all six axis weights > 0, all taps in
+// range) has a positive trilinear value iff any of the cell's eight corner voxels is set - one byte of the per-cell OR volume instead
+// of eight dependent byte loads and the interpolation; samples on a lattice plane / outside the volume take the exact evaluation
+__device__ __forceinline__ bool occ_occupied(const DevOcc& O, int g, float a_r, float a_th, float a_ph) {
+  if (O.cell) {
+    const Lin1 X = lin_setup(a_r, O.res[0]), Y = lin_setup(a_th, O.res[1]), Z = lin_setup(a_ph, O.res[2]);
+    const bool interior = fminf(fminf(fminf(X.w0, X.w1), fminf(Y.w0, Y.w1)), fminf(Z.w0, Z.w1)) > 0.f;
+    if (interior) {
+      const int64_t c0 = O.res[0] - 1, c1 = O.res[1] - 1, c2 = O.res[2] - 1;
+      return O.cell[(((int64_t)g * c2 + Z.i0) * c1 + Y.i0) * c0 + X.i0] != 0;
+    }
+  }
+  return occ_sample(O, g, a_r, a_th, a_ph) > 0.f;
+}
+
+__host__ inline DevOcc make_occ(const ego_scene& sc, int coarse) {
+  DevOcc o;
+  o.vol = coarse ? nullptr : sc.occ;  // the coarse (proposal) pass always sees the full field
+  o.res[0] = sc.occ_res[0]; o.res[1] = sc.occ_res[1]; o.res[2] = sc.occ_res[2];
+  o.cell = (o.vol && o.res[0] >= 2 && o.res[1] >= 2 && o.res[2] >= 2) ? sc.occ_cell : nullptr;
+  return o;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Row E scalars
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float softplus_shift(float f, float shift) {
@@ -280,7 +352,7 @@ __device__ __forceinline__ void envmap_lookup(const float* __restrict__ em, int 
 
 // Equirectangular camera ray of pixel (row, col) of an H x W panorama: get_ray_directions_360 (dataLoader/ray_utils.py:24-40),
 // the datasets' normalisation and get_rays (:85-113).  m = camera-to-world pose, 3x4 row-major (kernel argument or device memory);
-// o[6] = origin, direction.  ONE body for ego_erp_rays (csrc/ego_ops.hip) and the ray-bank gather (csrc/ego_batch.hip): a gathered ray
+// o[6] = origin, direction.  ONE body for ego_erp_rays (csrc/ego_stages.hip) and the ray-bank gather (csrc/ego_batch.hip): a gathered ray
 // has the bits of the corresponding row of ego_erp_rays.
 __device__ __forceinline__ void erp_ray(int H, int W, int row, int col, const float* m, int normalize, float* o) {
   const float i = (float)col + 0.5f, j = (float)row + 0.5f;

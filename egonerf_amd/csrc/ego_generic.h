@@ -1,5 +1,5 @@
 // Internal (not part of the C ABI): the any-shape compatibility kernels of ego_generic.hip, called by the ABI entry points of
-// ego_pack.hip / ego_shade.hip / ego_ops.hip when the scene's shape is not the tuned one.
+// ego_pack.hip / ego_shade.hip / ego_march.hip when the scene's shape is not the tuned one.
 #pragma once
 #include "../../include/egonerf_hip.h"
 

@@ -35,6 +35,9 @@ int ego_shaded_count(int32_t mode, const int32_t* n_live, const uint8_t* act, in
 int ego_shade_live(const ego_scene* sc, const float* rays, const float* z, const float* coords, int64_t N, int32_t S, const int32_t* live,
                    const int32_t* n_live, float* rgb, void* stream);
 
+// workgroups of b threads for n items
+inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
 inline int ego_launch_status(const char* kernel) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ego_fail((int)e, "%s: launch failed: %s", kernel, hipGetErrorString(e));
@@ -50,7 +53,7 @@ struct EgoRoctx {
   int (*push)(const char*);
   int (*pop)();
 };
-const EgoRoctx* ego_roctx();   // csrc/ego_ops.hip; nullptr when tracing is off or the roctx library is absent
+const EgoRoctx* ego_roctx();   // csrc/ego_runtime.hip; nullptr when tracing is off or the roctx library is absent
 
 struct EgoRange {
   const EgoRoctx* r;

@@ -147,8 +147,6 @@ __global__ __launch_bounds__(256) void k_msi_render(const float* __restrict__ ra
   depth[i] = dp;
 }
 
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
 }  // namespace
 
 extern "C" {

@@ -20,7 +20,6 @@
 namespace {
 
 inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 constexpr int LD = 160;        // row width of the weight-gradient B operands (ego_weight_grad_det's 5 column blocks)
 // host copies of ego_device.h's axis maps (matMode / vecMode, EgoNeRF.py:30-33)
 inline int px(int i) { return i == 2 ? 1 : 0; }

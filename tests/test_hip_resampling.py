@@ -6,6 +6,10 @@ Truth is the oracle's sample_pdf / raw2alpha evaluated in float64.  Every fine s
 tests/test_hip_parity.py::test_stage_sample_pdf (clause c): a float32 cdf carries ~1e-7 of rounding, which (u - cdf_lo) / denom turns
 into 4e-7 / denom of the bin's width.  The inputs keep every cdf step clear of the reference's `denom < 1e-5` switch, so no entry is
 excused; that the inputs are that well conditioned is itself asserted (the float32 oracle must stay within half of the bound)."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -126,6 +130,33 @@ def test_sample_pdf_vs_float64(Sc, n_fine, mode):
     for use_coarse in (1, 0):
         check_case(z, w, None if mode == "eval" else u, n_fine, use_coarse, mode)
     print("worst err/bound so far:", WORST, " float32 oracle on this case:", round(r32, 3))
+
+
+# ---- 1b. the same launches, bit for bit, against a recorded build -------------------------------------------------------------------
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resample_digests.json")
+
+
+def sample_pdf_digests():
+    """case -> [sha256 of z_out's bytes, sha256 of z_new's bytes] for every shape above, u = NULL and hash-uniform u, use_coarse 0 and 1.
+    tools/capture_resample_digests.py records this from another build of the library."""
+    out = {}
+    for Sc, n_fine in WAVE + WORKGROUP:
+        z, w, u = make_inputs(Sc, n_fine)
+        for mode in ("eval", "train"):
+            for use_coarse in (0, 1):
+                got = run_kernel(z, w, n_fine if mode == "eval" else u, use_coarse)
+                out[f"{Sc}+{n_fine} {mode} use_coarse={use_coarse}"] = [hashlib.sha256(t.contiguous().numpy().tobytes()).hexdigest() for t in got]
+    return out
+
+
+def test_sample_pdf_bits_match_recorded():
+    """Both kernels are deterministic (no atomics, every float operation an explicit _rn intrinsic or a double add in a fixed order), so a
+    rewrite that keeps the arithmetic returns the recorded build's bytes: equality, no tolerance.  The fixture names its commit."""
+    recorded = json.load(open(DIGESTS))["digests"]
+    got = sample_pdf_digests()
+    assert len(got) == 48 and sorted(got) == sorted(recorded)
+    differs = [f"{case}: {name}" for case in got for name, a, b in zip(("z_out", "z_new"), got[case], recorded[case]) if a != b]
+    assert not differs, differs
 
 
 # ---- 2. ties and an unsorted coarse run --------------------------------------------------------------------------------------------

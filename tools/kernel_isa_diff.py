@@ -8,9 +8,10 @@ Per kernel (matched by demangled name over all code objects of a library, so a k
   * its instruction stream as llvm-objdump prints it, without addresses and encodings (the `// addr: words` tail of a line) and with
     the literal of a pc-relative address computation (s_getpc_b64 followed by s_add_u32 / s_addc_u32) masked: those literals are
     distances to other symbols of the code object, which move with the file layout.  Branch targets stay: they are relative to the
-    kernel itself.  The zero padding behind a kernel's last instruction (printed as `...`) is not part of the stream.
+    kernel itself.  The padding behind a kernel's last instruction is not part of the stream: zeros (printed as `...`), and the run of
+    `s_nop 0` that closes a source's text section behind its last kernel (which kernel that is changes when kernels change sources).
 The compiler gives kernels of an anonymous namespace no per-file decoration in this (non-RDC) build, so names compare as they are.
-Exit status 1 if the kernel sets differ or any kernel differs."""
+A kernel that differs is listed with the resource line of both builds.  Exit status 1 if the kernel sets differ or any kernel differs."""
 from __future__ import annotations
 
 import argparse
@@ -76,6 +77,9 @@ def _streams(objdump: str, co: str) -> dict:
             if re.match(r"s_addc?_u32 ", ins):
                 ins = re.sub(r"(0x[0-9a-f]+|-?\d+)$", "<pcrel>", ins)
         cur.append(ins)
+    for body in out.values():
+        while body and body[-1] == "s_nop 0":
+            del body[-1]
     return out
 
 
@@ -121,6 +125,8 @@ def main() -> int:
             n_diff += bool(why)
             res = " ".join(f"{k[1:]}={mn[k]}" for k in META)
             lines.append(("differs  " if why else "same     ") + f"{name}  [{len(sn)} instructions; {res}]" + ("  <- " + "; ".join(why) if why else ""))
+            if why:   # a kernel that was meant to change is judged by its resources: the old build's line next to the new one
+                lines.append(f"  before {name}  [{len(so)} instructions; " + " ".join(f"{k[1:]}={mo[k]}" for k in META) + "]")
     n_old, n_new = sum(map(len, old.values())), sum(map(len, new.values()))
     lines.append(f"kernels: {n_old} before, {n_new} after; same {n_same}, differs {n_diff}")
     text = "\n".join(lines) + "\n"

@@ -7,7 +7,7 @@ Per case: the mark names collected through train.KERNEL_MARKS (one per library c
 rgb_map, depth, alpha and of every parameter gradient in named_parameters() order, from pinned rays / jitter / u / target
 (egonerf_amd.synth).  Two checkouts that queue the same calls with the same arguments give the same file, except where float atomics
 add in arrival order; those entries are listed under "excused" (derived from the case's own mark names: the atomic table scatters and
-the environment map's gradient, csrc/ego_ops.hip::k_envmap_bwd; and every parameter gradient when model.deterministic_scatter is off,
+the environment map's gradient, csrc/ego_stages.hip::k_envmap_bwd; and every parameter gradient when model.deterministic_scatter is off,
 which also turns ego_weight_grad's fixed-order sums into atomics).
 --compare fails on any other difference.  Each case runs once; the first failure ends the run."""
 import hashlib
