@@ -6,7 +6,7 @@ Public surface mirrors the reference modules for that path:
     egonerf_amd.renderer    <- renderer.py (volume_renderer, PSNR evaluation, ray sharding)
     egonerf_amd.sampler     <- sampler.py
 Beyond the reference:
-    egonerf_amd.msi         multi-sphere images: bake_msi, MultiSphereImage, layer_bounds
+    egonerf_amd.msi         multi-sphere images: bake_msi, refine_msi, MultiSphereImage, layer_bounds
 Native code: egonerf_amd/csrc/*.hip -> libegonerf_hip.so behind include/egonerf_hip.h (C ABI).
 """
 __all__ = ["model", "coordinates", "renderer", "sampler", "synth", "msi"]

@@ -121,6 +121,9 @@ PROTOTYPES = {
     "ego_resolve_frame": (C.c_int, [P, P, I64, I64, I32, I32, I32, F32, F32, P, I32, P, P, P]),
     "ego_msi_layers": (C.c_int, [P, P, I32, P, I64, I32, P, I32, I64, I64, I32, P, P]),
     "ego_msi_render": (C.c_int, [P, I64, F32, F32, F32, P, I32, I32, I32, I32, P, P, P, P, P]),
+    "ego_msi_render_backward_workspace_bytes": (I64, [I64, I32]),
+    "ego_msi_render_backward": (C.c_int, [P, I64, F32, F32, F32, P, I32, I32, I32, I32, P, P, P, P, P, P, I64, P]),
+    "ego_msi_project": (C.c_int, [P, I64, P]),
     "ego_copy_out": (C.c_int, [I32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), I32, P]),
     "ego_density_feature_backward_workspace_bytes": (I64, [SP, I64, I32]),
     "ego_density_feature_backward": (C.c_int, [SP, P, I64, I32, P, C.POINTER(VmGrad), P, I64, P]),

@@ -1,4 +1,4 @@
-// Multi-sphere images (include/egonerf_hip.h: ego_msi_layers, ego_msi_render): a scene integrated once into L concentric
+// Multi-sphere images (include/egonerf_hip.h: ego_msi_layers, ego_msi_render, ego_msi_render_backward, ego_msi_project): a scene integrated once into L concentric
 // shells of premultiplied RGBA around a centre, and views from nearby positions composited from the shells alone - L sphere
 // intersections, L bilinear taps and an "over" per pixel, no tables and no MLP.
 //
@@ -6,7 +6,8 @@
 // whole texels; the thread finds its run of the ray's ascending z by bisection and folds it in sample order.  k_msi_render is the playback
 // hot path: one thread per ray, wave64, no LDS; a tap is four loads of one whole texel (16 B float, 8 B half), neighbouring pixels hit
 // neighbouring texels, the radii are wave-uniform.  All arithmetic is fp32 and - like the whole library (-ffp-contract=off) and once more
-// by the pragma below - never contracted: tests/msi_ref.py restates both kernels operation by operation.
+// by the pragma below - never contracted: tests/msi_ref.py restates both kernels operation by operation.  k_msi_render_bwd is playback's
+// backward for float32 texels (float atomic adds to the taps), k_msi_project the clamp that follows an optimiser step.
 #include "ego_device.h"
 #include "ego_host.h"
 
@@ -104,47 +105,183 @@ __device__ __forceinline__ f32x4 msi_sample(const T* __restrict__ img, const Msi
   return o;
 }
 
-// One thread per ray.  p = o - c, d = the unit direction; layer k is crossed (from inside) at t_k = -b + sqrt(b b - p.p + R_k R_k),
-// b = p.d, and skipped when the eye is not inside it (R_k <= |p|); the "over" runs front to back through every layer - no early exit.
+// A ray as every MSI kernel sees it: p = o - c, d = the unit direction, dn = the given direction's length, b = p.d, bb_pp = b b - p.p,
+// pn = |p|.  The direction is normalised first - exact for a direction of length exactly 1, a rounding otherwise - so that the pinhole
+// cameras' rays, which are not normalised, cross the shells where they should.
+struct MsiRay {
+  float px, py, pz, dx, dy, dz, dn, b, bb_pp, pn;
+};
+
+__device__ __forceinline__ MsiRay msi_ray(const float* __restrict__ rays, int64_t i, float cx, float cy, float cz) {
+  const f32x2* in = (const f32x2*)(rays + i * 6);   // 24 bytes per row, 8-byte aligned (checked by the entry point)
+  const f32x2 q0 = in[0], q1 = in[1], q2 = in[2];
+  MsiRay r;
+  r.px = q0.x - cx; r.py = q0.y - cy; r.pz = q1.x - cz;
+  r.dn = __fsqrt_rn((q1.y * q1.y + q2.x * q2.x) + q2.y * q2.y);
+  r.dx = q1.y / r.dn; r.dy = q2.x / r.dn; r.dz = q2.y / r.dn;
+  const float pp = (r.px * r.px + r.py * r.py) + r.pz * r.pz;
+  r.b = (r.px * r.dx + r.py * r.dy) + r.pz * r.dz;
+  r.bb_pp = r.b * r.b - pp;
+  r.pn = __fsqrt_rn(pp);
+  return r;
+}
+
+// Layer of radius R is crossed (from inside) at t = -b + sqrt(b b - p.p + R R); the tap is the crossing point's direction from the centre
+__device__ __forceinline__ float msi_cross(const MsiRay& r, float R) { return __fsqrt_rn(fmaxf(r.bb_pp + R * R, 0.f)) - r.b; }
+__device__ __forceinline__ MsiTap msi_layer_tap(const MsiRay& r, float R, float tk, int Hm, int Wm) {
+  return msi_tap((r.px + tk * r.dx) / R, (r.py + tk * r.dy) / R, (r.pz + tk * r.dz) / R, Hm, Wm);
+}
+
+// One thread per ray.  A layer is skipped when the eye is not inside it (R_k <= |p|); the "over" runs front to back through every
+// layer - no early exit; depth is reported in the GIVEN ray's parameter, as a model does.
 template <typename T>
 __global__ __launch_bounds__(256) void k_msi_render(const float* __restrict__ rays, int64_t N, float cx, float cy, float cz,
                                                     const float* __restrict__ radii, int L, int Hm, int Wm, const T* __restrict__ layers,
                                                     const T* __restrict__ background, float* __restrict__ rgb, float* __restrict__ depth) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  const f32x2* in = (const f32x2*)(rays + i * 6);   // 24 bytes per row, 8-byte aligned (checked by the entry point)
-  const f32x2 q0 = in[0], q1 = in[1], q2 = in[2];
-  const float px = q0.x - cx, py = q0.y - cy, pz = q1.x - cz;
-  // the direction is normalised first - exact for a direction of length exactly 1, a rounding otherwise - so that the pinhole cameras'
-  // rays, which are not normalised, cross the shells where they should; depth is reported in the GIVEN ray's parameter, as a model does
-  const float dn = __fsqrt_rn((q1.y * q1.y + q2.x * q2.x) + q2.y * q2.y);
-  const float dx = q1.y / dn, dy = q2.x / dn, dz = q2.y / dn;
-  const float pp = (px * px + py * py) + pz * pz;
-  const float b = (px * dx + py * dy) + pz * dz;
-  const float bb_pp = b * b - pp;
-  const float pn = __fsqrt_rn(pp);
+  const MsiRay ray = msi_ray(rays, i, cx, cy, cz);
   const int64_t texels = (int64_t)Hm * Wm;
   float T_ = 1.f, r = 0.f, g = 0.f, bl = 0.f, dp = 0.f;
   for (int k = 0; k < L; ++k) {
     const float R = radii[k];
-    if (R <= pn) continue;
-    const float tk = __fsqrt_rn(fmaxf(bb_pp + R * R, 0.f)) - b;
-    const MsiTap tap = msi_tap((px + tk * dx) / R, (py + tk * dy) / R, (pz + tk * dz) / R, Hm, Wm);
-    const f32x4 v = msi_sample(layers + (int64_t)k * texels * 4, tap);
+    if (R <= ray.pn) continue;
+    const float tk = msi_cross(ray, R);
+    const f32x4 v = msi_sample(layers + (int64_t)k * texels * 4, msi_layer_tap(ray, R, tk, Hm, Wm));
     r = r + T_ * v.x;
     g = g + T_ * v.y;
     bl = bl + T_ * v.z;
-    dp = dp + (T_ * v.w) * (tk / dn);
+    dp = dp + (T_ * v.w) * (tk / ray.dn);
     T_ = T_ * (1.f - v.w);
   }
   if (background) {   // the shell at infinity, seen in the ray's direction; its alpha is taken as 1
-    const f32x4 v = msi_sample(background, msi_tap(dx, dy, dz, Hm, Wm));
+    const f32x4 v = msi_sample(background, msi_tap(ray.dx, ray.dy, ray.dz, Hm, Wm));
     r = r + T_ * v.x;
     g = g + T_ * v.y;
     bl = bl + T_ * v.z;
   }
   rgb[i * 3] = r; rgb[i * 3 + 1] = g; rgb[i * 3 + 2] = bl;
   depth[i] = dp;
+}
+
+// ---- the backward of playback (DESIGN.md 3.3 "Refinement") --------------------------------------------------------------------------
+// rgb = sum_k T_k C_k + T_end C_bg over the live layers, T_k = prod_{j<k} (1 - A_j).  With g = d loss / d rgb:
+//   dC_k = T_k g,  dA_k = -T_k B_{k+1},  B_k = C_k.g + (1 - A_k) B_{k+1},  B_end = C_bg.g (0 without a background),  dC_bg = T_end g.
+// Nothing divides by (1 - A_k): a forward walk stores T_k of every live layer in the workspace ([L][N], so a wave's accesses are
+// contiguous), a walk back carries B.  Behind a layer with A = 1 every T_k is exactly 0 and so is everything added there.  A sample's
+// gradient goes to its four taps with the forward's weights, by float atomic adds: the sums depend on the order of arrival.
+
+__device__ __forceinline__ float dot_g(const f32x4 v, float gx, float gy, float gz) { return (v.x * gx + v.y * gy) + v.z * gz; }
+
+// The forward walk: T_k of every live layer -> ws[k N + i]; returns T_end
+__device__ __forceinline__ float msi_store_transmittance(const MsiRay& ray, bool in, int64_t i, int64_t N, const float* __restrict__ radii,
+                                                         int L, int Hm, int Wm, const float* __restrict__ layers, float* __restrict__ ws) {
+  const int64_t texels = (int64_t)Hm * Wm;
+  float T_ = 1.f;
+  for (int k = 0; k < L; ++k) {
+    const float R = radii[k];
+    if (!in || R <= ray.pn) continue;
+    ws[(int64_t)k * N + i] = T_;
+    const f32x4 v = msi_sample(layers + (int64_t)k * texels * 4, msi_layer_tap(ray, R, msi_cross(ray, R), Hm, Wm));
+    T_ = T_ * (1.f - v.w);
+  }
+  return T_;
+}
+
+// The adds: the four lanes of a quad take their four rays in turn, and for each lane c adds channel c - a wave's add instruction is
+// sixteen whole texels (16 B each), not sixty-four single dwords in sixty-four places (a lane per ray with sixteen adds of its own per
+// layer was measured first: 3.5 x slower).  The values cross the lanes by DPP quad broadcasts, which every lane of the wave
+// has to execute: no lane returns early, a lane without a ray or a ray outside the layer carries zeros.
+template <int J>
+__device__ __forceinline__ float quad_f(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), J * 0x55, 0xf, 0xf, true));
+}
+template <int J>
+__device__ __forceinline__ int quad_i(int x) { return __builtin_amdgcn_update_dpp(0, x, J * 0x55, 0xf, 0xf, true); }
+
+struct QuadTap {
+  int i00, i01, i10, i11;   // texels < 2^31 (checked by the entry point)
+  float fr, fc;
+};
+
+// One add instruction: lane (q, c) adds `a` to channel c of `texel`.  Every lane of the wave arrives here.  The first branch matters only
+// for images of a few texels: when the sixteen quads aim at ONE texel the wave sums their shares first, pairwise, and adds once.  On an
+// image of useful size the rays of a wave never all share a texel and it costs one wave-uniform test per add (nothing measurable).  It is
+// there for accuracy, not speed: thousands of shares added one by one to a single float32 wander further from the exact sum than the
+// tolerance of tests/test_hip_msi_refine.py allows; summed sixteen at a time they do not.
+__device__ __forceinline__ void add_quad(float* __restrict__ img, int texel, int c, float a) {
+  if (__all(texel == __builtin_amdgcn_readfirstlane(texel))) {
+    a = a + __shfl_xor(a, 4);
+    a = a + __shfl_xor(a, 8);
+    a = a + __shfl_xor(a, 16);
+    a = a + __shfl_xor(a, 32);
+    if ((threadIdx.x & 63) >= 4) return;
+  }
+  if (a != 0.f) unsafeAtomicAdd(img + (int64_t)texel * 4 + c, a);
+}
+
+template <int J>
+__device__ __forceinline__ void scatter_quad_from(float* __restrict__ img, const QuadTap& t, const f32x4 dv, int c) {
+  const float x = quad_f<J>(dv.x), y = quad_f<J>(dv.y), z = quad_f<J>(dv.z), w = quad_f<J>(dv.w);
+  const float mine = c == 0 ? x : (c == 1 ? y : (c == 2 ? z : w));
+  const float fr = quad_f<J>(t.fr), fc = quad_f<J>(t.fc);
+  const int i00 = quad_i<J>(t.i00), i01 = quad_i<J>(t.i01), i10 = quad_i<J>(t.i10), i11 = quad_i<J>(t.i11);
+  const float gc = 1.f - fc, gr = 1.f - fr;
+  add_quad(img, i00, c, mine * (gc * gr));
+  add_quad(img, i01, c, mine * (fc * gr));
+  add_quad(img, i10, c, mine * (gc * fr));
+  add_quad(img, i11, c, mine * (fc * fr));
+}
+
+// live == false: the lane contributes nothing (zero gradient, zero weights on texel 0), whatever its tap holds
+__device__ __forceinline__ void scatter_quad(float* __restrict__ img, const MsiTap& tap, bool live, f32x4 dv, int c) {
+  QuadTap t;
+  t.i00 = live ? (int)tap.i00 : 0; t.i01 = live ? (int)tap.i01 : 0; t.i10 = live ? (int)tap.i10 : 0; t.i11 = live ? (int)tap.i11 : 0;
+  t.fr = live ? tap.fr : 0.f; t.fc = live ? tap.fc : 0.f;
+  if (!live) dv = f32x4{0.f, 0.f, 0.f, 0.f};
+  scatter_quad_from<0>(img, t, dv, c);
+  scatter_quad_from<1>(img, t, dv, c);
+  scatter_quad_from<2>(img, t, dv, c);
+  scatter_quad_from<3>(img, t, dv, c);
+}
+
+__global__ __launch_bounds__(256) void k_msi_render_bwd(const float* __restrict__ rays, int64_t N, float cx, float cy, float cz,
+                                                        const float* __restrict__ radii, int L, int Hm, int Wm,
+                                                        const float* __restrict__ layers, const float* __restrict__ background,
+                                                        const float* __restrict__ g_rgb, float* __restrict__ g_layers,
+                                                        float* __restrict__ g_background, float* __restrict__ ws) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool in = i < N;
+  const int64_t ii = in ? i : N - 1;   // a lane past the end reads the last ray and adds nothing
+  const int c = threadIdx.x & 3;
+  const MsiRay ray = msi_ray(rays, ii, cx, cy, cz);
+  const int64_t texels = (int64_t)Hm * Wm;
+  const float gx = g_rgb[ii * 3], gy = g_rgb[ii * 3 + 1], gz = g_rgb[ii * 3 + 2];
+  const float T_end = msi_store_transmittance(ray, in, ii, N, radii, L, Hm, Wm, layers, ws);
+  float B = 0.f;
+  if (background) {
+    const MsiTap tap = msi_tap(ray.dx, ray.dy, ray.dz, Hm, Wm);
+    B = dot_g(msi_sample(background, tap), gx, gy, gz);
+    if (g_background) scatter_quad(g_background, tap, in, f32x4{T_end * gx, T_end * gy, T_end * gz, 0.f}, c);
+  }
+  if (!g_layers) return;   // only the background's gradient was asked for (the same for every lane)
+  for (int k = L - 1; k >= 0; --k) {
+    const float R = radii[k];
+    const bool live = in && !(R <= ray.pn);
+    const float Tk = live ? ws[(int64_t)k * N + ii] : 0.f;
+    const MsiTap tap = msi_layer_tap(ray, R, msi_cross(ray, R), Hm, Wm);
+    const f32x4 v = msi_sample(layers + (int64_t)k * texels * 4, tap);
+    scatter_quad(g_layers + (int64_t)k * texels * 4, tap, live, f32x4{Tk * gx, Tk * gy, Tk * gz, -(Tk * B)}, c);
+    if (live) B = dot_g(v, gx, gy, gz) + (1.f - v.w) * B;
+  }
+}
+
+// in place: C <- max(C, 0), A <- clamp(A, 0, 1); a NaN becomes 0
+__global__ __launch_bounds__(256) void k_msi_project(float* __restrict__ texels, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const f32x4 v = load_texel(texels, i);
+  store_texel(texels, i, f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fminf(fmaxf(v.w, 0.f), 1.f)});
 }
 
 }  // namespace
@@ -190,6 +327,43 @@ int ego_msi_render(const float* rays, int64_t N, float cx, float cy, float cz, c
     k_msi_render<_Float16><<<blocks, 256, 0, (hipStream_t)stream>>>(rays, N, cx, cy, cz, radii, L, Hm, Wm, (const _Float16*)layers,
                                                                     (const _Float16*)background, rgb, depth);
   return ego_launch_status("k_msi_render");
+}
+
+int64_t ego_msi_render_backward_workspace_bytes(int64_t N, int32_t L) {
+  if (N < 0 || L < 1) return -1;
+  return N * (int64_t)L * (int64_t)sizeof(float);
+}
+
+int ego_msi_render_backward(const float* rays, int64_t N, float cx, float cy, float cz, const float* radii, int32_t L, int32_t Hm, int32_t Wm,
+                            int32_t texel_type, const void* layers, const void* background, const float* g_rgb, float* g_layers,
+                            float* g_background, void* workspace, int64_t workspace_bytes, void* stream) {
+  EGO_TRACE("ego_msi_render_backward");
+  EGO_REQUIRE(N >= 0 && L >= 1 && Hm >= 1 && Wm >= 1, "msi_render_backward: N < 0, or L, Hm or Wm < 1");
+  EGO_REQUIRE(cx == cx && cy == cy && cz == cz, "msi_render_backward: NaN centre");
+  EGO_REQUIRE(texel_type == EGO_MSI_F32 || texel_type == EGO_MSI_F16, "msi_render_backward: unknown texel type");
+  EGO_REQUIRE(texel_type == EGO_MSI_F32, "msi_render_backward: half texels have no gradient (convert the image to float32 texels)");
+  EGO_REQUIRE((int64_t)Hm * Wm < (1ll << 31), "msi_render_backward: Hm * Wm must stay below 2^31");
+  if (N == 0) return EGO_OK;
+  EGO_REQUIRE(rays && radii && layers && g_rgb && (g_layers || g_background), "msi_render_backward: null argument");
+  EGO_REQUIRE(!g_background || background, "msi_render_backward: g_background without a background");
+  EGO_REQUIRE(((uintptr_t)rays & 7) == 0 && ((uintptr_t)layers & 15) == 0 && ((uintptr_t)background & 15) == 0 &&
+                  ((uintptr_t)g_layers & 15) == 0 && ((uintptr_t)g_background & 15) == 0 && ((uintptr_t)g_rgb & 3) == 0,
+              "msi_render_backward: rays must be 8-byte aligned, layers, background and their gradients aligned to one texel (16 B)");
+  EGO_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0 && workspace_bytes >= ego_msi_render_backward_workspace_bytes(N, L),
+              "msi_render_backward: workspace missing, misaligned or smaller than ego_msi_render_backward_workspace_bytes(N, L)");
+  k_msi_render_bwd<<<nblk(N, 256), 256, 0, (hipStream_t)stream>>>(rays, N, cx, cy, cz, radii, L, Hm, Wm, (const float*)layers, (const float*)background,
+                                                                  g_rgb, g_layers, g_background, (float*)workspace);
+  return ego_launch_status("k_msi_render_bwd");
+}
+
+int ego_msi_project(float* texels, int64_t n_texels, void* stream) {
+  EGO_TRACE("ego_msi_project");
+  EGO_REQUIRE(n_texels >= 0 && n_texels < (1ll << 31) * 256, "msi_project: n_texels < 0 or too large for one launch");
+  if (n_texels == 0) return EGO_OK;
+  EGO_REQUIRE(texels, "msi_project: null argument");
+  EGO_REQUIRE(((uintptr_t)texels & 15) == 0, "msi_project: texels must be aligned to one texel (16 B float)");
+  k_msi_project<<<nblk(n_texels, 256), 256, 0, (hipStream_t)stream>>>(texels, n_texels);
+  return ego_launch_status("k_msi_project");
 }
 
 }  // extern "C"

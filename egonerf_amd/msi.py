@@ -4,7 +4,8 @@
 chunk - and folds every ray's samples into per-layer premultiplied RGBA (csrc/ego_msi.hip: ego_msi_layers).  A `MultiSphereImage` renders
 rays of ANY nearby origin from the shells alone (ego_msi_render: L sphere intersections, L bilinear taps and an "over" per ray - no tables,
 no MLP) and is shaped like a model, so `FrameRenderer(msi, H, W, ...)` and `evaluation_path` take it as it is: stereo, supersampling, byte
-frames and graphs included.  Not part of the reference; formulas, layout and limits: DESIGN.md 3.3.
+frames and graphs included.  Playback is differentiable in float32 texels (ego_msi_render_backward), and `refine_msi` optimises a baked
+image against a teacher's renders from inside a headbox.  Not part of the reference; formulas, layout and limits: DESIGN.md 3.3.
 """
 from __future__ import annotations
 
@@ -67,6 +68,30 @@ def _check_rays(rays, device, what: str) -> None:
         raise ValueError(f"{what}: rays must be contiguous")
 
 
+class _RenderFunction(torch.autograd.Function):
+    """Playback with a backward: the forward is the plain ego_msi_render call, the backward ego_msi_render_backward into zeroed float32
+    gradients of the texels' layout.  depth is not differentiable; rays get no gradient."""
+
+    @staticmethod
+    def forward(ctx, msi, rays, layers, background):
+        rgb, depth = msi._render(rays, layers, background)
+        ctx.msi = msi
+        ctx.save_for_backward(rays, layers, *(() if background is None else (background,)))
+        ctx.mark_non_differentiable(depth)
+        return rgb, depth
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb, _g_depth):
+        msi, (rays, layers, *rest) = ctx.msi, ctx.saved_tensors
+        background = rest[0] if rest else None
+        g_rgb = g_rgb.to(torch.float32).contiguous()
+        g_layers = torch.zeros_like(layers) if ctx.needs_input_grad[2] else None   # 1 GiB at L = 32, 1024 x 2048: only when asked for
+        g_background = torch.zeros_like(background) if background is not None and ctx.needs_input_grad[3] else None
+        msi._render_backward(rays, layers, background, g_rgb, g_layers, g_background)
+        return None, None, g_layers, g_background
+
+
 class MultiSphereImage:
     """L concentric shells of premultiplied RGBA around `center`, each an Hm x Wm equirectangular image.
 
@@ -80,7 +105,11 @@ class MultiSphereImage:
     evaluation_path take it in a model's place; every other keyword of EgoNeRF.forward is accepted and ignored.  rays: [N, 6] float32,
     contiguous; the direction need not be of unit length (the pinhole cameras' is not): the kernel normalises it and reports depth in the
     given ray's parameter, as a model does.  A layer whose
-    radius is not larger than the eye's distance from the centre is skipped; colours are not clamped (`finish_frame` does)."""
+    radius is not larger than the eye's distance from the centre is skipped; colours are not clamped (`finish_frame` does).
+
+    With grad enabled and float32 `layers` (or `background`) that require grad, `render` records a graph: `rgb.backward(...)` fills
+    `layers.grad` (and `background.grad`) through ego_msi_render_backward; depth stays non-differentiable.  Half texels that require
+    grad are refused."""
 
     def __init__(self, layers: torch.Tensor, radii, bounds, center, near_far, background: Optional[torch.Tensor] = None):
         if not isinstance(layers, torch.Tensor):
@@ -132,17 +161,34 @@ class MultiSphereImage:
     @_lib.device_guard
     def render(self, rays: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(rgb [N, 3], depth [N]) float32 of `rays` [N, 6], on the current stream (not synchronised)."""
+        wants_grad = torch.is_grad_enabled() and (self.layers.requires_grad or (self.background is not None and self.background.requires_grad))
+        if wants_grad and self.layers.dtype != torch.float32:
+            raise ValueError("MultiSphereImage.render: half texels have no gradient; train a float32 image (msi.float()) and convert back")
         if not self.layers.is_cuda:
             raise ValueError("MultiSphereImage.render: the image must live on a HIP device (the HIP path has no CPU fallback)")
         _check_rays(rays, self.device, "MultiSphereImage.render")
+        if wants_grad:
+            return _RenderFunction.apply(self, rays, self.layers, self.background)
+        return self._render(rays, self.layers, self.background)
+
+    def _render(self, rays: torch.Tensor, layers: torch.Tensor, background: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         N = rays.shape[0]
         rgb = torch.empty(N, 3, device=self.device, dtype=torch.float32)
         depth = torch.empty(N, device=self.device, dtype=torch.float32)
         c = self.center
         _lib.check(_lib.load().ego_msi_render(rays.data_ptr(), N, float(c[0]), float(c[1]), float(c[2]), self.radii.data_ptr(), self.L, self.Hm,
-                                              self.Wm, TEXEL_TYPES[self.layers.dtype], self.layers.data_ptr(), _lib.ptr(self.background),
+                                              self.Wm, TEXEL_TYPES[layers.dtype], layers.data_ptr(), _lib.ptr(background),
                                               rgb.data_ptr(), depth.data_ptr(), _lib.stream_handle()), "ego_msi_render")
         return rgb, depth
+
+    def _render_backward(self, rays, layers, background, g_rgb, g_layers, g_background) -> None:
+        """g_rgb [N, 3] -> added into g_layers and g_background (either may be None, not both): float32, contiguous, the texels' shapes."""
+        N, lib, c = rays.shape[0], _lib.load(), self.center
+        ws = torch.empty(max(int(lib.ego_msi_render_backward_workspace_bytes(N, self.L)), 4) // 4, device=self.device, dtype=torch.float32)
+        _lib.check(lib.ego_msi_render_backward(rays.data_ptr(), N, float(c[0]), float(c[1]), float(c[2]), self.radii.data_ptr(), self.L, self.Hm,
+                                               self.Wm, TEXEL_TYPES[layers.dtype], layers.data_ptr(), _lib.ptr(background), g_rgb.data_ptr(),
+                                               _lib.ptr(g_layers), _lib.ptr(g_background), ws.data_ptr(), ws.numel() * 4,
+                                               _lib.stream_handle()), "ego_msi_render_backward")
 
     # ---- texel type -----------------------------------------------------------------------------------------------------------------
     def _as(self, dtype) -> "MultiSphereImage":
@@ -242,3 +288,76 @@ def bake_msi(model, Hm: int, Wm: int, L: int, n_samples: int, center=None, dtype
             flat[first:first + count, :3] = env[:count].to(dtype)
             flat[first:first + count, 3] = 1
     return MultiSphereImage(image, radii, bounds, c, list(model.near_far), background)
+
+
+def project_msi(msi: MultiSphereImage) -> None:
+    """In place on float32 texels (ego_msi_project): C <- max(C, 0), A <- clamp(A, 0, 1), so that playback's transmittance stays in [0, 1]."""
+    if msi.layers.dtype != torch.float32 or not msi.layers.is_cuda:
+        raise ValueError("project_msi: needs float32 texels on a HIP device")
+    lib, st = _lib.load(), _lib.stream_handle()
+    for t in msi.parameters():
+        _lib.check(lib.ego_msi_project(t.data_ptr(), t.numel() // 4, st), "ego_msi_project")
+        torch.autograd.graph.increment_version(t)   # written through a raw pointer
+
+
+def headbox_rays(n: int, center: torch.Tensor, headbox: float, generator: torch.Generator) -> torch.Tensor:
+    """[n, 6] float32 on the device of `center` ([3] float32, a DEVICE tensor: nothing here copies from the host, so a loop that draws
+    rays does not wait for its stream): origins uniform in the ball of radius `headbox` around `center`, directions uniform on the unit
+    sphere."""
+    device = center.device
+    o = torch.randn(n, 3, device=device, generator=generator)
+    o = o * (headbox * torch.rand(n, 1, device=device, generator=generator) ** (1.0 / 3.0) / o.norm(dim=1, keepdim=True).clamp_min(1e-20))
+    d = torch.randn(n, 3, device=device, generator=generator)
+    d = d / d.norm(dim=1, keepdim=True).clamp_min(1e-20)
+    return torch.cat([o + center, d], dim=1).contiguous()
+
+
+DEFAULT_REFINE_LR = 1e-3
+
+
+def refine_msi(msi: MultiSphereImage, teacher, steps: int, rays_per_step: int = 65536, headbox: Optional[float] = None,
+               lr: float = DEFAULT_REFINE_LR, seed: int = 0, render_kwargs: Optional[dict] = None, log: Optional[list] = None) -> MultiSphereImage:
+    """Optimises the texels of `msi` against `teacher` (a model, or anything called like one) on rays from inside a headbox; returns a
+    new image of the input's texel type, radii, bounds, centre and near_far.
+
+    Works on a float32 copy.  Per step: `rays_per_step` rays drawn on the device from a generator seeded with `seed` (origins uniform in
+    the ball of radius `headbox` - scene units, 0 < headbox < radii[0], default 0.2 radii[0] - around the centre, unit directions uniform
+    on the sphere); the target `teacher(rays, is_train=False, need_alpha=False, **render_kwargs)[0]` under no_grad; the mean squared
+    error of `render(rays)[0]` against it; backward (ego_msi_render_backward); one FusedAdam step at `lr`; ego_msi_project.  Nothing in
+    the loop synchronises with the host; `log`, if a list, receives every step's loss as a device tensor.
+
+    `lr`: Adam walks a texel by about 10 lr for every isolated hit, whatever the gradient's size, so the rate has to fit how often a
+    texel is hit.  The default suits an image whose texels are hit in every step; a 1024 x 2048 image under 65536 rays per step
+    (a texel hit once in eight steps) needs 1e-5 to 3e-5 and is made worse by 1e-3 (profiles/r13/msi_refine.json)."""
+    from .optim import FusedAdam
+    steps, n = int(steps), int(rays_per_step)
+    if steps < 0 or n < 1:
+        raise ValueError(f"refine_msi: steps must be >= 0 and rays_per_step >= 1, got {steps} and {n}")
+    if not lr > 0:
+        raise ValueError(f"refine_msi: lr must be positive, got {lr}")
+    r0 = float(msi.radii[0])
+    headbox = 0.2 * r0 if headbox is None else float(headbox)
+    if not 0 < headbox < r0:
+        raise ValueError(f"refine_msi: headbox must lie in (0, radii[0] = {r0:g}) - the eye stays inside the innermost shell - got {headbox:g}")
+    if not msi.layers.is_cuda:
+        raise ValueError("refine_msi: the image must live on a HIP device (the HIP path has no CPU fallback)")
+    dev, kw = msi.device, dict(render_kwargs or {})
+    bg = None if msi.background is None else msi.background.detach().float().clone().requires_grad_(True)
+    work = MultiSphereImage(msi.layers.detach().float().clone().requires_grad_(True), msi.radii, msi.bounds, msi.center, msi.near_far, bg)
+    with torch.cuda.device(dev), torch.enable_grad():   # a caller's no_grad must not reach the loop's backward
+        opt = FusedAdam(list(work.parameters()), lr=lr, betas=(0.9, 0.99))
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        center = torch.from_numpy(msi.center).to(dev)   # once, before the loop: a copy from host memory waits for the stream
+        for _ in range(steps):
+            rays = headbox_rays(n, center, headbox, gen)
+            with torch.no_grad():
+                target = teacher(rays, is_train=False, need_alpha=False, **kw)[0]
+            loss = torch.mean((work.render(rays)[0] - target) ** 2)
+            loss.backward()
+            opt.step()
+            opt.zero_grad()
+            project_msi(work)
+            if isinstance(log, list):
+                log.append(loss.detach())
+    out_bg = None if bg is None else bg.detach().to(msi.layers.dtype)
+    return MultiSphereImage(work.layers.detach().to(msi.layers.dtype), msi.radii, msi.bounds, msi.center, msi.near_far, out_bg)

@@ -317,6 +317,25 @@ int ego_msi_layers(const float* z, const float* alpha, int32_t alpha_stride, con
 int ego_msi_render(const float* rays, int64_t N, float cx, float cy, float cz, const float* radii, int32_t L, int32_t Hm, int32_t Wm,
                    int32_t texel_type, const void* layers, const void* background, float* rgb, float* depth, void* stream);
 
+/* The backward of ego_msi_render for float32 texels (DESIGN.md 3.3 "Refinement"): g_rgb [N][3] = d loss / d rgb -> ADDED into g_layers
+ * [L][Hm][Wm][4] and g_background [Hm][Wm][4] (float32; the caller zeroes them; either may be NULL, not both).  The arguments up to `background` are
+ * ego_msi_render's; EGO_MSI_F16 is refused.  Per ray, over the live layers with T_k = prod_{j<k} (1 - A_j): dC_k = T_k g,
+ * dA_k = -T_k B_{k+1}, B_k = C_k.g + (1 - A_k) B_{k+1}, B_end = C_bg.g (0 without a background), dC_bg = T_end g, the background's alpha
+ * gets nothing; each goes to the four taps of the forward with the forward's weights.  Nothing divides by (1 - A_k): T_k of the forward
+ * walk is kept in `workspace` (ego_msi_render_backward_workspace_bytes(N, L) = 4 N L bytes, 4-byte aligned, the caller's), so everything
+ * behind a layer with A = 1 receives exactly 0.  A skipped layer receives nothing; depth, rays, radii and the centre have no gradient.
+ * The adds are float atomics: the sums depend on the order of arrival and are not bit-reproducible.  Four adjacent lanes add the four
+ * channels of one texel (values exchanged across the quad).  Hm Wm < 2^31.  N == 0 is a no-op; no host synchronisation; bad arguments
+ * return EGO_E_BADARG before anything is queued. */
+int64_t ego_msi_render_backward_workspace_bytes(int64_t N, int32_t L);
+int ego_msi_render_backward(const float* rays, int64_t N, float cx, float cy, float cz, const float* radii, int32_t L, int32_t Hm, int32_t Wm,
+                            int32_t texel_type, const void* layers, const void* background, const float* g_rgb, float* g_layers,
+                            float* g_background, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* In place on n_texels float32 texels (16-byte aligned): C <- max(C, 0), A <- clamp(A, 0, 1); a NaN becomes 0.  Run after every optimiser
+ * step on an image's texels, it keeps the transmittance of playback inside [0, 1]. */
+int ego_msi_project(float* texels, int64_t n_texels, void* stream);
+
 int ego_from_cartesian(const ego_scene* sc, const float* xyz, int64_t M, float* c7, void* stream);
 int ego_normalize_coord(const ego_scene* sc, const float* c7, int64_t M, float* c7n, void* stream);
 
