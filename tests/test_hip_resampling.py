@@ -138,7 +138,7 @@ DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "re
 
 def sample_pdf_digests():
     """case -> [sha256 of z_out's bytes, sha256 of z_new's bytes] for every shape above, u = NULL and hash-uniform u, use_coarse 0 and 1.
-    tools/capture_resample_digests.py records this from another build of the library."""
+    tools/capture_digests.py records this from another build of the library."""
     out = {}
     for Sc, n_fine in WAVE + WORKGROUP:
         z, w, u = make_inputs(Sc, n_fine)

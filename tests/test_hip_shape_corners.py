@@ -18,6 +18,9 @@ pinned to the reference at two corners by tests/golden/shape_corners.npz (oracle
 
 Measured on an MI355X, |HIP - f64| (|oracle f32 - f64|) per corner: the table of DESIGN.md 4.5."""
 import functools
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -296,6 +299,91 @@ def test_training_gradients_at_the_corners(name, scatter):
         hip_err = float((named[k].grad.cpu().double() - g64[k]).abs().max()) / scale
         assert hip_err <= B_GRAD or k in j.excused, (k, hip_err)
     j.finish(most_excused=len(named) // 2)
+
+
+# ---- the any-shape kernels bit for bit against a recorded build ---------------------------------------------------------------------
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "generic_digests.json")
+DIGEST_M = (3, 43)              # 129 samples: three 64-sample units, the last holding one lane
+DIGEST_BIG = 4097 * 64 + 1      # both kernels' unit loops take a second trip (grids of 2048 x 2 and 4096 waves)
+DIGEST_MODELS = {**{name: (name, {}, 160) for name in CORNERS}, "rgb_head": (None, dict(shadingMode="RGB", app_dim=3), 160),
+                 "in160 blocked dv": ("in160", {}, 0)}   # case -> (corner, SceneConfig keywords, ldv of the backward; 0 = the tuned scatters' blocked dv)
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def _digest_coords(cfg, M):
+    """stage_inputs' coordinates with the grid flag overridden: samples 0..63 yin, 64..127 yang, the rest as drawn (mixed).  A unit then
+    meets any_yang == false, one meets any_yin == false; with M = 129 the third unit holds one lane (its idle lanes repeat it), so the
+    unit that meets both grids is every later unit of the large case.  -> c7n [M][7], coords [M][4] (the sample's own grid's triple), dirs"""
+    q, dirs = stage_inputs(cfg, M)
+    q[:64, 6], q[64:128, 6] = 0.0, 1.0
+    g = q[:, 6] != 0
+    coords = torch.cat([torch.where(g[:, None], q[:, 3:6], q[:, 0:3]), q[:, 6:7]], -1).contiguous()
+    return q, coords, dirs
+
+
+def _train_pair_digests(model, cfg, N, S, ldx, ldh, ldv_fwd, ldv_bwd):
+    """ego_shade_train_generic, then ego_shade_backward_generic on its dumps, through the C ABI: the digest of every output buffer."""
+    from egonerf_amd import _lib
+    lib, st, M = _lib.load(), _lib.stream_handle(), N * S
+    sc = model.scene(training=True)
+    _, coords, _ = _digest_coords(cfg, M)
+    coords = coords.cuda()
+    rays = T(synth.make_rays(N, seed=SEED_RAYS)).cuda()
+    hid, mlp = model.head_hidden, cfg.shadingMode != "RGB"
+    z = lambda *shape: torch.zeros(*shape, device="cuda")
+    rgb, v = z(M, 3), z(M, ldv_fwd)
+    x, h1, h2 = (z(M, ldx), z(M, ldh), z(M, ldh)) if mlp else (None, None, None)
+    _lib.check(lib.ego_shade_train_generic(sc, rays.data_ptr(), coords.data_ptr(), N, S, rgb.data_ptr(), _lib.ptr(x), ldx, _lib.ptr(h1), _lib.ptr(h2), ldh,
+                                           v.data_ptr(), ldv_fwd, st), "ego_shade_train_generic")
+    dc = (T(synth.hash_uniform(96, 0, M * 3).reshape(M, 3).astype(np.float32)) - 0.5).cuda()
+    dh2, dh1 = (z(M, hid), z(M, hid)) if mlp else (None, None)
+    dfe, dv = z(M, 64), z(M, ldv_bwd) if ldv_bwd else z((M + 31) // 32 * 32, 144)
+    _lib.check(lib.ego_shade_backward_generic(sc, coords.data_ptr(), dc.data_ptr(), rgb.data_ptr(), _lib.ptr(x), ldx, _lib.ptr(h1), _lib.ptr(h2), ldh,
+                                              _lib.ptr(dh2), _lib.ptr(dh1), dfe.data_ptr(), dv.data_ptr(), ldv_bwd, N, S, st), "ego_shade_backward_generic")
+    torch.cuda.synchronize()
+    named = dict(rgb=rgb, x=x, h1=h1, h2=h2, v=v, dc=dc, dh2=dh2, dh1=dh1, dfe64=dfe, dv=dv)
+    return {k: _sha(t) for k, t in named.items() if t is not None}
+
+
+def generic_digests():
+    """case -> {buffer: sha256 of its bytes} for direct calls of the any-shape kernels: ego_shade_train_generic (rgb, x, h1, h2, v) and
+    ego_shade_backward_generic (dc, dh2, dh1, dfe64, dv) on 3 x 43 samples, compute_appfeature, renderModule and an eval forward with
+    n_coarse = 37 (rgb, depth, alpha), for the seven CORNERS, one shadingMode "RGB" model and in160 with the blocked dv (ldv = 0); and
+    the training pair once more on min_everything with 4097 x 64 + 1 samples (tight leading dimensions: every buffer under 100 MB).
+    ego_scatter_generic adds floats in arrival order and is left out.  tools/capture_digests.py records this from another build."""
+    out = {}
+    with torch.no_grad():
+        for case, (corner, kw, ldv_bwd) in DIGEST_MODELS.items():
+            cfg = _cfg(corner) if corner else synth.SceneConfig(n_voxel=20 ** 3, **kw)
+            model = make_model(cfg, _weights(cfg), "cuda")
+            assert not model.is_tuned_shape
+            ldx = (model.head_in_mlpC // 160 + 1) * 160
+            out[case] = d = _train_pair_digests(model, cfg, *DIGEST_M, ldx, 160, 160, ldv_bwd)
+            if ldv_bwd == 0:
+                continue   # the same model's stage ops and render are digested under its corner's name
+            q, _, dirs = _digest_coords(cfg, DIGEST_M[0] * DIGEST_M[1])
+            feat = model.compute_appfeature(q.cuda())
+            rgb, depth, _, _, alpha = model(_rays().cuda(), n_coarse=37, exp_sampling=True)
+            d.update(compute_appfeature=_sha(feat), renderModule=_sha(model.renderModule(None, dirs.cuda(), feat)), eval_rgb=_sha(rgb),
+                     eval_depth=_sha(depth), eval_alpha=_sha(alpha))
+        cfg = _cfg("min_everything")
+        model = make_model(cfg, _weights(cfg), "cuda")
+        out[f"min_everything M={DIGEST_BIG}"] = _train_pair_digests(model, cfg, DIGEST_BIG, 1, model.head_in_mlpC, model.head_hidden, 12, 12)
+    return out
+
+
+@pytest.mark.gpu
+def test_generic_bits_match_recorded():
+    """The head kernels have no atomics, so a rewrite that keeps their arithmetic returns the recorded build's bytes: equality, no
+    tolerance.  The fixture names the commit it was recorded from (never the tree under test)."""
+    recorded = json.load(open(DIGESTS))["digests"]
+    got = generic_digests()
+    assert len(got) == len(DIGEST_MODELS) + 1 == 10 and {c: sorted(d) for c, d in got.items()} == {c: sorted(d) for c, d in recorded.items()}
+    differs = [f"{case}: {name}" for case in got for name in got[case] if got[case][name] != recorded[case][name]]
+    assert not differs, differs
 
 
 @pytest.mark.gpu
