@@ -1,4 +1,4 @@
-// Multi-sphere images (include/egonerf_hip.h: ego_msi_layers, ego_msi_render, ego_msi_render_backward, ego_msi_project): a scene integrated once into L concentric
+// Multi-sphere images (include/egonerf_hip.h: ego_msi_layers, ego_msi_render, ego_msi_render_backward, ego_msi_project, ego_msi_adam_step): a scene integrated once into L concentric
 // shells of premultiplied RGBA around a centre, and views from nearby positions composited from the shells alone - L sphere
 // intersections, L bilinear taps and an "over" per pixel, no tables and no MLP.
 //
@@ -7,7 +7,10 @@
 // hot path: one thread per ray, wave64, no LDS; a tap is four loads of one whole texel (16 B float, 8 B half), neighbouring pixels hit
 // neighbouring texels, the radii are wave-uniform.  All arithmetic is fp32 and - like the whole library (-ffp-contract=off) and once more
 // by the pragma below - never contracted: tests/msi_ref.py restates both kernels operation by operation.  k_msi_render_bwd is playback's
-// backward for float32 texels (float atomic adds to the taps), k_msi_project the clamp that follows an optimiser step.
+// backward for float32 texels (float atomic adds to the taps), k_msi_project the clamp that follows an optimiser step, k_msi_adam an Adam step
+// of the texels a batch touched, clamp and zeroing of the gradient included.
+#include <algorithm>
+
 #include "ego_device.h"
 #include "ego_host.h"
 
@@ -276,12 +279,78 @@ __global__ __launch_bounds__(256) void k_msi_render_bwd(const float* __restrict_
   }
 }
 
-// in place: C <- max(C, 0), A <- clamp(A, 0, 1); a NaN becomes 0
+// C <- max(C, 0), A <- clamp(A, 0, 1); a NaN becomes 0.  The one clamp of k_msi_project and k_msi_adam: their bits agree
+__device__ __forceinline__ f32x4 msi_project_texel(const f32x4 v) {
+  return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fminf(fmaxf(v.w, 0.f), 1.f)};
+}
+
+// in place
 __global__ __launch_bounds__(256) void k_msi_project(float* __restrict__ texels, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const f32x4 v = load_texel(texels, i);
-  store_texel(texels, i, f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fminf(fmaxf(v.w, 0.f), 1.f)});
+  store_texel(texels, i, msi_project_texel(load_texel(texels, i)));
+}
+
+// ---- Adam on every texel's own clock (DESIGN.md 3.3 "Texel Adam") -------------------------------------------------------------------
+// One lane per texel, a streaming pass over the gradient: 16 B per lane, and a lane whose four gradient values all compare equal to 0
+// is done - it reads and writes nothing else.  A touched lane (a NaN compares unequal: touched) advances the texel's own step count,
+// its moments - m and v of one texel in one 32-byte record, so that a scattered hit opens one line for them, not two - and the texel,
+// torch.optim.Adam's rule in its order with the bias corrections read from a table at the texel's count.  No atomics, no LDS: a texel
+// belongs to one lane, the result does not depend on the schedule.
+struct TexelAdam {
+  float lr, b1, b2, c1, c2, eps;   // c1 = 1 - b1, c2 = 1 - b2, rounded once
+  const f32x2* bias;               // [n_bias]: {1 - b1^t, sqrt(1 - b2^t)} at t - 1
+  int n_bias, flags;
+};
+
+// one channel: the moments, then the step; float32, every operation rounded on its own
+__device__ __forceinline__ float adam_m(const TexelAdam& a, float m, float g) { return a.b1 * m + a.c1 * g; }
+__device__ __forceinline__ float adam_v(const TexelAdam& a, float v, float g) { return a.b2 * v + (a.c2 * g) * g; }
+__device__ __forceinline__ float adam_p(const TexelAdam& a, float p, float m, float v, float step, float root) {
+  return p - (step * m) / (__fsqrt_rn(v) / root + a.eps);
+}
+
+__device__ __forceinline__ void adam_texel(const TexelAdam& a, float* __restrict__ texels, float* __restrict__ grad,
+                                           float* __restrict__ moments, int* __restrict__ hits, int64_t i, const f32x4 g) {
+  const int h = hits[i];
+  const int t = h == 0x7fffffff ? h : h + 1;   // saturating
+  hits[i] = t;
+  const f32x2 c = a.bias[max(min(t, a.n_bias), 1) - 1];   // t >= 1 unless the caller's counts were negative: the read stays in the table
+  const float step = a.lr / c.x;
+  const f32x4 m0 = load_texel(moments, 2 * i), v0 = load_texel(moments, 2 * i + 1), p0 = load_texel(texels, i);
+  const f32x4 m{adam_m(a, m0.x, g.x), adam_m(a, m0.y, g.y), adam_m(a, m0.z, g.z), adam_m(a, m0.w, g.w)};
+  const f32x4 v{adam_v(a, v0.x, g.x), adam_v(a, v0.y, g.y), adam_v(a, v0.z, g.z), adam_v(a, v0.w, g.w)};
+  const f32x4 p{adam_p(a, p0.x, m.x, v.x, step, c.y), adam_p(a, p0.y, m.y, v.y, step, c.y), adam_p(a, p0.z, m.z, v.z, step, c.y),
+                adam_p(a, p0.w, m.w, v.w, step, c.y)};
+  store_texel(moments, 2 * i, m);
+  store_texel(moments, 2 * i + 1, v);
+  store_texel(texels, i, (a.flags & EGO_TEXEL_ADAM_PROJECT) ? msi_project_texel(p) : p);
+  if (a.flags & EGO_TEXEL_ADAM_ZERO_GRAD) store_texel(grad, i, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
+// A lane takes texels i, i + stride, ...; the gradients of ADAM_AHEAD of them are loaded before the first is looked at, so that a
+// wave has 4 KiB of gradient in flight, not 1.  A lane past the end holds a zero gradient: untouched.  The depth matters little
+// (DESIGN.md 3.3 holds the figures of experiment builds with 1, 4 and 8; such a build edits the constant below: the project keeps
+// no switch for an experiment in its kernel sources).  With at most 2048 workgroups the stride is 524288 texels: images of up to that many
+// texels only ever use the first of the ADAM_AHEAD bodies, a 1024 x 2048 layer stack uses all of them over many rounds.
+constexpr int ADAM_AHEAD = 4;
+constexpr int ADAM_MAX_BLOCKS = 2048;   // a memory-bound pass: 8 workgroups per CU, the rest by the stride
+__global__ __launch_bounds__(256) void k_msi_adam(float* __restrict__ texels, float* __restrict__ grad, float* __restrict__ moments,
+                                                  int* __restrict__ hits, int64_t n, const TexelAdam a) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x; first < n; first += ADAM_AHEAD * stride) {
+    f32x4 g[ADAM_AHEAD];
+#pragma unroll
+    for (int j = 0; j < ADAM_AHEAD; ++j) {
+      const int64_t i = first + j * stride;
+      g[j] = i < n ? load_texel(grad, i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int j = 0; j < ADAM_AHEAD; ++j) {
+      if (g[j].x == 0.f && g[j].y == 0.f && g[j].z == 0.f && g[j].w == 0.f) continue;
+      adam_texel(a, texels, grad, moments, hits, first + j * stride, g[j]);
+    }
+  }
 }
 
 }  // namespace
@@ -364,6 +433,28 @@ int ego_msi_project(float* texels, int64_t n_texels, void* stream) {
   EGO_REQUIRE(((uintptr_t)texels & 15) == 0, "msi_project: texels must be aligned to one texel (16 B float)");
   k_msi_project<<<nblk(n_texels, 256), 256, 0, (hipStream_t)stream>>>(texels, n_texels);
   return ego_launch_status("k_msi_project");
+}
+
+int ego_msi_adam_step(float* texels, float* grad, float* moments, int32_t* hits, int64_t n_texels, float lr, float beta1, float beta2,
+                      float eps, const float* bias, int32_t n_bias, int32_t flags, void* stream) {
+  EGO_TRACE("ego_msi_adam_step");
+  // the strided launch itself has no limit; the bound is ego_msi_project's, so that the two entry points take the same tensors
+  EGO_REQUIRE(n_texels >= 0 && n_texels < (1ll << 31) * 256, "msi_adam_step: n_texels < 0 or too large (2^39 texels, ego_msi_project's limit)");
+  EGO_REQUIRE((flags & ~(EGO_TEXEL_ADAM_PROJECT | EGO_TEXEL_ADAM_ZERO_GRAD)) == 0, "msi_adam_step: unknown flag bits");
+  EGO_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "msi_adam_step: betas must lie in [0, 1)");
+  EGO_REQUIRE(eps > 0.f, "msi_adam_step: eps must be positive");
+  EGO_REQUIRE(n_bias >= 1, "msi_adam_step: n_bias < 1");
+  if (n_texels == 0) return EGO_OK;
+  EGO_REQUIRE(texels && grad && moments && hits && bias, "msi_adam_step: null argument");
+  EGO_REQUIRE(((uintptr_t)texels & 15) == 0 && ((uintptr_t)grad & 15) == 0 && ((uintptr_t)moments & 15) == 0 && ((uintptr_t)hits & 3) == 0 &&
+                  ((uintptr_t)bias & 7) == 0,
+              "msi_adam_step: texels, grad and moments must be aligned to one texel (16 B), hits to 4 B, bias to one entry (8 B)");
+  TexelAdam a;
+  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.c1 = 1.f - beta1; a.c2 = 1.f - beta2; a.eps = eps;
+  a.bias = (const f32x2*)bias; a.n_bias = n_bias; a.flags = flags;
+  const unsigned blocks = (unsigned)std::min<int64_t>(nblk(n_texels, 256), ADAM_MAX_BLOCKS);
+  k_msi_adam<<<blocks, 256, 0, (hipStream_t)stream>>>(texels, grad, moments, hits, n_texels, a);
+  return ego_launch_status("k_msi_adam");
 }
 
 }  // extern "C"

@@ -316,7 +316,8 @@ DEFAULT_REFINE_LR = 1e-3
 
 
 def refine_msi(msi: MultiSphereImage, teacher, steps: int, rays_per_step: int = 65536, headbox: Optional[float] = None,
-               lr: float = DEFAULT_REFINE_LR, seed: int = 0, render_kwargs: Optional[dict] = None, log: Optional[list] = None) -> MultiSphereImage:
+               lr: float = DEFAULT_REFINE_LR, seed: int = 0, render_kwargs: Optional[dict] = None, log: Optional[list] = None,
+               optimizer: str = "dense") -> MultiSphereImage:
     """Optimises the texels of `msi` against `teacher` (a model, or anything called like one) on rays from inside a headbox; returns a
     new image of the input's texel type, radii, bounds, centre and near_far.
 
@@ -328,13 +329,25 @@ def refine_msi(msi: MultiSphereImage, teacher, steps: int, rays_per_step: int = 
 
     `lr`: Adam walks a texel by about 10 lr for every isolated hit, whatever the gradient's size, so the rate has to fit how often a
     texel is hit.  The default suits an image whose texels are hit in every step; a 1024 x 2048 image under 65536 rays per step
-    (a texel hit once in eight steps) needs 1e-5 to 3e-5 and is made worse by 1e-3 (profiles/r13/msi_refine.json)."""
+    (a texel hit once in eight steps) needs 1e-5 to 3e-5 and is made worse by 1e-3 (profiles/r13/msi_refine.json).
+
+    `optimizer`: "dense" (the default) is the loop above.  "texel" steps only the texels a batch hit, each on its own clock
+    (`optim.TexelAdam`, ego_msi_adam_step): the image is projected once before the loop; per step the same rays, target and loss, the
+    loss's gradient `(rgb - target) 2 / (3 N)` handed straight to ego_msi_render_backward, which adds into gradient buffers allocated
+    and zeroed once, and one fused step that updates, projects and re-zeroes exactly the texels that received a gradient - no autograd,
+    no pass over the whole image to zero, step or project it.  An isolated hit then moves a texel by at most `lr` and is not walked
+    on.  Use "dense" when every texel is hit in (nearly) every step - a small image, many rays - where the two rules coincide and
+    "dense" is the loop the tests pin bit for bit; use "texel" when a step reaches a fraction of the texels, as a 1024 x 2048 image
+    under 65536 rays does.  Measured there (DESIGN.md 3.3 "Texel Adam", profiles/r16/msi_texel_adam.json) it takes a fifth off the
+    step and is 7 dB better than "dense" at 1e-3, but it does not change which rates work: 3e-5 to 1e-4 there, for either loop."""
     from .optim import FusedAdam
     steps, n = int(steps), int(rays_per_step)
     if steps < 0 or n < 1:
         raise ValueError(f"refine_msi: steps must be >= 0 and rays_per_step >= 1, got {steps} and {n}")
     if not lr > 0:
         raise ValueError(f"refine_msi: lr must be positive, got {lr}")
+    if optimizer not in ("dense", "texel"):
+        raise ValueError(f'refine_msi: optimizer must be "dense" or "texel", got {optimizer!r}')
     r0 = float(msi.radii[0])
     headbox = 0.2 * r0 if headbox is None else float(headbox)
     if not 0 < headbox < r0:
@@ -342,6 +355,8 @@ def refine_msi(msi: MultiSphereImage, teacher, steps: int, rays_per_step: int = 
     if not msi.layers.is_cuda:
         raise ValueError("refine_msi: the image must live on a HIP device (the HIP path has no CPU fallback)")
     dev, kw = msi.device, dict(render_kwargs or {})
+    if optimizer == "texel":
+        return _refine_texel(msi, teacher, steps, n, headbox, lr, seed, kw, log)
     bg = None if msi.background is None else msi.background.detach().float().clone().requires_grad_(True)
     work = MultiSphereImage(msi.layers.detach().float().clone().requires_grad_(True), msi.radii, msi.bounds, msi.center, msi.near_far, bg)
     with torch.cuda.device(dev), torch.enable_grad():   # a caller's no_grad must not reach the loop's backward
@@ -361,3 +376,36 @@ def refine_msi(msi: MultiSphereImage, teacher, steps: int, rays_per_step: int = 
                 log.append(loss.detach())
     out_bg = None if bg is None else bg.detach().to(msi.layers.dtype)
     return MultiSphereImage(work.layers.detach().to(msi.layers.dtype), msi.radii, msi.bounds, msi.center, msi.near_far, out_bg)
+
+
+@torch.no_grad()
+def _refine_texel(msi: MultiSphereImage, teacher, steps: int, n: int, headbox: float, lr: float, seed: int, kw: dict,
+                  log: Optional[list]) -> MultiSphereImage:
+    """refine_msi's "texel" loop (arguments already checked): no autograd, nothing that sweeps the whole image inside the loop."""
+    from .optim import TexelAdam
+    dev = msi.device
+    bg = None if msi.background is None else msi.background.detach().float().clone()
+    work = MultiSphereImage(msi.layers.detach().float().clone(), msi.radii, msi.bounds, msi.center, msi.near_far, bg)
+    with torch.cuda.device(dev):
+        project_msi(work)   # once: from here on only stepped texels move, and the step projects them
+        params = list(work.parameters())
+        for p in params:
+            p.grad = torch.zeros_like(p)   # once: the step leaves them zero
+        g_bg = None if bg is None else bg.grad
+        opt = TexelAdam(params, lr=lr, betas=(0.9, 0.99), project=True, zero_grad=True)
+        opt.step()   # on the all-zero gradient: touches no texel and creates the state (a copy from host memory) outside the loop
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        center = torch.from_numpy(msi.center).to(dev)   # once, before the loop: a copy from host memory waits for the stream
+        scale = 2.0 / (3 * n)
+        for _ in range(steps):
+            rays = headbox_rays(n, center, headbox, gen)
+            target = teacher(rays, is_train=False, need_alpha=False, **kw)[0]
+            diff = work._render(rays, work.layers, work.background)[0] - target
+            work._render_backward(rays, work.layers, work.background, diff * scale, work.layers.grad, g_bg)
+            opt.step()
+            if isinstance(log, list):
+                log.append(torch.mean(diff ** 2))
+    out_bg = None if bg is None else bg.to(msi.layers.dtype)
+    for p in params:
+        p.grad = None
+    return MultiSphereImage(work.layers.to(msi.layers.dtype), msi.radii, msi.bounds, msi.center, msi.near_far, out_bg)

@@ -1,6 +1,9 @@
 """Multi-tensor Adam over `ego_adam_step` — a drop-in for the reference's `torch.optim.Adam(grad_vars, betas=(0.9, 0.99))`
 (train.py:182,186): same parameter groups (model.get_optparam_groups), same update rule, and `param_groups[i]["lr"]` stays
-writable so train.py:328-329's per-step exponential decay reads unchanged.  One launch updates all 33 tensors."""
+writable so train.py:328-329's per-step exponential decay reads unchanged.  One launch updates all 33 tensors.
+
+`TexelAdam` (not in the reference) is Adam for the texels of a multi-sphere image over `ego_msi_adam_step`: it steps only the texels
+a batch hit, each on its own clock."""
 from __future__ import annotations
 
 import torch
@@ -130,4 +133,109 @@ class FusedAdam(torch.optim.Optimizer):
         for (b1, b2, eps, step), ts in batches.items():
             arr = (_lib.AdamTensor * len(ts))(*ts)
             _lib.check(lib.ego_adam_step(arr, len(ts), b1, b2, eps, step, st), "ego_adam_step")
+        return loss
+
+
+BIAS_TABLE_CAP = 1 << 20
+
+
+def adam_bias_table(beta1: float, beta2: float):
+    """[n, 2] float32 numpy: entry t - 1 = {1 - beta1^t, sqrt(1 - beta2^t)}, evaluated in float64 and rounded once, for t = 1 .. n, where
+    n is the first t at which both entries round to 1.0f (from there on the corrections are the identity, and `ego_msi_adam_step` reads
+    the last entry), at most BIAS_TABLE_CAP."""
+    import numpy as np
+    b1, b2 = float(beta1), float(beta2)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"adam_bias_table: betas must lie in [0, 1), got {beta1}, {beta2}")
+    rows, t0, block = [], 1, 4096
+    while t0 <= BIAS_TABLE_CAP:
+        t = np.arange(t0, min(t0 + block, BIAS_TABLE_CAP + 1), dtype=np.float64)
+        rows.append(np.stack([1.0 - b1 ** t, np.sqrt(1.0 - b2 ** t)], axis=1).astype(np.float32))
+        done = np.flatnonzero((rows[-1] == np.float32(1.0)).all(axis=1))
+        if done.size:
+            rows[-1] = rows[-1][:done[0] + 1]
+            break
+        t0 += block
+    return np.ascontiguousarray(np.concatenate(rows))
+
+
+class TexelAdam(torch.optim.Optimizer):
+    """Adam that steps only the texels a batch hit (`ego_msi_adam_step`): for parameters of four-channel texels
+    (`MultiSphereImage.layers`, `.background`) of which a step's gradient reaches a fraction.  A texel whose four gradient values are all
+    0 is left alone - its value, its moments and its step count keep their bits - and every other texel takes torch.optim.Adam's step
+    on ITS OWN clock: the bias corrections of its t-th step at its t-th hit.  One isolated hit then moves a texel by lr g / (|g| + eps)
+    and nothing more, where dense Adam walks on for many steps on that hit's momentum.
+
+    Parameters: float32, contiguous, on a HIP device, last dimension 4; anything else raises.  `project=True` clamps every stepped texel
+    as `project_msi` does (colour >= 0, alpha in [0, 1]); `zero_grad=True` stores zeros over every gradient it consumed, so that the
+    gradient buffer is all zero after `step()` and can be accumulated into again without a pass that clears it.  The state - `moments`
+    [..., 2, 4] (m, then v, of a texel side by side), `hits` (int32, a texel's own step count), `bias` (the table of bias corrections)
+    and `bias_betas` (the betas it was built for: a step that finds other betas in its group builds the table anew, a copy from host
+    memory) - lives in `self.state` and round-trips through `state_dict` / `load_state_dict`.  There is no host step count:
+    `step()` does not synchronise and can be captured into a graph (after a first eager step has created the state)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, project=False, zero_grad=False):
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not eps > 0:
+            raise ValueError("TexelAdam: bad betas / eps")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, project=bool(project), zero_grad=bool(zero_grad)))
+        for group in self.param_groups:
+            for p in group["params"]:
+                self._check(p)
+
+    @staticmethod
+    def _check(p) -> None:
+        if p.dtype != torch.float32:
+            raise ValueError(f"TexelAdam: parameters must be float32, got {p.dtype}")
+        if p.dim() < 1 or p.shape[-1] != 4:
+            raise ValueError(f"TexelAdam: parameters are texels, their last dimension must be 4, got {tuple(p.shape)}")
+        if not p.is_contiguous():
+            raise ValueError("TexelAdam: parameters must be contiguous")
+        if not p.is_cuda:
+            raise ValueError("TexelAdam: parameters must live on a HIP device (the HIP path has no CPU fallback)")
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        # the base class casts every state tensor to its parameter's type: the counts are taken from the saved values again, as int32
+        saved_ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        params = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(saved_ids, params):
+            saved = state_dict["state"].get(i)
+            if saved is not None and "hits" in saved:
+                self.state[p]["hits"] = saved["hits"].to(device=p.device, dtype=torch.int32, copy=True)
+
+    @torch.no_grad()
+    @_lib.device_guard
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib, st = _lib.load(), _lib.stream_handle()
+        tables = {}   # (beta1, beta2, device) -> the table built in this call: parameters that ask for the same one share it
+        for group in self.param_groups:
+            b1, b2 = (float(b) for b in group["betas"])
+            flags = (_lib.TEXEL_ADAM_PROJECT if group["project"] else 0) | (_lib.TEXEL_ADAM_ZERO_GRAD if group["zero_grad"] else 0)
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                self._check(p)
+                if g.dtype != torch.float32 or g.shape != p.shape or not g.is_contiguous() or g.device != p.device:
+                    raise ValueError("TexelAdam: a gradient must be float32, contiguous and of its parameter's shape and device")
+                state = self.state[p]
+                if not state:
+                    state["moments"] = torch.zeros(*p.shape[:-1], 2, 4, device=p.device, dtype=torch.float32)
+                    state["hits"] = torch.zeros(p.shape[:-1], device=p.device, dtype=torch.int32)
+                if state.get("bias_betas") != (b1, b2):   # first step, or the group's betas were changed: the table follows them
+                    key = (b1, b2, p.device)
+                    if key not in tables:
+                        tables[key] = torch.from_numpy(adam_bias_table(b1, b2)).to(p.device)
+                    state["bias"], state["bias_betas"] = tables[key], (b1, b2)
+                bias = state["bias"]
+                _lib.check(lib.ego_msi_adam_step(p.data_ptr(), g.data_ptr(), state["moments"].data_ptr(), state["hits"].data_ptr(),
+                                                 p.numel() // 4, float(group["lr"]), b1, b2, float(group["eps"]), bias.data_ptr(),
+                                                 bias.shape[0], flags, st), "ego_msi_adam_step")
+                torch.autograd.graph.increment_version(p)   # written through a raw pointer: keep autograd / caches honest
+                if group["zero_grad"]:
+                    torch.autograd.graph.increment_version(g)
         return loss

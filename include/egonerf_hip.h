@@ -336,6 +336,22 @@ int ego_msi_render_backward(const float* rays, int64_t N, float cx, float cy, fl
  * step on an image's texels, it keeps the transmittance of playback inside [0, 1]. */
 int ego_msi_project(float* texels, int64_t n_texels, void* stream);
 
+/* Adam that steps only the texels a batch hit, each on its own clock (DESIGN.md 3.3 "Texel Adam"; append-only addition, EGO_ABI_VERSION
+ * stays 17).  texels and grad [n_texels][4] float32, moments [n_texels][2][4] float32 - m, then v, of one texel in one 32-byte record - all
+ * 16-byte aligned; hits [n_texels] int32: how many steps each texel has taken; bias [n_bias][2] float32, dev, 8-byte aligned: entry t - 1 is
+ * {1 - beta1^t, sqrt(1 - beta2^t)}, evaluated in float64 by the caller and rounded once.  A texel whose four gradient values all compare
+ * equal to 0 is UNTOUCHED: its texel, moments and count keep their bits, and it is not projected.  Every other texel (a NaN gradient
+ * included) takes, on all four channels, float32 without contraction: t = ++hits (saturating at 2^31 - 1); m = beta1 m + (1 - beta1) g;
+ * v = beta2 v + ((1 - beta2) g) g; c = bias[min(t, n_bias) - 1]; p = p - ((lr / c.x) m) / (sqrt(v) / c.y + eps) - torch.optim.Adam's rule
+ * and order at step t.  With EGO_TEXEL_ADAM_PROJECT the new texel is then clamped as ego_msi_project clamps (the same device function);
+ * with EGO_TEXEL_ADAM_ZERO_GRAD its gradient is stored as zeros, so that after the call no gradient value is non-zero, without a memset.
+ * One lane per texel, no atomics (bit-reproducible), no host synchronisation (capturable).  n_texels == 0 is a no-op; null or misaligned
+ * pointers, n_bias < 1, betas outside [0, 1), eps <= 0, unknown flag bits or n_texels >= 2^39 (ego_msi_project's limit; the strided
+ * launch here has none of its own) return EGO_E_BADARG before anything is queued. */
+enum { EGO_TEXEL_ADAM_PROJECT = 1, EGO_TEXEL_ADAM_ZERO_GRAD = 2 };
+int ego_msi_adam_step(float* texels, float* grad, float* moments, int32_t* hits, int64_t n_texels, float lr, float beta1, float beta2,
+                      float eps, const float* bias, int32_t n_bias, int32_t flags, void* stream);
+
 int ego_from_cartesian(const ego_scene* sc, const float* xyz, int64_t M, float* c7, void* stream);
 int ego_normalize_coord(const ego_scene* sc, const float* c7, int64_t M, float* c7n, void* stream);
 

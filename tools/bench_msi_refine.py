@@ -3,6 +3,7 @@
     python tools/bench_msi_refine.py                     # L = 16, 32 -> profiles/r13/msi_refine.json
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_msi_refine.py --child --L 32 --only times
     python tools/bench_msi_refine.py --trace DIR --L 32  # the playback kernels in that trace, into the JSON under `trace`
+    python tools/bench_msi_refine.py --optimizer texel   # the texel optimiser next to the dense one -> profiles/r16/msi_texel_adam.json
 
 The model, the bake (1024 x 2048, half texels), the frames and the PSNR are tools/bench_msi.py's: the `before` column repeats
 profiles/r11/msi.json's method.  One step = one process = one L, under a time limit of its own.
@@ -17,6 +18,13 @@ profiles/r11/msi.json's method.  One step = one process = one L, under a time li
     upper count).
 (b) PSNR of the 8-bit 1024 x 2048 ERP frame against the direct render's at eye offsets of 0, 5, 10 and 20 % of the innermost radius,
     before and after `refine_msi` with headbox = 0.2 x the innermost radius, for every learning rate of the sweep; same poses.
+`--optimizer texel` (the default `dense` is the record above, unchanged) measures `refine_msi(optimizer="texel")` against the dense loop
+in the same run.  (a) gains legs: `backward_texel_step`, the backward into persistent gradient buffers followed by the fused
+ego_msi_adam_step that projects and re-zeroes (the step consumes its gradient, so it cannot be repeated without a backward; the fused
+step's time is this leg minus `backward_quad`, and it stands against `zero_grad` + `adam` + `project`); `texel_step_keep_grad`, the
+fused step without re-zeroing on a gradient that stays (a lower bound: it lacks the 16-byte store per touched texel); `step_dense` and
+`step_texel`, one whole iteration of either loop, teacher included; and `touched_share`, the share of texels with a non-zero gradient
+after one backward.  (b) runs `texel` at `--lrs` (default 1e-3, 3e-4, 1e-4, 3e-5) and `dense` at `--dense-lrs` (default 1e-3, 3e-5).
 The first step that fails or runs out of time ends the run: nothing more is started, what was measured is written, the exit status is 1."""
 from __future__ import annotations
 
@@ -37,7 +45,8 @@ from bench_msi import CHUNK, DIRECT, ERP, OFFSETS, S, pose_at, psnr8   # noqa: E
 
 ATOMIC_RATE = 1.3e12   # bytes of float atomic adds per second, chip-wide
 LRS = (1e-3, 3e-3, 1e-2, 1e-4, 3e-5, 1e-5)   # the three rates the default was to be chosen from, then the sweep continued downwards
-OUR_KERNELS = re.compile(r"k_msi_(render_bwd\w*|render|project)")
+TEXEL_LRS, DENSE_LRS_BESIDE_TEXEL = (1e-3, 3e-4, 1e-4, 3e-5), (1e-3, 3e-5)
+OUR_KERNELS = re.compile(r"k_msi_(render_bwd\w*|render|project|adam)")
 
 
 def time_legs(legs: dict, reps: int, iters: int) -> dict:
@@ -57,7 +66,68 @@ def time_legs(legs: dict, reps: int, iters: int) -> dict:
     return {k: dict(median=float(np.median(v)), min=min(v), max=max(v), n=len(v)) for k, v in times.items()}
 
 
-def run_step(L: int, Hm: int, Wm: int, rays_per_step: int, steps: int, lrs, reps: int, iters: int, only: str) -> dict:
+def texel_legs(msi, model, work, rays, backward, headbox: float, rays_per_step: int) -> tuple:
+    """The legs `--optimizer texel` adds (module docstring) and the share of texels one backward touches."""
+    import torch
+    from egonerf_amd.msi import MultiSphereImage, headbox_rays, project_msi
+    from egonerf_amd.optim import FusedAdam, TexelAdam
+    dev = rays.device
+
+    def copy_of(image, requires_grad):
+        bg = None if image.background is None else image.background.detach().clone().requires_grad_(requires_grad)
+        return MultiSphereImage(image.layers.detach().clone().requires_grad_(requires_grad), msi.radii, msi.bounds, msi.center, msi.near_far, bg)
+
+    params = list(work.parameters())   # their .grad are the buffers `backward` adds into
+    for g in (p.grad for p in params):
+        g.zero_()
+    backward()
+    touched = sum(int((p.grad != 0).any(dim=-1).sum()) for p in params) / sum(p.numel() // 4 for p in params)
+    fused = TexelAdam(params, lr=1e-3, project=True, zero_grad=True)
+    kept = TexelAdam(params, lr=1e-3, project=True, zero_grad=False)
+    center = torch.from_numpy(msi.center).to(dev)
+    gen = torch.Generator(device=dev).manual_seed(2)
+    # one whole iteration of either loop, as refine_msi runs it
+    dense_work = copy_of(work, True)
+    dense_opt = FusedAdam(list(dense_work.parameters()), lr=1e-5, betas=(0.9, 0.99))
+    texel_work = copy_of(work, False)
+    for p in texel_work.parameters():
+        p.grad = torch.zeros_like(p)
+    texel_opt = TexelAdam(list(texel_work.parameters()), lr=1e-5, project=True, zero_grad=True)
+    texel_bg_grad = None if texel_work.background is None else texel_work.background.grad
+
+    def step_dense():
+        r = headbox_rays(rays_per_step, center, headbox, gen)
+        with torch.no_grad():
+            target = model(r, is_train=False, need_alpha=False, **DIRECT)[0]
+        with torch.enable_grad():
+            loss = torch.mean((dense_work.render(r)[0] - target) ** 2)
+            loss.backward()
+        dense_opt.step()
+        dense_opt.zero_grad()
+        project_msi(dense_work)
+
+    def step_texel():
+        with torch.no_grad():
+            r = headbox_rays(rays_per_step, center, headbox, gen)
+            target = model(r, is_train=False, need_alpha=False, **DIRECT)[0]
+            diff = texel_work._render(r, texel_work.layers, texel_work.background)[0] - target
+            texel_work._render_backward(r, texel_work.layers, texel_work.background, diff * (2.0 / (3 * rays_per_step)), texel_work.layers.grad,
+                                        texel_bg_grad)
+            texel_opt.step()
+            torch.mean(diff ** 2)
+
+    def backward_texel_step():
+        backward()
+        fused.step()
+
+    def refill():   # what `backward_texel_step` left zero, for the leg whose gradient stays
+        backward()
+
+    return dict(backward_texel_step=backward_texel_step, texel_step_keep_grad=kept.step, step_dense=step_dense, step_texel=step_texel), touched, refill
+
+
+def run_step(L: int, Hm: int, Wm: int, rays_per_step: int, steps: int, lrs, reps: int, iters: int, only: str, optimizer: str = "dense",
+             dense_lrs=()) -> dict:
     import torch
     from egonerf_amd import synth
     from egonerf_amd.camera import FrameRenderer
@@ -97,7 +167,23 @@ def run_step(L: int, Hm: int, Wm: int, rays_per_step: int, steps: int, lrs, reps
                     forward=no_grad(lambda: work.render(rays)),
                     backward_quad=backward,
                     zero_grad=no_grad(lambda: [g.zero_() for g in grads]), adam=opt.step, project=lambda: project_msi(work))
+        if optimizer == "texel":
+            more, out["touched_share"], refill = texel_legs(msi, model, work, rays, backward, headbox, rays_per_step)
+            legs.update(more)
+            keep = legs.pop("texel_step_keep_grad")   # in a pass of its own: the other legs zero or overwrite the gradient it needs
         ms = time_legs(legs, reps, iters)
+        if optimizer == "texel":
+            for g in grads:
+                g.zero_()
+            refill()
+            ms.update(time_legs(dict(texel_step_keep_grad=keep), reps, iters))
+            dense_sum = ms["zero_grad"]["median"] + ms["adam"]["median"] + ms["project"]["median"]
+            fused_ms = ms["backward_texel_step"]["median"] - ms["backward_quad"]["median"]
+            out["dense_update_ms"], out["fused_update_ms"] = dense_sum, fused_ms
+            out["fused_update_spread_ms"] = sum(ms[k]["max"] - ms[k]["min"] for k in ("backward_texel_step", "backward_quad"))   # of a difference
+            out["dense_update_spread_ms"] = sum(ms[k]["max"] - ms[k]["min"] for k in ("zero_grad", "adam", "project"))
+            del more, keep, refill
+        legs.clear()
         added = rays_per_step * (L * 64 + (48 if g_bg is not None else 0))
         floor_ms = added / ATOMIC_RATE * 1e3
         out["ms_per_step_part"] = ms
@@ -118,16 +204,19 @@ def run_step(L: int, Hm: int, Wm: int, rays_per_step: int, steps: int, lrs, reps
 
         out["psnr_db_before"] = psnr(msi)
         out["refined"] = []
-        for lr in lrs:
+        runs = [(optimizer, lr) for lr in lrs] + ([("dense", lr) for lr in dense_lrs] if optimizer == "texel" else [])
+        for which, lr in runs:
             log = []
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            refined = refine_msi(msi, model, steps, rays_per_step=rays_per_step, headbox=headbox, lr=lr, seed=0, render_kwargs=DIRECT, log=log)
+            extra = dict(optimizer=which) if optimizer == "texel" else {}   # the default call is the r13 record's, as it was
+            refined = refine_msi(msi, model, steps, rays_per_step=rays_per_step, headbox=headbox, lr=lr, seed=0, render_kwargs=DIRECT, log=log,
+                                 **extra)
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
             losses = torch.stack(log).cpu().numpy() if log else np.zeros(0)
             k = max(1, len(losses) // 20)
-            out["refined"].append(dict(lr=lr, steps=steps, ms_per_step=wall / max(steps, 1) * 1e3, psnr_db=psnr(refined),
+            out["refined"].append(dict(**extra, lr=lr, steps=steps, ms_per_step=wall / max(steps, 1) * 1e3, psnr_db=psnr(refined),
                                        loss_first=float(losses[:k].mean()) if len(losses) else None,
                                        loss_last=float(losses[-k:].mean()) if len(losses) else None))
             del refined
@@ -161,18 +250,25 @@ def main() -> int:
     ap.add_argument("--msi", type=int, nargs=2, default=[1024, 2048], metavar=("HM", "WM"))
     ap.add_argument("--rays", type=int, default=65536, help="rays per refinement step")
     ap.add_argument("--steps", type=int, default=1000, help="refinement steps per learning rate")
-    ap.add_argument("--lrs", type=float, nargs="+", default=list(LRS))
+    ap.add_argument("--lrs", type=float, nargs="+", help=f"default: {LRS}, with --optimizer texel {TEXEL_LRS}")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20, help="calls per leg and repetition")
     ap.add_argument("--step-timeout", type=int, default=400, help="seconds per step (a process of its own)")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "r13", "msi_refine.json"))
+    ap.add_argument("--optimizer", default="dense", choices=["dense", "texel"],
+                    help="dense: today's loop, the r13 record; texel: refine_msi(optimizer='texel') next to the dense loop in one run")
+    ap.add_argument("--dense-lrs", type=float, nargs="+", default=list(DENSE_LRS_BESIDE_TEXEL), help="with --optimizer texel: the dense loop's rates")
+    ap.add_argument("--out", help="default: profiles/r13/msi_refine.json, with --optimizer texel profiles/r16/msi_texel_adam.json")
     ap.add_argument("--only", default="all", choices=["all", "times", "quality"], help="the part to run: (a) times, (b) quality, or both")
     ap.add_argument("--trace", help="summarise the kernel statistics of a rocprofv3 run in this directory (into --out, key `trace`) and exit")
     ap.add_argument("--child", action="store_true", help="run one step (the first --L) in this process and print the result")
     a = ap.parse_args()
+    texel = a.optimizer == "texel"
+    a.lrs = a.lrs or list(TEXEL_LRS if texel else LRS)
+    a.out = a.out or os.path.join(HERE, "profiles", *(("r16", "msi_texel_adam.json") if texel else ("r13", "msi_refine.json")))
     if a.child:
         sys.path.insert(0, HERE)
-        print("RESULT " + json.dumps(run_step(a.L[0], a.msi[0], a.msi[1], a.rays, a.steps, a.lrs, a.reps, a.iters, a.only)), flush=True)
+        print("RESULT " + json.dumps(run_step(a.L[0], a.msi[0], a.msi[1], a.rays, a.steps, a.lrs, a.reps, a.iters, a.only,
+                                                  a.optimizer, a.dense_lrs)), flush=True)
         return 0
     doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
     if a.trace:
@@ -183,6 +279,8 @@ def main() -> int:
         for L in a.L:
             cmd = [sys.executable, os.path.abspath(__file__), "--child", "--L", str(L), "--msi", str(a.msi[0]), str(a.msi[1]), "--rays", str(a.rays),
                    "--steps", str(a.steps), "--reps", str(a.reps), "--iters", str(a.iters), "--only", a.only, "--lrs", *[repr(v) for v in a.lrs]]
+            if texel:
+                cmd += ["--optimizer", "texel", "--dense-lrs", *[repr(v) for v in a.dense_lrs]]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
             except subprocess.TimeoutExpired:
@@ -197,14 +295,21 @@ def main() -> int:
             if "ms_per_step_part" in res:
                 ms = {k: round(v["median"], 3) for k, v in res["ms_per_step_part"].items()}
                 print(f"L {L:3d}: ms {ms}; atomic floor {res['atomic_floor_ms']:.3f} ms", flush=True)
+            if "touched_share" in res:
+                print(f"L {L:3d}: touched share {res['touched_share']:.4f}; update: dense {res['dense_update_ms']:.3f} ms "
+                      f"(spread {res['dense_update_spread_ms']:.3f}), fused {res['fused_update_ms']:.3f} ms (spread {res['fused_update_spread_ms']:.3f})",
+                      flush=True)
             if "psnr_db_before" in res:
                 print(f"L {L:3d}: psnr before {res['psnr_db_before']}", flush=True)
             for row in res.get("refined", []):
-                print(f"       lr {row['lr']:g}, {row['steps']} steps ({row['ms_per_step']:.2f} ms each): psnr {row['psnr_db']}; "
+                print(f"       {row.get('optimizer', 'dense')} lr {row['lr']:g}, {row['steps']} steps ({row['ms_per_step']:.2f} ms each): psnr {row['psnr_db']}; "
                       f"loss {row['loss_first']:.3e} -> {row['loss_last']:.3e}", flush=True)
         moved = [k for k in (f"{f:.2f}" for f in OFFSETS) if k != "0.00"]
-        gain = {repr(lr): float(np.mean([row["psnr_db"][k] - res["psnr_db_before"][k] for res in steps for row in res["refined"]
-                                         if row["lr"] == lr for k in moved])) for lr in a.lrs} if steps and a.only != "times" else {}
+        runs = [("dense", lr) for lr in a.lrs] if not texel else [("texel", lr) for lr in a.lrs] + [("dense", lr) for lr in a.dense_lrs]
+        gain = {(f"{which} " if texel else "") + repr(lr): float(np.mean([row["psnr_db"][k] - res["psnr_db_before"][k] for res in steps
+                                                                         for row in res["refined"]
+                                                                         if row["lr"] == lr and row.get("optimizer", "dense") == which for k in moved]))
+                for which, lr in runs} if steps and a.only != "times" else {}
         doc.update(tool="tools/bench_msi_refine.py", samples=S, direct=DIRECT, frame_erp=list(ERP), chunk=CHUNK,
                    offsets_of_innermost_radius=list(OFFSETS), atomic_rate_bytes_per_s=ATOMIC_RATE, reps=a.reps, calls_per_rep=a.iters, failed=failed)
         doc.update(steps=steps, mean_psnr_gain_db_off_centre=gain)
