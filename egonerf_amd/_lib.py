@@ -64,7 +64,7 @@ class VmGrad(C.Structure):
 
 
 def grad_struct(tensors) -> VmGrad:
-    """tensors: [plane_yin x3, line_yin x3, plane_yang x3, line_yang x3] gradient tables (channel-last memory)."""
+    """tensors: the 12 gradient tables of a field in field_tables.tables order (channel-last memory)."""
     g = VmGrad()
     for gi in range(2):
         for i in range(3):

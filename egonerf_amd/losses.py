@@ -22,7 +22,7 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
 
 
 def _channel_last_ptr(p: torch.Tensor, what: str) -> int:
-    """Tables are (1, C, H, W) tensors whose memory is [H][W][C] (model._channel_last_param)."""
+    """Tables are (1, C, H, W) tensors whose memory is [H][W][C] (field_tables.carve_channel_last)."""
     if p.dim() != 4 or p.shape[0] != 1 or not p.permute(0, 2, 3, 1).is_contiguous() or p.dtype != torch.float32:
         raise RuntimeError(f"{what}: expected a float32 (1, C, H, W) table with channel-last memory")
     return p.data_ptr()

@@ -26,8 +26,9 @@ import numpy as np
 import torch
 import torch.nn
 
-from . import _lib
+from . import _lib, field_tables, stage_autograd
 from .coordinates import YinYangSphericalCoords, _require_cuda
+from .losses import table_regulariser
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]  # models/EgoNeRF.py:30-33
 VEC_MODE = [2, 1, 0]
@@ -48,35 +49,6 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().float()
 
 
-def _channel_last_param(C_: int, H: int, W: int, scale: float, device) -> torch.nn.Parameter:
-    """Reference-shaped (1,C,H,W) parameter whose memory is [H][W][C]."""
-    mem = torch.empty(1, H, W, C_, device=device, dtype=torch.float32)
-    mem.copy_(scale * torch.randn(1, C_, H, W).permute(0, 2, 3, 1))
-    return torch.nn.Parameter(mem.permute(0, 3, 1, 2))
-
-
-def _carve_channel_last(shapes, device, dtype=torch.float32) -> List[torch.Tensor]:
-    """One flat allocation carved into [1,H,W,C]-memory tables, returned as reference-shaped (1,C,H,W) views.  The tables of a
-    field come from one buffer so that the kernels can address every tap as `base + 32-bit byte offset` (csrc/ego_device.h
-    DevField; the library rejects a field whose tables span 4 GB or more).  Each table starts on a 256-byte boundary."""
-    esz = torch.empty((), dtype=dtype).element_size()
-    align = 256 // esz
-    offs, total = [], 0
-    for (C_, H, W) in shapes:
-        offs.append(total)
-        total += (C_ * H * W + align - 1) // align * align
-    flat = torch.empty(total, device=device, dtype=dtype)
-    return [flat[o:o + C_ * H * W].view(1, H, W, C_).permute(0, 3, 1, 2) for o, (C_, H, W) in zip(offs, shapes)]
-
-
-def _table_ptr(t: torch.Tensor) -> int:
-    """Device pointer of a (1,C,H,W) tensor after checking its memory really is [H][W][C]."""
-    if not t.permute(0, 2, 3, 1).is_contiguous():
-        raise RuntimeError(f"table of shape {tuple(t.shape)} / strides {t.stride()} is not channel-last; "
-                           "assign parameters with param.data.copy_(...) so the layout is kept")
-    return t.data_ptr()
-
-
 # ---------------------------------------------------------------------------------------------------
 # models/tensorBase.py
 # ---------------------------------------------------------------------------------------------------
@@ -86,10 +58,8 @@ def raw2alpha(sigma: torch.Tensor, dist: torch.Tensor):
     mode is on and either requires grad: the forward values are the same bits, the backward (stage_autograd.Raw2AlphaFunction) is the
     fp32-grade gradient of the reference function."""
     _require_cuda(sigma, "raw2alpha")
-    from .stage_autograd import needs_grad
-    if needs_grad(sigma, dist):
-        from .stage_autograd import Raw2AlphaFunction
-        return Raw2AlphaFunction.apply(sigma, dist)
+    if stage_autograd.needs_grad(sigma, dist):
+        return stage_autograd.Raw2AlphaFunction.apply(sigma, dist)
     return _raw2alpha(sigma, dist)
 
 
@@ -149,10 +119,8 @@ def SHRender(xyz_sampled, viewdirs: torch.Tensor, features: torch.Tensor) -> tor
     function only.)  Differentiable (to viewdirs and features) when grad mode is on and either requires grad: same forward bits,
     fp32-grade backward (stage_autograd.SHRenderFunction)."""
     _require_cuda(viewdirs, "SHRender")
-    from .stage_autograd import needs_grad
-    if needs_grad(viewdirs, features):
-        from .stage_autograd import SHRenderFunction
-        return SHRenderFunction.apply(viewdirs, features)
+    if stage_autograd.needs_grad(viewdirs, features):
+        return stage_autograd.SHRenderFunction.apply(viewdirs, features)
     return _sh_render(viewdirs, features)
 
 
@@ -372,6 +340,19 @@ class YinYangAlphaGridMask(torch.nn.Module):
         return out
 
 
+class _SceneEntry:
+    """EgoNeRF's one cached ego_scene struct, with everything the struct points to that nobody else keeps alive."""
+
+    def __init__(self, blobs=None, app16=None):
+        self.key = None      # EgoNeRF._scene_key() the struct was built for; None: nothing cached
+        self.struct = None
+        self.holds = ()      # detached MLP / basis weights behind mlp_w, mlp_b, basis
+        self.luts = ()       # the radius LUTs behind r_lut, r_lut_fine
+        self.mask = None     # model.alphaMask at build time: its packed() / cell_or() buffers are behind occ, occ_cell
+        self.blobs = {} if blobs is None else blobs   # {training: packed MLP / basis image}; outlives an invalidation
+        self.app16 = app16   # (appearance table versions, [12 half tables]) behind app16; outlives an invalidation
+
+
 class EgoNeRF(TensorBase):
     supports_need_alpha = True  # forward(..., need_alpha=False): see volume_renderer(keep_alpha=False)
     supports_marched_event = True  # forward(..., marched_event=ev): see renderer._render_to_host
@@ -380,13 +361,12 @@ class EgoNeRF(TensorBase):
         assert isinstance(coordinates, YinYangSphericalCoords), "EgoNeRF needs YinYangSphericalCoords (EgoNeRF.py:522)"
         self.matMode_yin = self.matMode_yang = MAT_MODE
         self.vecMode_yin = self.vecMode_yang = VEC_MODE
+        self._scene = _SceneEntry()
+        self._sched_cache = {}
         self.init_svd_volume(gridSize[0], device)
         if isinstance(self.renderModule, torch.nn.Module):
             self.renderModule._owner = _WeakOwner(self)
-        self._scene_cache = None
-        self._packed = None
-        self._packed_versions = None
-        self._sched_cache = {}
+        self._last_render = self._last_shaded = None   # see forward / last_shaded_samples
         # The sample distances [N, S] of the latest TRAINING render (train.render_train: the march's own buffer, no gradient): what
         # losses.distortion_loss needs next to the returned alpha.  Eval renders leave it alone.
         self.last_train_z = None
@@ -401,7 +381,6 @@ class EgoNeRF(TensorBase):
         # at construction) = the float-atomic scatters of rounds 1-4 (run-to-run differences of ~1e-6 of the largest gradient).
         self.deterministic_scatter = os.environ.get("EGO_SCATTER", "sorted") != "atomic"
         self._app_table_dtype = "f32"   # "f16": inference gathers appearance taps from a half-precision copy of the tables
-        self._app16 = None              # (versions, [12 half tensors])
         # opt-in skipping (EgoNeRF.forward itself evaluates every sample; TensorBase.forward's semantics, tensorBase.py:464-487,
         # pinned to the reference by tests/golden/skip_semantics.npz; see include/egonerf_hip.h):
         self.use_alpha_mask = False          # apply self.alphaMask with TensorBase.forward's semantics (sigma = 0 where empty)
@@ -412,8 +391,8 @@ class EgoNeRF(TensorBase):
         # surface the fp32 transmittance underflows to 0 within a few samples, so this is what early termination amounts to.
         # EGO_EXACT_SKIP=0 in the environment switches it off for A/B measurements.
         self.skip_zero_weight_tiles = os.environ.get("EGO_EXACT_SKIP", "1") != "0"
-        self.coarse_sigma_plane_yin, self.coarse_sigma_line_yin = [None] * 3, [None] * 3
-        self.coarse_sigma_plane_yang, self.coarse_sigma_line_yang = [None] * 3, [None] * 3
+        for name in field_tables.list_names("density", coarse=True):
+            setattr(self, name, [None] * 3)
         if self.coarse_sigma_grid_update_rule is not None:
             if self.coarse_sigma_grid_update_rule != "conv":
                 raise NotImplementedError  # EgoNeRF.py:92-94
@@ -430,70 +409,23 @@ class EgoNeRF(TensorBase):
                 shapes.append((n_component[i], gridSize[m1], gridSize[m0]))
             for i in range(3):
                 shapes.append((n_component[i], gridSize[VEC_MODE[i]], 1))
-        views = _carve_channel_last(shapes, device)   # [plane x3, line x3] yin, then yang: one buffer per field
+        views = field_tables.carve_channel_last(shapes, device)   # field_tables' order, four lists of three: one buffer per field
         for v, (C_, H, W) in zip(views, shapes):
             v.copy_(scale * torch.randn(1, C_, H, W))
-        params = [torch.nn.Parameter(v) for v in views]
-        return [torch.nn.ParameterList(params[0:3]), torch.nn.ParameterList(params[3:6]),
-                torch.nn.ParameterList(params[6:9]), torch.nn.ParameterList(params[9:12])]
-
-    @torch.no_grad()
-    def _reflatten_tables(self, kind: str):
-        """Move the 12 tables of `kind` ("density" | "app") into one fresh buffer (after they were replaced one by one, e.g. by
-        upsample_volume_grid): new Parameters, so an optimiser must be rebuilt afterwards (the reference does, train.py:380)."""
-        lists = [getattr(self, f"{kind}_{what}_{g}") for g in ("yin", "yang") for what in ("plane", "line")]
-        olds = [p for l in lists for p in l]
-        views = _carve_channel_last([(p.shape[1], p.shape[2], p.shape[3]) for p in olds], olds[0].device)
-        for v, p in zip(views, olds):
-            v.copy_(p.data)
-        k = 0
-        for l in lists:
-            for i in range(len(l)):
-                l[i] = torch.nn.Parameter(views[k], requires_grad=olds[k].requires_grad)
-                k += 1
-        self._scene_cache = None
-
-    # -- compact addressing guard -----------------------------------------------------------------------------
-    def _table_lists(self, kind: str):
-        return [getattr(self, f"{kind}_{what}_{g}") for g in ("yin", "yang") for what in ("plane", "line")]
-
-    def _is_compact(self, kind: str) -> bool:
-        """True iff the 12 tables of `kind` end within 4 GB of the lowest of them (what csrc/ego_device.h's 32-bit tap offsets
-        need; ego_field_is_compact is the library's own check)."""
-        ts = [p for l in self._table_lists(kind) for p in l]
-        lo = min(t.data_ptr() for t in ts)
-        hi = max(t.data_ptr() + t.numel() * t.element_size() for t in ts)
-        return hi - lo < (1 << 32)
-
-    @torch.no_grad()
-    def _recompact_tables(self, kind: str):
-        """Move the 12 tables of `kind` into one fresh buffer IN PLACE (`param.data = view`): the Parameter objects - and with
-        them an optimiser's references and state - stay.  Needed after anything that re-allocates the parameters one by one
-        (`Module._apply`: .to() / .cuda() / .float(); `load_state_dict(assign=True)`): separate hipMalloc segments of this size
-        have no bounded distance, and the forward gathers address a tap as base + 32-bit offset."""
-        olds = [p for l in self._table_lists(kind) for p in l]
-        views = _carve_channel_last([(p.shape[1], p.shape[2], p.shape[3]) for p in olds], olds[0].device)
-        for v, p in zip(views, olds):
-            v.copy_(p.data)
-            p.data = v
-        self._scene_cache = None
+        return [torch.nn.ParameterList([torch.nn.Parameter(v) for v in views[k:k + 3]]) for k in range(0, 12, 3)]
 
     def _apply(self, fn, *args, **kwargs):
         """nn.Module._apply re-allocates every parameter on its own; restore what the kernels rely on afterwards: one buffer per
         field (compact addressing), the non-parameter device state (pooled density tables, packed weights, half copies) on
         the new device."""
         r = super()._apply(fn, *args, **kwargs)
-        self._scene_cache = None
-        self._packed = self._packed_versions = self._app16 = None
+        self.invalidate_scene(moved=True)
         self._sched_cache = {}
-        if not hasattr(self, "density_plane_yin"):   # called from inside __init__ (renderModule.to(device)) before the tables exist
-            return r
-        dev = self.density_plane_yin[0].device
-        self.device = dev
+        dev = self.device = self.density_plane_yin[0].device
         if dev.type == "cuda":
             for kind in ("density", "app"):
-                if not self._is_compact(kind):
-                    self._recompact_tables(kind)
+                if not field_tables.is_compact(field_tables.tables(self, kind)):
+                    field_tables.recarve(self, kind, keep_parameters=True)
             stale = self.coarse_sigma_plane_yin[0] is None or self.coarse_sigma_plane_yin[0].device != dev
             if self.coarse_sigma_grid_update_rule == "conv" and stale:
                 self.update_coarse_sigma_grid()
@@ -501,10 +433,9 @@ class EgoNeRF(TensorBase):
 
     def init_svd_volume(self, res, device):
         g = self.gridSize.tolist()
-        (self.density_plane_yin, self.density_line_yin, self.density_plane_yang,
-         self.density_line_yang) = self.init_one_svd(self.density_n_comp, g, 0.1, device)
-        (self.app_plane_yin, self.app_line_yin, self.app_plane_yang,
-         self.app_line_yang) = self.init_one_svd(self.app_n_comp, g, 0.1, device)
+        for kind, n_comp in (("density", self.density_n_comp), ("app", self.app_n_comp)):
+            for name, plist in zip(field_tables.list_names(kind), self.init_one_svd(n_comp, g, 0.1, device)):
+                setattr(self, name, plist)
         self.basis_mat_yin = torch.nn.Linear(sum(self.app_n_comp), self.app_dim, bias=False).to(device)
         self.basis_mat_yang = torch.nn.Linear(sum(self.app_n_comp), self.app_dim, bias=False).to(device)
 
@@ -526,25 +457,21 @@ class EgoNeRF(TensorBase):
     # -- regularisers (train.py:289-304) ----------------------------------------------------------------------
     def vectorDiffs(self, vector_comps):
         """EgoNeRF.py:189-196: sum over line tables of mean |off-diagonal of the component Gram matrix|."""
-        from .losses import table_regulariser
         return table_regulariser("ortho", list(vector_comps), [1.0] * len(vector_comps))
 
     def vector_comp_diffs(self):
         """EgoNeRF.py:198-199."""
-        from .losses import table_regulariser
         lines = (list(self.density_line_yin) + list(self.app_line_yin) + list(self.density_line_yang) + list(self.app_line_yang))
         return table_regulariser("ortho", lines, [1.0] * len(lines))
 
     def density_L1(self):
         """EgoNeRF.py:206-212."""
-        from .losses import table_regulariser
         t = []
         for i in range(len(self.density_plane_yin)):
             t += [self.density_plane_yin[i], self.density_line_yin[i], self.density_plane_yang[i], self.density_line_yang[i]]
         return table_regulariser("l1", t, [1.0] * len(t))
 
     def _tv(self, reg, planes):
-        from .losses import table_regulariser
         w = float(getattr(reg, "TVLoss_weight", 1.0))
         return table_regulariser("tv", planes, [1e-2 * w] * len(planes))
 
@@ -570,14 +497,13 @@ class EgoNeRF(TensorBase):
     def upsample_volume_grid(self, res_target):
         """EgoNeRF.py:428-435.  The caller then calls coordinates.set_resolution(res_target) (train.py:376-377; note that
         call resets r0 to 0.05 unless r0 is passed) and rebuilds the optimiser."""
-        self.app_plane_yin, self.app_line_yin = self.up_sampling_VM(self.app_plane_yin, self.app_line_yin, res_target)
-        self.density_plane_yin, self.density_line_yin = self.up_sampling_VM(self.density_plane_yin, self.density_line_yin, res_target)
-        self.app_plane_yang, self.app_line_yang = self.up_sampling_VM(self.app_plane_yang, self.app_line_yang, res_target)
-        self.density_plane_yang, self.density_line_yang = self.up_sampling_VM(self.density_plane_yang, self.density_line_yang, res_target)
-        self._reflatten_tables("app")
-        self._reflatten_tables("density")
+        for g in ("yin", "yang"):   # the reference's order: app yin, density yin, app yang, density yang (tables replaced in their lists)
+            for kind in ("app", "density"):
+                self.up_sampling_VM(getattr(self, f"{kind}_plane_{g}"), getattr(self, f"{kind}_line_{g}"), res_target)
+        field_tables.recarve(self, "app", keep_parameters=False)
+        field_tables.recarve(self, "density", keep_parameters=False)
         self.update_stepSize(res_target)
-        self._scene_cache = None
+        self.invalidate_scene()
         print(f"upsamping to {res_target}")
 
     @torch.no_grad()
@@ -587,32 +513,25 @@ class EgoNeRF(TensorBase):
         if self.coarse_sigma_grid_update_rule != "conv":
             raise NotImplementedError
         st = _lib.stream_handle()
-        srcs = [(g, what, i, getattr(self, f"density_{what}_{g}")[i]) for g in ("yin", "yang") for what in ("plane", "line") for i in range(3)]
-        for *_k, src in srcs:
+        srcs = field_tables.tables(self, "density")
+        for src in srcs:
             _require_cuda(src, "update_coarse_sigma_grid")
-        shapes = [(src.shape[1], src.shape[2] // 2, 1 if src.shape[3] == 1 else src.shape[3] // 2) for *_k, src in srcs]
+        shapes = [(src.shape[1], src.shape[2] // 2, 1 if src.shape[3] == 1 else src.shape[3] // 2) for src in srcs]
         # The pooled tables are refreshed IN PLACE while their shapes stand (every training step, train.py:356-357): no allocation
         # per step, the scene struct stays valid, and a captured hipGraph of the iteration reads on replay k + 1 what replay k wrote
-        # (freshly allocated tables would be invisible to the already captured forward).
-        cur = [getattr(self, f"coarse_sigma_{what}_{g}")[i] for (g, what, i, _src) in srcs]
-        same = all(c is not None and c.device == src.device and tuple(c.shape) == (1, C_, H, W)
-                   for c, (C_, H, W), (*_k, src) in zip(cur, shapes, srcs))
-        if same:
-            # ... and only while they still form ONE carved buffer: a caller may have assigned coarse_sigma_* one by one (separate
-            # allocations have no bounded distance, and the march addresses a tap as base + 32-bit offset: ADVICE r03)
-            lo = min(c.data_ptr() for c in cur)
-            hi = max(c.data_ptr() + c.numel() * c.element_size() for c in cur)
-            same = hi - lo < (1 << 32) and all(c.dtype == torch.float32 and c.permute(0, 2, 3, 1).is_contiguous() for c in cur)
+        # (freshly allocated tables would be invisible to the already captured forward) ...
+        cur = field_tables.tables(self, "density", coarse=True)
+        same = all(c is not None and c.device == src.device and tuple(c.shape) == (1, *shape) for c, shape, src in zip(cur, shapes, srcs))
+        # ... and only while they still form ONE carved buffer: a caller may have assigned coarse_sigma_* one by one (separate
+        # allocations have no bounded distance, and the march addresses a tap as base + 32-bit offset: ADVICE r03)
+        same = same and field_tables.is_compact(cur) and all(c.dtype == torch.float32 and c.permute(0, 2, 3, 1).is_contiguous() for c in cur)
         if not same:
-            dsts = _carve_channel_last(shapes, srcs[0][3].device)   # one buffer: compact addressing like the full tables
-            for (g, what, i, src), dst in zip(srcs, dsts):
-                getattr(self, f"coarse_sigma_{what}_{g}")[i] = dst
-            self._scene_cache = None
+            field_tables.assign(self, "density", field_tables.carve_channel_last(shapes, srcs[0].device), coarse=True)
+            self.invalidate_scene()
         # all 12 tables in one launch (this runs after every training step, train.py:356-357)
         fs, fd = _lib.VmField(), _lib.VmField()
-        res = [int(v) for v in self.gridSize.tolist()]
-        self._fill_field(fs, "density", self.density_n_comp, res)
-        self._fill_field(fd, "density", self.density_n_comp, [r // 2 for r in res], coarse=True)
+        self._fill_field(fs, "density")
+        self._fill_field(fd, "density", coarse=True)
         _call("ego_avgpool_field", C.byref(fs), C.byref(fd), st)
 
     @property
@@ -648,7 +567,7 @@ class EgoNeRF(TensorBase):
         if value not in ("f16x3", "f16f8", "f16f6", "f32"):
             raise ValueError("mlp_precision must be 'f16x3', 'f16f8', 'f16f6' or 'f32'")
         self._mlp_precision = value
-        self._scene_cache = None
+        self.invalidate_scene()
 
     @torch.no_grad()
     def check_mlp_precision(self, rays: torch.Tensor, **forward_kw) -> dict:
@@ -679,32 +598,7 @@ class EgoNeRF(TensorBase):
         if value not in ("f32", "f16"):
             raise ValueError("app_table_dtype must be 'f32' or 'f16'")
         self._app_table_dtype = value
-        self._scene_cache = None
-
-    def _app_tables(self) -> List[torch.Tensor]:
-        out = []
-        for g in ("yin", "yang"):
-            out += list(getattr(self, f"app_plane_{g}")) + list(getattr(self, f"app_line_{g}"))
-        return out
-
-    def _fill_app16(self, sc):
-        tabs = self._app_tables()
-        ver = tuple((t.data_ptr(), t._version) for t in tabs)
-        if self._app16 is None or self._app16[0] != ver:
-            # [1,H,W,C] channel-last memory of the (1,C,H,W) parameters, converted to half (a cast, done when weights change), in
-            # one buffer
-            halves = _carve_channel_last([(t.shape[1], t.shape[2], t.shape[3]) for t in tabs], tabs[0].device, torch.float16)
-            for hv, t in zip(halves, tabs):
-                hv.copy_(t.detach())
-            self._app16 = (ver, halves)
-        halves = self._app16[1]
-        sc.app16.n_comp = self.app_n_comp[0]
-        sc.app16.res[:] = self.gridSize.tolist()
-        for gi in range(2):
-            for i in range(3):
-                sc.app16.plane[gi][i] = halves[gi * 6 + i].data_ptr()
-                sc.app16.line[gi][i] = halves[gi * 6 + 3 + i].data_ptr()
-        sc.app_f16 = 1
+        self.invalidate_scene()
 
     # -- C-ABI scene ----------------------------------------------------------------------------------------
     def _mlp_tensors(self) -> List[torch.Tensor]:
@@ -714,19 +608,40 @@ class EgoNeRF(TensorBase):
         return [m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias, self.basis_mat_yin.weight,
                 self.basis_mat_yang.weight]
 
-    def _fill_field(self, f: "_lib.VmField", prefix: str, n_comp, res, coarse=False):
+    def _fill_field(self, f: "_lib.VmField", kind: str, coarse=False, tensors=None):
+        """One ego_vm_field: the tables of `kind` (coarse: the 2x pooled ones at half the resolution), or `tensors` in their place."""
+        n_comp = self.density_n_comp if kind == "density" else self.app_n_comp
         if len(set(n_comp)) != 1:
             raise NotImplementedError("per-plane component counts must be equal (true for every shipped config)")
         f.n_comp = n_comp[0]
-        f.res[:] = res
-        for gi, g in enumerate(("yin", "yang")):
-            planes = getattr(self, f"coarse_sigma_plane_{g}" if coarse else f"{prefix}_plane_{g}")
-            lines = getattr(self, f"coarse_sigma_line_{g}" if coarse else f"{prefix}_line_{g}")
-            for i in range(3):
-                if planes[i] is None:
-                    raise RuntimeError("coarse density tables missing: call update_coarse_sigma_grid()")
-                f.plane[gi][i] = _table_ptr(planes[i])
-                f.line[gi][i] = _table_ptr(lines[i])
+        f.res[:] = [int(v) // 2 if coarse else int(v) for v in self.gridSize.tolist()]
+        field_tables.fill_pointers(f, field_tables.tables(self, kind, coarse) if tensors is None else tensors)
+
+    def invalidate_scene(self, moved: bool = False) -> None:
+        """The next scene() call builds the struct anew.  The per-mode packed blobs and the half tables stay (an earlier struct or a captured
+        graph may point into them; reused while device, size and table versions stand) unless the whole model `moved` (Module._apply)."""
+        self._scene = _SceneEntry() if moved else _SceneEntry(self._scene.blobs, self._scene.app16)
+
+    def packed_blob(self, training: bool = False) -> Optional[torch.Tensor]:
+        """The packed MLP / basis image of a mode as of the last scene(training) call (None before the first)."""
+        return self._scene.blobs.get(bool(training))
+
+    def _luts(self, dev) -> List[torch.Tensor]:
+        co = self.coordinates
+        return [co.lut_device(dev, 2)] + ([] if co.interval_th else [co.lut_device(dev, None)])
+
+    def _scene_key(self, training: bool) -> tuple:
+        """Everything the struct is a function of, as one tuple; no device work (the coordinates cache their LUTs).  Addresses stand for
+        allocations, (address, version) pairs for what is copied or packed at build time: the MLP / basis weights, and the appearance
+        tables while their half copy is in use.  id(alphaMask) is sound because the entry holds that mask: no other object can get its id."""
+        co = self.coordinates
+        copied = self._mlp_tensors() + (field_tables.tables(self, "app") if self._app_table_dtype == "f16" else [])
+        return (tuple(p.data_ptr() for p in self.parameters()), tuple((t.data_ptr(), t._version) for t in copied),
+                None if self.envmap is None else self.envmap.emission.data_ptr(), self.use_alpha_mask, id(self.alphaMask),
+                float(self.early_termination_eps), float(self.rayMarch_weight_thres) if self.use_weight_thres else None,
+                bool(self.skip_zero_weight_tiles), co.N_r, float(co.r0), float(co.far[0]), tuple(co.center.tolist()),
+                tuple(t.data_ptr() for t in self._luts(self.density_plane_yin[0].device)), float(self.distance_scale),
+                float(self.density_shift), self.fea2denseAct, self._mlp_precision, self._app_table_dtype, bool(training))
 
     @_lib.device_guard
     def scene(self, training: bool = False) -> "_lib.Scene":
@@ -741,68 +656,37 @@ class EgoNeRF(TensorBase):
         captured hipGraph that embeds it, reads the refreshed values (what GraphedTrainStep relies on).  The packed MLP / basis images
         are different: a SNAPSHOT taken by this call, one blob per mode (training / inference) - a struct returned earlier keeps reading
         the weights as of its own pack (a captured graph that contains the pack kernel re-packs on every replay); call scene() again
-        after the weights changed.  A holder that needs a frozen
-        snapshot must copy the tables; re-allocation (another shape / device, tables assigned one by one) invalidates the cached
-        struct and the next scene() call builds a new one."""
+        after the weights changed.  A holder that needs a frozen snapshot must copy the tables; re-allocation (another shape / device,
+        tables assigned one by one) invalidates the cached struct and the next scene() call builds a new one.  One struct is cached
+        (not one per mode), together with everything it points to that nobody else keeps alive (_SceneEntry)."""
         dev = self.density_plane_yin[0].device
         if dev.type != "cuda":
             raise RuntimeError(f"model parameters are on {dev}; the EgoNeRF hot path runs only on the HIP device")
-        for kind in ("density", "app"):  # e.g. after load_state_dict(assign=True); .to() / .cuda() / .float() are handled in _apply
-            if not self._is_compact(kind):
-                self._recompact_tables(kind)
-        mlp = self._mlp_tensors()
-        versions = tuple((t.data_ptr(), t._version) for t in mlp)
-        if self._app_table_dtype == "f16":  # the half copy follows the appearance tables' versions
-            versions += tuple((t.data_ptr(), t._version) for t in self._app_tables())
-        co = self.coordinates
-        luts = [co.lut_device(dev, 2)] + ([] if co.interval_th else [co.lut_device(dev, None)])  # held by the cache entry below
-        keys = tuple(p.data_ptr() for p in self.parameters()) + (None if self.envmap is None else self.envmap.emission.data_ptr(),
-                                                                  self.use_alpha_mask, id(self.alphaMask), float(self.early_termination_eps),
-                                                                  float(self.rayMarch_weight_thres) if self.use_weight_thres else None,
-                                                                  bool(self.skip_zero_weight_tiles), co.N_r, float(co.r0), float(co.far[0]), tuple(co.center.tolist()),
-                                                                  tuple(t.data_ptr() for t in luts), float(self.distance_scale),
-                                                                  float(self.density_shift), self.fea2denseAct, bool(training))
-        if self._scene_cache is not None and self._scene_cache[0] == keys and self._packed_versions == versions:
-            return self._scene_cache[1]
-        lib = _lib.load()
-        sc = _lib.new_scene()
-        co.fill_scene(sc, dev)
+        if self._scene.key != self._scene_key(training):
+            self._scene = self._build_scene(training, dev)
+        return self._scene.struct
+
+    def _build_scene(self, training: bool, dev) -> "_SceneEntry":
+        # Tables assigned one by one, e.g. by load_state_dict(assign=True) (.to() / .cuda() / .float() are handled in _apply), go back
+        # into one buffer first.  A hit needs no such check: its key holds the addresses the tables had when they were checked here.
+        for kind in ("density", "app"):
+            if not field_tables.is_compact(field_tables.tables(self, kind)):
+                field_tables.recarve(self, kind, keep_parameters=True)
+        entry = _SceneEntry(self._scene.blobs, self._scene.app16)
+        sc = entry.struct = _lib.new_scene()
+        entry.luts = self._luts(dev)
+        self.coordinates.fill_scene(sc, dev)
         sc.act_softplus = int(self.fea2denseAct == "softplus")
         sc.density_shift, sc.distance_scale = float(self.density_shift), float(self.distance_scale)
-        g = self.gridSize.tolist()
-        self._fill_field(sc.density, "density", self.density_n_comp, g)
-        self._fill_field(sc.app, "app", self.app_n_comp, g)
+        self._fill_field(sc.density, "density")
+        self._fill_field(sc.app, "app")
         if self.coarse_sigma_plane_yin[0] is not None:
-            self._fill_field(sc.density_coarse, "density", self.density_n_comp, [v // 2 for v in g], coarse=True)
-        holds = [t.detach().contiguous() for t in mlp]
-        if self.shadingMode == "RGB":
-            sc.head = 1   # EGO_HEAD_RGB: mlp_w / mlp_b stay null, mlp_in = mlp_hidden = 0
-        else:
-            sc.mlp_w[:] = [holds[0].data_ptr(), holds[2].data_ptr(), holds[4].data_ptr()]
-            sc.mlp_b[:] = [holds[1].data_ptr(), holds[3].data_ptr(), holds[5].data_ptr()]
-        sc.basis[:] = [holds[-2].data_ptr(), holds[-1].data_ptr()]
-        sc.app_dim = self.app_dim
-        sc.mlp_in, sc.mlp_hidden = self.head_in_mlpC, self.head_hidden
-        sc.view_pe, sc.fea_pe = (self.view_pe, self.head_fea_pe) if self.shadingMode != "RGB" else (0, 0)
-        sc.mlp_precision = 0 if training else {"f16x3": 0, "f32": 1, "f16f8": 2, "f16f6": 3}[self._mlp_precision]
-        # packed weights: the MFMA fragment layouts for the tuned shape (27 / 48 / 150 / 128 / 2 / 2, every shipped config), the fp32
-        # layout of the any-shape compatibility kernels otherwise (csrc/ego_generic.hip; the library reports the size for the shape)
-        sc.app.n_comp = self.app_n_comp[0]
-        need = lib.ego_packed_floats_scene(C.byref(sc))
-        if need <= 0:
-            raise RuntimeError("ego_packed_floats_scene rejected the scene")
-        # one blob per mode (ADVICE r05): a training pack writes only the regions the f16x3 training kernels read, so it must never land
-        # in the blob an earlier INFERENCE struct (or a captured preview-render graph) points to - that holder would mix fresh fp16 main
-        # terms with stale fp8 / fp6 correction terms
-        if self._packed is None:
-            self._packed = {}
-        blob = self._packed.get(bool(training))
-        if blob is None or blob.device != dev or blob.numel() != need:
-            blob = self._packed[bool(training)] = torch.zeros(need, device=dev)
-        _call("ego_pack_mlp_for", sc, blob.data_ptr(), int(training), _lib.stream_handle())
-        sc.packed = blob.data_ptr()
+            self._fill_field(sc.density_coarse, "density", coarse=True)
+        self._fill_head(sc, entry, training)
+        self._pack_head(sc, entry, training, dev)
         if self._app_table_dtype == "f16" and not training:
-            self._fill_app16(sc)
+            self._fill_app16(sc, entry)
+        entry.mask = self.alphaMask
         if self.use_alpha_mask and self.alphaMask is not None:
             self.alphaMask.fill_scene(sc)
         sc.term_eps = float(self.early_termination_eps)
@@ -814,9 +698,47 @@ class EgoNeRF(TensorBase):
             if not em.is_contiguous():
                 raise RuntimeError("envmap.emission must be contiguous [3][2h][h]")
             sc.envmap, sc.envmap_h = em.data_ptr(), em.shape[2]
-        self._scene_cache = (keys, sc, holds, luts)
-        self._packed_versions = versions
-        return sc
+        entry.key = self._scene_key(training)
+        return entry
+
+    def _fill_head(self, sc, entry, training: bool):
+        holds = entry.holds = [t.detach().contiguous() for t in self._mlp_tensors()]
+        if self.shadingMode == "RGB":
+            sc.head = 1   # EGO_HEAD_RGB: mlp_w / mlp_b stay null, mlp_in = mlp_hidden = 0
+        else:
+            sc.mlp_w[:] = [holds[0].data_ptr(), holds[2].data_ptr(), holds[4].data_ptr()]
+            sc.mlp_b[:] = [holds[1].data_ptr(), holds[3].data_ptr(), holds[5].data_ptr()]
+        sc.basis[:] = [holds[-2].data_ptr(), holds[-1].data_ptr()]
+        sc.app_dim = self.app_dim
+        sc.mlp_in, sc.mlp_hidden = self.head_in_mlpC, self.head_hidden
+        sc.view_pe, sc.fea_pe = (self.view_pe, self.head_fea_pe) if self.shadingMode != "RGB" else (0, 0)
+        sc.mlp_precision = 0 if training else {"f16x3": 0, "f32": 1, "f16f8": 2, "f16f6": 3}[self._mlp_precision]
+
+    def _pack_head(self, sc, entry, training: bool, dev):
+        """Packed weights: the MFMA fragment layouts for the tuned shape (27 / 48 / 150 / 128 / 2 / 2, every shipped config), the fp32
+        layout of the any-shape compatibility kernels otherwise (csrc/ego_generic.hip; the library reports the size for the shape).  One
+        blob per mode: a training pack writes only the regions the f16x3 training kernels read, so it must never land in the
+        blob an earlier INFERENCE struct (or a captured preview-render graph) points to: stale fp8 / fp6 correction terms under fresh fp16."""
+        need = _lib.load().ego_packed_floats_scene(C.byref(sc))
+        if need <= 0:
+            raise RuntimeError("ego_packed_floats_scene rejected the scene")
+        blob = entry.blobs.get(bool(training))
+        if blob is None or blob.device != dev or blob.numel() != need:
+            blob = entry.blobs[bool(training)] = torch.zeros(need, device=dev)
+        _call("ego_pack_mlp_for", sc, blob.data_ptr(), int(training), _lib.stream_handle())
+        sc.packed = blob.data_ptr()
+
+    def _fill_app16(self, sc, entry):
+        tabs = field_tables.tables(self, "app")
+        ver = tuple((t.data_ptr(), t._version) for t in tabs)
+        if entry.app16 is None or entry.app16[0] != ver:
+            # [1,H,W,C] channel-last memory of the (1,C,H,W) parameters as halves (a cast, done when weights change), in one buffer
+            halves = field_tables.carve_channel_last(field_tables.shapes_of(tabs), tabs[0].device, torch.float16)
+            for hv, t in zip(halves, tabs):
+                hv.copy_(t.detach())
+            entry.app16 = (ver, halves)
+        self._fill_field(sc.app16, "app", tensors=entry.app16[1])
+        sc.app_f16 = 1
 
     # -- stage methods (reference public API) ----------------------------------------------------------------
     def _sched(self, n_samples: int, device) -> torch.Tensor:
@@ -886,13 +808,9 @@ class EgoNeRF(TensorBase):
 
     @_lib.device_guard
     def _density(self, coords_sampled, coarse: int):
-        _require_cuda(coords_sampled, "compute_densityfeature")
-        _last_dim(coords_sampled, 7, "compute_densityfeature")
-        from .stage_autograd import needs_grad
-        params = [p for tl in self._table_lists("density") for p in tl]
-        if needs_grad(*params):
-            from .stage_autograd import DensityFeatureFunction
-            return DensityFeatureFunction.apply(self, coarse, coords_sampled.detach(), *params)
+        params = field_tables.tables(self, "density")
+        if stage_autograd.needs_grad(*params):
+            return stage_autograd.DensityFeatureFunction.apply(self, coarse, coords_sampled.detach(), *params)
         return self._density_forward(coords_sampled, coarse)
 
     def _density_forward(self, coords_sampled, coarse: int):
@@ -919,13 +837,9 @@ class EgoNeRF(TensorBase):
         """EgoNeRF.py:349-413: [...,7] -> [..., app_dim].  Differentiable to the 12 appearance tables and basis_mat_{yin,yang}.weight when
         grad mode is on and one of them requires grad (stage_autograd.AppFeatureFunction): same forward bits (whatever app_table_dtype),
         fp32-grade backward at the fp32 tables, bit-reproducible for the shipped 48-component shape."""
-        _require_cuda(coords_sampled, "compute_appfeature")
-        _last_dim(coords_sampled, 7, "compute_appfeature")
-        from .stage_autograd import needs_grad
-        params = [p for tl in self._table_lists("app") for p in tl] + [self.basis_mat_yin.weight, self.basis_mat_yang.weight]
-        if needs_grad(*params):
-            from .stage_autograd import AppFeatureFunction
-            return AppFeatureFunction.apply(self, coords_sampled.detach(), *params)
+        params = field_tables.tables(self, "app") + [self.basis_mat_yin.weight, self.basis_mat_yang.weight]
+        if stage_autograd.needs_grad(*params):
+            return stage_autograd.AppFeatureFunction.apply(self, coords_sampled.detach(), *params)
         return self._app_forward(coords_sampled)
 
     def _app_forward(self, coords_sampled):
@@ -973,7 +887,7 @@ class EgoNeRF(TensorBase):
             a = torch.nn.functional.max_pool3d(a, kernel_size=3, padding=1, stride=1).view(g[::-1])
             vols.append((a >= self.alphaMask_thres).float())
         self.alphaMask = YinYangAlphaGridMask(self.device, vols[0], vols[1])
-        self._scene_cache = None
+        self.invalidate_scene()
         return float((vols[0].sum() + vols[1].sum()) / (2 * g[0] * g[1] * g[2]))
 
     # -- the hot path -------------------------------------------------------------------------------------------
@@ -982,16 +896,6 @@ class EgoNeRF(TensorBase):
                 pretrain_envmap=False, pivotal_sample_th=0.0, resampling=False, use_coarse_sample=True, interval_th=False,
                 jitter: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, need_alpha: bool = True,
                 marched_event: Optional["torch.cuda.Event"] = None):
-        self._last_render, self._last_shaded = None, None   # set again by a call that runs ego_render_forward
-        out = self._forward(rays_chunk, is_train, ndc_ray, n_coarse, n_fine, exp_sampling, pretrain_envmap, resampling, use_coarse_sample,
-                            jitter, u, need_alpha, marched_event)
-        if marched_event is not None and not getattr(self, "_marched_recorded", False):
-            marched_event.record()   # a path without a march of its own (training, envmap pre-training, ...): "marched" = done
-        self._marched_recorded = False
-        return out
-
-    def _forward(self, rays_chunk, is_train, ndc_ray, n_coarse, n_fine, exp_sampling, pretrain_envmap, resampling, use_coarse_sample,
-                 jitter, u, need_alpha, marched_event):
         """EgoNeRF.forward (EgoNeRF.py:491-602) -> (rgb_map [N,3], depth_map [N], bg_map|None, env_map|None,
         alpha [N, S(+1)]).  `white_bg`, `pivotal_sample_th`, `interval_th` are accepted and unused, as in the
         reference.  `jitter` [N,n_coarse] / `u` [N,n_fine] pin the is_train noise.  `need_alpha=False` (eval only; what
@@ -999,65 +903,77 @@ class EgoNeRF(TensorBase):
         evaluating a ray once its transmittance is exactly 0 (the remaining weights are exactly 0 either way).  `marched_event` (a created
         torch.cuda.Event; volume_renderer's host hand-over passes it): recorded on the current stream behind the call's last march, ahead
         of its shade kernel (ego_render_args.marched) - or at the end of a call that takes another path."""
+        self._last_render = self._last_shaded = None   # set again by a call that runs ego_render_forward
         _require_cuda(rays_chunk, "EgoNeRF.forward")
         if rays_chunk.dim() != 2 or rays_chunk.shape[1] < 6:
             raise IndexError(f"EgoNeRF.forward: rays_chunk must be [N, >=6] (origin, direction), got {tuple(rays_chunk.shape)}")
+        marched = False   # whether the library was handed `marched_event`
         if pretrain_envmap:
-            return self.envmap.get_radiance(rays_chunk[:, 3:6])
-        if ndc_ray:
+            out = self.envmap.get_radiance(rays_chunk[:, 3:6])
+        elif ndc_ray:
             raise NotImplementedError  # EgoNeRF.py:503-504
-        rays = _f32c(rays_chunk[:, :6])
+        else:
+            rays = _f32c(rays_chunk[:, :6])
+            z_coarse, jitter, u = self._noise_plan(rays, n_coarse, n_fine, is_train, exp_sampling, resampling, jitter, u)
+            if not is_train and z_coarse is not None and rays.shape[0] and not bool((z_coarse[:, 0] == z_coarse[0, 0]).all()):
+                # rays that enter the aabb at different distances: the reference places the first-pass samples per ray but
+                # measures every ray with ray 0's distances (EgoNeRF.py:515-516) - evaluated the same way, stage by stage
+                out = self._forward_eval_ray0_distances(rays, z_coarse, int(n_coarse), int(n_fine), bool(resampling),
+                                                        bool(use_coarse_sample), need_alpha)
+            elif torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                # any supported shape trains: the tuned one through the MFMA kernels, the others through the fp32 compatibility kernels
+                from .train import render_train  # differentiable path: keeps activations, backward in HIP (egonerf_amd/train.py)
+                out = render_train(self, rays, n_coarse, n_fine, resampling, use_coarse_sample, jitter, u, z_coarse)
+            else:
+                out, marched = self._render_forward(rays, z_coarse, jitter, u, n_coarse, n_fine, resampling, use_coarse_sample, need_alpha,
+                                                    marched_event)
+        if marched_event is not None and not marched:
+            marched_event.record()   # a path without a march of its own (training, envmap pre-training, ...): "marched" = done
+        return out
+
+    def _noise_plan(self, rays, n_coarse, n_fine, is_train, exp_sampling, resampling, jitter=None, u=None):
+        """Where the first pass samples and with what noise -> (z_coarse | None, jitter | None, u | None) as ego_render_forward and
+        train.render_train take them.  Plain torch, no library call: it runs on CPU rays too.
+        z_coarse [N, n_coarse]: explicit distances, for TensorBase.sample_ray's per-ray uniform schedule (exp_sampling=False,
+        tensorBase.py:308-327; the noise is `rng += rand`) and for the plain exponential schedule in training (EgoNeRF.py:59-67: noise
+        in the exponent); otherwise the march follows the model's schedule (_sched) plus `jitter`.
+        Noise exists only with is_train; what the caller pins is used and nothing is drawn for it.  Otherwise, in this order: jitter =
+        torch.rand(N, n_coarse) from the CPU generator (tensorBase.py:320, EgoNeRF.py:81); a second draw of that shape when the jitter
+        went into z_coarse; with resampling, u = torch.rand(N, n_fine) from the generator of the rays' device (ray_utils.py:169)."""
         N, dev = rays.shape[0], rays.device
+        if not is_train:
+            return (None if exp_sampling else self.sample_ray_z(rays, n_coarse)), None, None
+        drawn = jitter is None
+        if drawn:
+            jitter = torch.rand(N, n_coarse)
         z_coarse = None
         if not exp_sampling:
-            # TensorBase.sample_ray (tensorBase.py:308-327): the per-ray uniform schedule is computed here and handed over as
-            # explicit distances; the noise (`rng += rand`) is `jitter`
-            if is_train and jitter is None:
-                jitter = torch.rand(N, n_coarse)  # CPU generator like tensorBase.py:320
-            z_coarse = self.sample_ray_z(rays, n_coarse, jitter.to(dev) if is_train else None)
-            if not is_train:
-                if N and not bool((z_coarse[:, 0] == z_coarse[0, 0]).all()):
-                    # rays that enter the aabb at different distances: the reference places the first-pass samples per ray but
-                    # measures every ray with ray 0's distances (EgoNeRF.py:515-516) - evaluated the same way, stage by stage
-                    return self._forward_eval_ray0_distances(rays, z_coarse, int(n_coarse), int(n_fine), bool(resampling),
-                                                             bool(use_coarse_sample), need_alpha)
-            jitter = None
-        if is_train and exp_sampling and not self.coordinates.interval_th:
-            if jitter is None:
-                jitter = torch.rand(N, n_coarse)
+            z_coarse = self.sample_ray_z(rays, n_coarse, jitter.to(dev))
+        elif not self.coordinates.interval_th:
             z_coarse = self._plain_exp_train_z(n_coarse, jitter.to(dev))
-            jitter = None
-        if is_train:
-            if jitter is None:
-                jitter = torch.rand(N, n_coarse).to(dev)  # CPU generator like EgoNeRF.py:81
-            if resampling and u is None:
-                u = torch.rand(N, n_fine, device=dev)  # device generator like ray_utils.py:169
-            jitter = _f32c(jitter)
-            u = _f32c(u) if resampling else None
-        else:
-            jitter = u = None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            # any supported shape trains: the tuned one through the MFMA kernels, the others through the fp32 compatibility kernels
-            from .train import render_train  # differentiable path: keeps activations, backward in HIP (egonerf_amd/train.py)
-            return render_train(self, rays, n_coarse, n_fine, resampling, use_coarse_sample, jitter, u, z_coarse)
+        if z_coarse is not None and drawn:
+            # With z_coarse given the march never reads `jitter`: these values are never used.  The draw is kept only so that the CPU
+            # generator is left in the state it has always been left in (a seeded run draws the same numbers afterwards).
+            jitter = torch.rand(N, n_coarse)
+        if resampling and u is None:
+            u = torch.rand(N, n_fine, device=dev)
+        return z_coarse, _f32c(jitter.to(dev)), _f32c(u) if resampling else None
+
+    def _render_forward(self, rays, z_coarse, jitter, u, n_coarse, n_fine, resampling, use_coarse_sample, need_alpha, marched_event):
+        """Fills ego_render_args, sizes the workspace and runs ego_render_forward -> (result, whether it took `marched_event`)."""
+        N, dev = rays.shape[0], rays.device
         sc = self.scene()
         args = _lib.RenderArgs()
         args.n_coarse, args.n_fine = int(n_coarse), int(n_fine)
         args.resampling, args.use_coarse_sample = int(bool(resampling)), int(bool(use_coarse_sample))
         args.r_sched = self._sched(n_coarse, dev).data_ptr()
         args.near_ = float(self.near_far[0])
-        if z_coarse is not None:
-            args.z_coarse = z_coarse.data_ptr()
-        if jitter is not None:
-            args.jitter = jitter.data_ptr()
-        if u is not None:
-            args.u = u.data_ptr()
-        if marched_event is not None and N:
+        args.z_coarse, args.jitter, args.u = _lib.ptr(z_coarse), _lib.ptr(jitter), _lib.ptr(u)
+        marched = marched_event is not None and N > 0
+        if marched:
             args.marched = marched_event.cuda_event
-            self._marched_recorded = True
         S = _lib.sample_count(n_coarse, n_fine, resampling, use_coarse_sample)
-        lib = _lib.load()
-        ws_bytes = lib.ego_render_workspace_bytes(N, C.byref(args))
+        ws_bytes = _lib.load().ego_render_workspace_bytes(N, C.byref(args))
         if ws_bytes < 0:
             raise RuntimeError("ego_render_workspace_bytes rejected the arguments (n_coarse < 2?)")
         ws = torch.empty(max(ws_bytes, 4) // 4, device=dev)
@@ -1071,7 +987,7 @@ class EgoNeRF(TensorBase):
               _lib.ptr(alpha), _lib.ptr(bg_map), _lib.ptr(env_map), _lib.stream_handle())
         if N:
             self._last_render = (N, args, ws)   # for last_shaded_samples (the workspace holds the live count / tile flags)
-        return rgb_map, depth, bg_map, env_map, alpha
+        return (rgb_map, depth, bg_map, env_map, alpha), marched
 
     @property
     def last_shaded_samples(self) -> Optional[torch.Tensor]:
@@ -1080,11 +996,10 @@ class EgoNeRF(TensorBase):
         the compact path (include/egonerf_hip.h: ego_render_forward_compacts), 32 x the shaded tiles (at most N S) on the tile paths, N S
         without skipping.  None when the last forward did not run ego_render_forward (training, envmap pre-training, the ray-0-distance
         evaluation, N = 0).  Computed on first access from the workspace the forward keeps for it."""
-        last = getattr(self, "_last_render", None)
-        if last is None:
+        if self._last_render is None:
             return None
         if self._last_shaded is None:
-            N, args, ws = last
+            N, args, ws = self._last_render
             with torch.cuda.device(ws.device):
                 out = torch.empty((), dtype=torch.int64, device=ws.device)
                 _call("ego_render_shaded_samples", N, C.byref(args), ws.data_ptr(), out.data_ptr(), _lib.stream_handle())
@@ -1157,7 +1072,7 @@ class EgoNeRF(TensorBase):
             self.envmap = EnvironmentMap(h=ckpt["envmap_res_H"], init_strategy="zero", device=self.device)
             self.envmap.load_envmap(emission=ckpt["envmap.emission"], device=self.device)
         self.load_state_dict(ckpt["state_dict"])
-        self._scene_cache = None
+        self.invalidate_scene()
         if self.coarse_sigma_grid_update_rule == "conv" and self.density_plane_yin[0].is_cuda:
             self.update_coarse_sigma_grid()  # EgoNeRF.py:185-186 (a CPU-resident model only holds weights)
         return ckpt["global_step"]
@@ -1165,7 +1080,7 @@ class EgoNeRF(TensorBase):
     def load_state_dict(self, state_dict, strict=True):
         """Values are copied into the existing channel-last parameters (shapes/keys are the reference's)."""
         r = super().load_state_dict(state_dict, strict=strict)
-        self._scene_cache = None
+        self.invalidate_scene()
         return r
 
 

@@ -19,7 +19,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import check as _chk
-from .model import _carve_channel_last
+from .field_tables import carve_channel_last, shapes_of
 
 
 def needs_grad(*tensors) -> bool:
@@ -40,13 +40,13 @@ def _workspace(model, nbytes: int, device) -> torch.Tensor:
 
 def _grad_tables(params: List[torch.Tensor]):
     """Channel-last gradient tables shaped like `params` (one buffer, like the parameters) + the ego_vm_grad struct over them."""
-    gs = _carve_channel_last([(p.shape[1], p.shape[2], p.shape[3]) for p in params], params[0].device)
+    gs = carve_channel_last(shapes_of(params), params[0].device)
     return gs, _lib.grad_struct(gs)
 
 
 class DensityFeatureFunction(torch.autograd.Function):
     """compute_densityfeature (coarse = 0) / compute_coarse_densityfeature (coarse = 1) with gradients to the 12 density tables
-    (plane_yin x3, line_yin x3, plane_yang x3, line_yang x3).  The coarse op differentiates through the 2x2 / 2x average pooling of
+    (in field_tables.tables order).  The coarse op differentiates through the 2x2 / 2x average pooling of
     EgoNeRF.py:124-133 into the full-resolution tables; its values come from the last update_coarse_sigma_grid() snapshot.  Shipped
     shape (16 components), fine op: bit-reproducible table gradients (sorted walk); otherwise float atomics."""
 

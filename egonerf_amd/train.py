@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .field_tables import tables as table_params  # (tests and tools import table_params from here too)
 from ._lib import SideStream, grad_struct as _grad_struct  # noqa: F401  (tests and tools import _grad_struct from here)
 
 
@@ -131,13 +132,6 @@ def _zeros_like_many(tensors, zero: bool = True):
 
 def _empty(device, *shape, dtype=torch.float32) -> torch.Tensor:
     return torch.empty(*shape, device=device, dtype=dtype)
-
-
-def table_params(model, kind: str) -> List[torch.nn.Parameter]:
-    out = []
-    for g in ("yin", "yang"):
-        out += list(getattr(model, f"{kind}_plane_{g}")) + list(getattr(model, f"{kind}_line_{g}"))
-    return out
 
 
 def differentiable_params(model) -> List[torch.nn.Parameter]:

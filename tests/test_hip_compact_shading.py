@@ -66,7 +66,7 @@ def scene_model(kind, env, shading="MLP_Fea"):
                     v[0, 0, :v.shape[2] // 2, :, 2 * d // 3:] = 0
                 model.alphaMask = YinYangAlphaGridMask(DEV, vols[0], vols[1])
                 model.use_alpha_mask = True
-                model._scene_cache = None
+                model.invalidate_scene()
         _MODELS[key] = model
     return _MODELS[key]
 

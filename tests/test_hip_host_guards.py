@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from egonerf_amd import _lib, synth
+from egonerf_amd import _lib, field_tables, synth
 from tests.helpers import make_model, make_oracle, maxerr
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,7 @@ def test_model_built_on_cpu_then_moved_renders_and_stays_compact():
     ids = [id(p) for p in cpu_model.parameters()]
     moved = cpu_model.to("cuda")
     assert [id(p) for p in moved.parameters()] == ids
-    assert moved._is_compact("density") and moved._is_compact("app")
+    assert all(field_tables.is_compact(field_tables.tables(moved, kind)) for kind in ("density", "app"))
     got = _render(moved, rays)
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
     again = _render(moved.float().cuda(), rays)   # no-op conversions must not break anything either
@@ -42,19 +42,18 @@ def test_model_built_on_cpu_then_moved_renders_and_stays_compact():
 def test_non_compact_tables_are_recompacted_lazily():
     """Parameters assigned one by one (what load_state_dict(assign=True) does): scene() notices a field that is not within one
     4 GB window and re-carves it; here the window is shrunk artificially by planting one table far away is not possible in a
-    test, so the hook is exercised through _recompact_tables directly and the render compared."""
+    test, so the hook is exercised through field_tables.recarve directly and the render compared."""
     cfg = synth.SceneConfig(n_voxel=20 ** 3)
     w = synth.make_weights(cfg, seed=77)
     model = make_model(cfg, w, "cuda")
     rays = torch.from_numpy(synth.make_rays(64, seed=5)).cuda()
     want = _render(model, rays)
     ids = [id(p) for p in model.parameters()]
-    for l in model._table_lists("app"):      # separate allocations, as after assign=True
-        for p in l:
-            p.data = p.data.clone(memory_format=torch.preserve_format)
-    model._recompact_tables("app")
-    model._recompact_tables("density")
-    assert [id(p) for p in model.parameters()] == ids and model._is_compact("app")
+    for p in field_tables.tables(model, "app"):      # separate allocations, as after assign=True
+        p.data = p.data.clone(memory_format=torch.preserve_format)
+    field_tables.recarve(model, "app", keep_parameters=True)
+    field_tables.recarve(model, "density", keep_parameters=True)
+    assert [id(p) for p in model.parameters()] == ids and field_tables.is_compact(field_tables.tables(model, "app"))
     got = _render(model, rays)
     assert torch.equal(got[0], want[0])
 
@@ -231,3 +230,38 @@ def test_marched_event_is_recorded_on_every_path():
     other.wait_event(ev)
     other.synchronize()
     assert ev.query()
+
+
+def test_replaced_alpha_mask_is_rendered_without_a_hand_invalidation():
+    """The scene cache keys the mask by id() and holds the mask it was built with, so a mask assigned over another one can never
+    inherit the id of a freed predecessor and be served the cached struct (whose occ / occ_cell would point into freed memory): the
+    render after the assignment equals a fresh model's, and the mask lives as long as the struct that points into it."""
+    import gc
+    import weakref
+    from egonerf_amd.model import YinYangAlphaGridMask
+    cfg = synth.SceneConfig(n_voxel=20 ** 3)
+    w = synth.make_weights(cfg, seed=1234)
+    model = make_model(cfg, w, "cuda")
+    rays = torch.from_numpy(synth.make_rays(64, seed=5)).cuda()
+    model.updateAlphaMask()
+    model.use_alpha_mask = True
+    first = _render(model, rays)
+    vols = [model.alphaMask.alpha_volume_yin.clone(), model.alphaMask.alpha_volume_yang.clone()]
+    for v in vols:
+        v[..., 3:5] = 0   # two radial shells emptied, as in test_skip_semantics_on_reference_mask
+    model.alphaMask = YinYangAlphaGridMask(model.device, vols[0].clone(), vols[1].clone())   # the model held the only reference to A
+    gc.collect()
+    second = _render(model, rays)
+    fresh = make_model(cfg, w, "cuda")
+    fresh.alphaMask, fresh.use_alpha_mask = YinYangAlphaGridMask(fresh.device, vols[0], vols[1]), True
+    want = _render(fresh, rays)
+    for got_, want_ in zip(second, want):
+        assert (got_ is None) == (want_ is None) and (got_ is None or torch.equal(got_, want_))
+    assert not torch.equal(second[0], first[0])
+    alive = weakref.ref(model.alphaMask)
+    model.alphaMask = None
+    gc.collect()
+    assert alive() is not None   # the cached struct still points into B's buffers
+    model.scene()                # built anew (the key changed): nothing points into B any more
+    gc.collect()
+    assert alive() is None

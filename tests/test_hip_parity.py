@@ -55,7 +55,7 @@ def test_device_packer_is_bit_exact(tiny):
     _, _, w, model = tiny
     model.scene()
     torch.cuda.synchronize()
-    blob = model._packed[False].cpu().numpy()   # the inference blob (training packs go to one of their own)
+    blob = model.packed_blob(training=False).cpu().numpy()   # the inference blob (training packs go to one of their own)
     assert np.array_equal(blob[:em.PACKED_FLOATS], em.pack_mlp(w))
     assert np.array_equal(blob[em.PACKED_FLOATS:2 * em.PACKED_FLOATS].view(np.uint32), em.pack_mlp_f16(w).view(np.uint32))
     assert blob.shape[0] == 2 * em.PACKED_FLOATS + 9216 + em.F8_FLOATS + em.F6_FLOATS  # + basis fragments in the fp16-table K order + f16f8 + f16f6 images
@@ -329,7 +329,7 @@ def test_alpha_mask_matches_reference(golden, tiny):
     assert maxerr(ref_mask.sample_alpha(T(fx["coords"])), fx["sampled"]) <= 2e-6
     assert 0.0 < frac <= 1.0
     model.alphaMask = None
-    model._scene_cache = None
+    model.invalidate_scene()
 
 
 def test_skip_semantics_on_reference_mask(golden, tiny):
@@ -377,7 +377,7 @@ def test_skip_semantics_on_reference_mask(golden, tiny):
         model.use_alpha_mask = model.use_weight_thres = False
         model.rayMarch_weight_thres = 1e-4
         model.alphaMask = None
-        model._scene_cache = None
+        model.invalidate_scene()
 
 
 def test_masked_and_terminated_render_vs_oracle(full):
@@ -405,7 +405,7 @@ def test_masked_and_terminated_render_vs_oracle(full):
         # mask rule - alpha per grid step >= 1e-4 - is not: on this semi-transparent synthetic field it moves RGB by ~0.1,
         # which is why it stays opt-in, as in EgoNeRF.forward.)
         model.use_alpha_mask = False
-        model._scene_cache = None
+        model.invalidate_scene()
         with torch.no_grad():
             term = model(rays.to(DEV), exp_sampling=True, **kw)
         assert maxerr(term[0], base[0]) <= 1.5e-5
@@ -413,7 +413,7 @@ def test_masked_and_terminated_render_vs_oracle(full):
         model.use_alpha_mask = False
         model.early_termination_eps = 0.0
         model.alphaMask = None
-        model._scene_cache = None
+        model.invalidate_scene()
 
 
 def test_erp_rays_on_device():

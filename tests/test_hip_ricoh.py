@@ -182,7 +182,7 @@ def test_alpha_mask_rule_on_the_ricoh_scene(ricoh):
             from egonerf_amd.model import YinYangAlphaGridMask
             model.alphaMask = YinYangAlphaGridMask(DEV, vols[0], vols[1])
             model.use_alpha_mask, model.use_weight_thres, model.rayMarch_weight_thres = True, True, thres
-            model._scene_cache = None
+            model.invalidate_scene()
             got = model(rays, **kw)
         orc.alpha_mask, orc.weight_thres = (vols[0].cpu(), vols[1].cpu()), thres
         ref, inter = orc.forward(rays.cpu(), keep=True, **okw)
@@ -207,7 +207,7 @@ def test_alpha_mask_rule_on_the_ricoh_scene(ricoh):
         model.use_alpha_mask = model.use_weight_thres = False
         model.rayMarch_weight_thres = 1e-4
         model.alphaMask = None
-        model._scene_cache = None
+        model.invalidate_scene()
 
 
 def test_config3_occupancy_skipping_on_full_size(ricoh):

@@ -13,7 +13,7 @@ model = synth.build_model(cfg, w, dev)
 model.mlp_precision = "f16f6"
 sc = model.scene()
 torch.cuda.synchronize()
-blob = model._packed.cpu().numpy()
+blob = model.packed_blob().cpu().numpy()
 off = 2 * em.PACKED_FLOATS + 9216 + em.F8_FLOATS
 got = blob[off:off + em.F6_FLOATS].view(np.uint32)
 exp = em.pack_mlp_f6(w).view(np.uint32)

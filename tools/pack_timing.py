@@ -1,11 +1,11 @@
 import sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, ctypes as C
 from egonerf_amd import synth, _lib
 cfg = synth.SceneConfig()
 model = synth.build_model(cfg, synth.make_weights(cfg, seed=1234), "cuda")
 sc = model.scene(); lib, st = _lib.load(), _lib.stream_handle()
-buf = model._packed
+buf = model.packed_blob()   # the inference blob scene() just packed
 def t(fn, reps=50):
     for _ in range(5): fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,6 +1,8 @@
-"""Fingerprint of the training step (egonerf_amd.train.RenderFunction): which library calls a step queues, and the bits it computes.
+"""Fingerprint of the training step (egonerf_amd.train.RenderFunction): which library calls a step queues, and the bits it computes;
+and of EgoNeRF.forward without a graph (inference_cases: the bits of every output, under no_grad).
 
-    python tools/train_step_fingerprint.py OUT.json            one eager forward + backward per case (+ one GraphedTrainStep case)
+    python tools/train_step_fingerprint.py OUT.json            one eager forward + backward per case (+ one GraphedTrainStep case),
+                                                               one forward per inference case
     python tools/train_step_fingerprint.py --compare A.json B.json
 
 Per case: the mark names collected through train.KERNEL_MARKS (one per library call, in queueing order) and the sha256 of the bytes of
@@ -58,6 +60,47 @@ def cases():
             yield f"{mode} head, 48-component tables, EGO_SORTED_WALK={walk}", head, {}, {}, dict(EGO_SORTED_WALK=walk), RESAMPLED, False
     yield "tuned head, 8-component density", dict(density_n_comp=(8, 8, 8)), {}, {}, {}, RESAMPLED, False
     yield "tuned, loss uses alpha", dict(use_envmap=True, envmap_res_H=16), {}, {}, {}, RESAMPLED, True
+
+
+def inference_cases():
+    """(name, SceneConfig keywords, model attributes, rays start outside the box, forward keywords).  Public names only: the same file
+    runs against an older checkout.  The attribute "alpha_mask" stands for updateAlphaMask() + use_alpha_mask."""
+    exp = dict(exp_sampling=True)
+    yield "eval exp_sampling=1", {}, {}, False, dict(exp, **SINGLE)
+    yield "eval exp_sampling=0, equal entry distances", {}, {}, False, dict(SINGLE)
+    yield "eval exp_sampling=0, rays from outside the box (ray-0 distances)", {}, {}, True, dict(SINGLE)
+    yield "eval exp_sampling=0, rays from outside the box, resampling", {}, {}, True, dict(RESAMPLED)
+    yield "eval resampling", {}, {}, False, dict(exp, **RESAMPLED)
+    yield "eval envmap", dict(use_envmap=True, envmap_res_H=16), {}, False, dict(exp, **RESAMPLED)
+    yield ("eval alpha mask + weight threshold + early termination", {},
+           dict(alpha_mask=True, use_weight_thres=True, rayMarch_weight_thres=2e-2, early_termination_eps=1e-3), False, dict(exp, **RESAMPLED))
+    yield "eval app_table_dtype=f16", {}, dict(app_table_dtype="f16"), False, dict(exp, **RESAMPLED)
+    for prec in ("f16f6", "f16f8", "f16x3", "f32"):
+        yield f"eval mlp_precision={prec}", {}, dict(mlp_precision=prec), False, dict(exp, **RESAMPLED)
+    yield "eval need_alpha=False", {}, {}, False, dict(exp, need_alpha=False, **RESAMPLED)
+
+
+def run_inference_case(name, cfg_kw, attrs, outside, kw):
+    attrs = dict(attrs)
+    model = build(cfg_kw, {})
+    model.eval()
+    if attrs.pop("alpha_mask", False):
+        model.updateAlphaMask()
+        model.use_alpha_mask = True
+    for k, v in attrs.items():
+        setattr(model, k, v)
+    rays = torch.from_numpy(synth.make_rays(N, seed=6)).to(DEV)
+    if outside:   # every other ray starts well outside the aabb and looks back in: the entry distances differ from ray to ray
+        far = 3.0 * float(model.aabb.abs().max())
+        rays[1::2, :3] -= far * rays[1::2, 3:6]
+    with torch.no_grad():
+        out = model(rays, **kw)
+        shaded = model.last_shaded_samples   # None: the call did not go through ego_render_forward
+    torch.cuda.synchronize()
+    assert (shaded is None) == outside, (name, "expected the ray-0-distance path" if outside else "expected ego_render_forward")
+    hashes = {k: None if t is None else sha(t) for k, t in zip(("rgb_map", "depth", "bg_map", "env_map", "alpha"), out)}
+    hashes["last_shaded_samples"] = None if shaded is None else int(shaded)
+    return dict(marks=[], excused=[], sha256=hashes)
 
 
 def build(cfg_kw, attrs):
@@ -172,6 +215,9 @@ def main(argv):
         out["cases"][case[0]] = run_case(*case, timed_iterations=20 if i == 0 else 0)
     print("case: graphed step", flush=True)
     out["cases"]["GraphedTrainStep, 5 replays"] = run_graphed()
+    for case in inference_cases():
+        print("case:", case[0], flush=True)
+        out["cases"][case[0]] = run_inference_case(*case)
     os.makedirs(os.path.dirname(os.path.abspath(argv[0])), exist_ok=True)
     json.dump(out, open(argv[0], "w"), indent=1)
     print("wrote", argv[0])
