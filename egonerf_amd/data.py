@@ -68,6 +68,10 @@ class RayBank:
     def __len__(self) -> int:
         return self.total
 
+    def image_of(self, idx: torch.Tensor) -> torch.Tensor:
+        """The image index of ray indices (int64, any device): idx // (n_rows * n_cols), the index space of the class docstring."""
+        return torch.div(idx, self.n_rows * self.n_cols, rounding_mode="floor")
+
     def gather(self, idx: torch.Tensor):
         """(rays [B,6], rgb [B,3]) = (all_rays[idx], all_rgbs[idx]) of the materialised arrays, bit for bit.  idx: int64 on the bank's
         device, every entry in [0, total) (not checked - that would synchronise; a row with an index outside comes back as NaN)."""

@@ -914,13 +914,24 @@ class EgoNeRF(TensorBase):
             raise NotImplementedError  # EgoNeRF.py:503-504
         else:
             rays = _f32c(rays_chunk[:, :6])
+            # d loss / d rays: defined where the sample distances do not depend on the ray; refused before any launch elsewhere
+            ray_grads = torch.is_grad_enabled() and rays.requires_grad
+            if ray_grads and not exp_sampling and not is_train:
+                raise NotImplementedError("ray gradients are not defined on the eval-mode path that measures every ray with ray 0's distances "
+                                          "(exp_sampling=False, is_train=False); render with exp_sampling=True")
+            if ray_grads and not exp_sampling:
+                raise NotImplementedError("ray gradients need exp_sampling=True: with explicit z_coarse (TensorBase.sample_ray) the sample "
+                                          "distances depend on the ray, and z is a constant of the ray gradient")
+            if ray_grads and not self.coordinates.interval_th:
+                raise NotImplementedError("ray gradients need the linearised exponential grid (interval_th=True): the plain exponential grid "
+                                          "normalises r through a truncated logarithm, whose cell the ray-gradient kernel does not re-derive")
             z_coarse, jitter, u = self._noise_plan(rays, n_coarse, n_fine, is_train, exp_sampling, resampling, jitter, u)
             if not is_train and z_coarse is not None and rays.shape[0] and not bool((z_coarse[:, 0] == z_coarse[0, 0]).all()):
                 # rays that enter the aabb at different distances: the reference places the first-pass samples per ray but
                 # measures every ray with ray 0's distances (EgoNeRF.py:515-516) - evaluated the same way, stage by stage
                 out = self._forward_eval_ray0_distances(rays, z_coarse, int(n_coarse), int(n_fine), bool(resampling),
                                                         bool(use_coarse_sample), need_alpha)
-            elif torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            elif ray_grads or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
                 # any supported shape trains: the tuned one through the MFMA kernels, the others through the fp32 compatibility kernels
                 from .train import render_train  # differentiable path: keeps activations, backward in HIP (egonerf_amd/train.py)
                 out = render_train(self, rays, n_coarse, n_fine, resampling, use_coarse_sample, jitter, u, z_coarse)

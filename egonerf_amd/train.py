@@ -10,6 +10,8 @@ bit-reproducible by default (`ego_scatter_*_sorted`; the appearance walk also pr
 atomics for `model.deterministic_scatter = False` and table shapes the sorted kernels are not built for.  The MLP weight and
 bias gradients come from `ego_weight_grad` (csrc/ego_wgrad.hip), un-permuted with the column maps of `ego_train_layout`.
 `forward` records every decision that shapes the step in one `StepPlan`; `backward` only reads it.
+Rays that require grad receive d loss / d (origin, direction) from `ego_view_grad` + `ego_ray_grad`; when they alone ask for a
+gradient (a frozen model being localised) the step has no sort, no scatter and no weight-gradient pass.
 """
 from __future__ import annotations
 
@@ -169,13 +171,14 @@ class StepPlan(NamedTuple):
     side: Optional["torch.cuda.Stream"]   # where the sort and the scatters run (None: in line)
 
 
-def _plan_step(model, sc, N: int, S: int) -> StepPlan:
+def _plan_step(model, sc, N: int, S: int, param_grads: bool = True) -> StepPlan:
+    """param_grads = False (a frozen model being localised: only the rays ask for a gradient): no sort, the backward runs no scatter."""
     M, device = N * S, model.density_plane_yin[0].device
     head_tuned = model.head_is_tuned and not model.train_fp32_head
     dens16 = model.density_n_comp[0] == 16
     # Deterministic table gradients (model.deterministic_scatter, the default): tuned table shapes only (16 / 48 components); anything
     # else keeps the atomic scatters
-    sorts = bool(model.deterministic_scatter and (dens16 or head_tuned))
+    sorts = bool(param_grads and model.deterministic_scatter and (dens16 or head_tuned))
     walk = _generic_head_sorted_app(model, sorts or None, M)
     walk_basis = bool(head_tuned and WALK_BASIS and walk)
     compat = None
@@ -312,20 +315,23 @@ def _scatter_tables(plan: StepPlan, sc, sv, side: SideStream, kind: str, d, g_ta
     side.run(lambda s: _chk(call(s), what))
 
 
-def _head_backward_tuned(plan: StepPlan, sc, sv, dc, g_app, side: SideStream) -> dict:
+def _head_backward_tuned(plan: StepPlan, sc, sv, dc, g_app, side: SideStream, scatter: bool = True) -> dict:
     """ego_shade_backward, then the appearance scatter on the side stream -> what the weight gradients read.  dh2 / dh1: scaled fp16 in
-    the kernel's own operand order + one power of two per sample (include/egonerf_hip.h); dv: blocked fp32, not written with walk_dv."""
+    the kernel's own operand order + one power of two per sample (include/egonerf_hip.h); dv: blocked fp32, not written with walk_dv.
+    scatter = False (no parameter asks for a gradient): the data gradients only - no dv, no product buffer, no scatter."""
     lib, st, dev, M, Mp = _lib.load(), _lib.stream_handle(), dc.device, plan.M, plan.Mp
     tp = _empty(dev, lib.ego_train_packed_floats())
     _chk(lib.ego_pack_train(sc, tp.data_ptr(), st), "ego_pack_train")
     f16 = lambda *shape: _empty(dev, *shape, dtype=torch.float16)
     hb = dict(dh2=f16(Mp, 128), dh1=f16(Mp, 128), dh_scale=_empty(dev, 2, Mp), dfe=_empty(dev, M, 32))
-    dv = None if plan.walk_dv else _empty(dev, Mp, 144)
+    dv = None if plan.walk_dv or not scatter else _empty(dev, Mp, 144)
     # max |dv| (walk_dv: max |dfe|), found by the backward while it holds the values: the sorted scatter's fixed-point unit comes from it
     hb["dv_absmax"] = _empty(dev, 1)
     _chk(lib.ego_shade_backward(sc, tp.data_ptr(), sv["coords"].data_ptr(), dc.data_ptr(), sv["rgb"].data_ptr(), C.byref(_shade_dump(sv)),
                                 hb["dh2"].data_ptr(), hb["dh1"].data_ptr(), hb["dh_scale"].data_ptr(), hb["dfe"].data_ptr(), _lib.ptr(dv),
                                 hb["dv_absmax"].data_ptr(), plan.N, plan.S, st), "ego_shade_backward")
+    if not scatter:
+        return hb
     # the product buffer exists (zero-filled, on the main stream) BEFORE the side stream is allowed to write its d(basis) block into it
     hb["Gall"] = torch.zeros(352, _G_LD, device=dev)
     walk = (hb["dv_absmax"].data_ptr(), None, None, 0)
@@ -361,7 +367,7 @@ def _weight_grads_tuned(plan: StepPlan, model, sv, hb, dc, side: SideStream) -> 
     return [t.view(shp) for t, shp in zip(Gall.view(-1).index_select(0, gidx).split(gsizes), gshapes)]
 
 
-def _head_backward_generic(plan: StepPlan, sc, model, sv, dc, g_app, side: SideStream) -> dict:
+def _head_backward_generic(plan: StepPlan, sc, model, sv, dc, g_app, side: SideStream, scatter: bool = True) -> dict:
     """Backward of the appearance head for any model shape the compatibility kernels support (row-major buffers).  Another head over the
     SHIPPED table shape: dv in the tuned scatters' blocked layout, and the sorted walk takes the table gradients (deterministic, 0.75 ms
     where the any-shape atomic scatter takes 9.8)."""
@@ -373,7 +379,8 @@ def _head_backward_generic(plan: StepPlan, sc, model, sv, dc, g_app, side: SideS
                                                 _lib.ptr(sv["h1"]), _lib.ptr(sv["h2"]), _G_LD, _lib.ptr(hb["dh2"]), _lib.ptr(hb["dh1"]),
                                                 hb["dfe"].data_ptr(), hb["dv"].data_ptr(), 0 if plan.sorted_app else _G_LD, plan.N, plan.S,
                                                 _lib.stream_handle()), "ego_shade_backward_generic")
-    _scatter_tables(plan, sc, sv, side, "app", hb["dv"], g_app)
+    if scatter:
+        _scatter_tables(plan, sc, sv, side, "app", hb["dv"], g_app)
     return hb
 
 
@@ -410,6 +417,23 @@ def _envmap_grad(sc, model, sv, g_rgb) -> torch.Tensor:
     return g_em
 
 
+def _ray_grad(plan: StepPlan, sc, model, sv, hb, dfeat, g_rgb, fine_pass: bool) -> torch.Tensor:
+    """d loss / d rays [N, 6] from what the backward has in hand: dfeat (ego_march_backward), the head's dfe and dh1, the
+    forward's coords and z.  Two launches (one for the RGB head, which has no view term), no atomics: bit-reproducible."""
+    lib, st, dev, rays = _lib.load(), _lib.stream_handle(), dfeat.device, sv["rays"]
+    d_view = None
+    if model.shadingMode != "RGB":
+        d_view = _empty(dev, plan.M, 3)
+        layout, scale = (2, hb["dh_scale"][1].data_ptr()) if plan.head_tuned else (0, None)
+        _chk(lib.ego_view_grad(sc, rays.data_ptr(), plan.S, plan.M, hb["dh1"].data_ptr(), layout, scale, d_view.data_ptr(), st), "ego_view_grad")
+    env = (g_rgb, sv["raw"], sv["bg"], sv["env"]) if sv["env"] is not None else (None,) * 4
+    g_rays = _empty(dev, plan.N, 6)
+    _chk(lib.ego_ray_grad(sc, rays.data_ptr(), sv["z"].data_ptr(), sv["coords"].data_ptr(), dfeat.data_ptr(), hb["dfe"].data_ptr(),
+                          hb["dfe"].shape[1], _lib.ptr(d_view), *(_lib.ptr(t) for t in env), plan.N, plan.S, int(fine_pass), None,
+                          g_rays.data_ptr(), st), "ego_ray_grad")
+    return g_rays
+
+
 class RenderFunction(torch.autograd.Function):
     @staticmethod
     @_lib.device_guard
@@ -423,7 +447,8 @@ class RenderFunction(torch.autograd.Function):
         sc = model.scene(training=True)
         N = rays.shape[0]
         S = _lib.sample_count(opts["n_coarse"], opts["n_fine"], opts["resampling"], opts["use_coarse_sample"])
-        plan = _plan_step(model, sc, N, S)
+        # (needs_input_grad: model, rays, opts, *params) a frozen model whose rays ask for a gradient plans a step without the sort
+        plan = _plan_step(model, sc, N, S, param_grads=any(ctx.needs_input_grad[3:]) or not ctx.needs_input_grad[1])
         b = _march(plan, sc, model, rays, opts)
         model.last_train_z = b["z"]   # the 5-tuple has no place for it; losses.distortion_loss reads it right after the render
         rgb = _empty(dev, N, S, 3)
@@ -435,7 +460,7 @@ class RenderFunction(torch.autograd.Function):
         bg_map, env_map = (_empty(dev, N, 3), _empty(dev, N, 3)) if has_env else (None, None)
         _chk(lib.ego_composite(sc, rays.data_ptr(), b["z"].data_ptr(), b["weight"].data_ptr(), b["bg"].data_ptr(), rgb.data_ptr(), N, S,
                                rgb_map.data_ptr(), depth.data_ptr(), _lib.ptr(bg_map), _lib.ptr(env_map), raw.data_ptr(), st), "ego_composite")
-        ctx.model, ctx.plan = model, plan
+        ctx.model, ctx.plan, ctx.fine_pass = model, plan, bool(opts["resampling"])
         ctx.saved = dict(b, rgb=rgb, raw=raw, env=env_map, rays=rays, sort_ws=sort_ws, **dump)
         # depth is computed under no_grad in the reference (EgoNeRF.py:595-598); one call: a second would replace the first
         if has_env:
@@ -446,17 +471,18 @@ class RenderFunction(torch.autograd.Function):
 
     @staticmethod
     @_lib.device_guard
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g_rgb, _g_depth=None, g_alpha=None, *_unused):
         model, plan, sv = ctx.model, ctx.plan, ctx.saved
         dev = sv["z"].device
+        # rays: d loss / d (origin, direction) only when asked for; params: False for a frozen model being localised, whose backward is
+        # ego_march_backward, the head's data-gradient kernel and the ray-gradient kernels - no scatter, no weight-gradient pass
+        want_rays, want_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:]) or not ctx.needs_input_grad[1]
         sc = _head_scene(model.scene(training=True), plan)
         g_rgb = torch.zeros(plan.N, 3, device=dev) if g_rgb is None else g_rgb.contiguous().float()
         if g_alpha is not None:  # ray_entropy_loss (train.py:306-309); the envmap's ones column takes no gradient
             g_alpha = g_alpha.contiguous().float()
             assert g_alpha.shape == sv["alpha"].shape
-        # keeps the channel-last strides of the parameters; the sorted scatters store every texel, the atomic ones add into zeros
-        g_dens = _zeros_like_many(table_params(model, "density"), zero=not plan.sorted_dens)
-        g_app = _zeros_like_many(table_params(model, "app"), zero=not plan.sorted_app)
         dc, dfeat = _empty(dev, plan.N, plan.S, 3), _empty(dev, plan.N, plan.S)   # d colour (-> d(pre-sigmoid) in the head backward), d density feature
         _chk(_lib.load().ego_march_backward(sc, sv["z"].data_ptr(), sv["alpha"].data_ptr(), sv["alpha"].shape[1], sv["weight"].data_ptr(),
                                             sv["sigma"].data_ptr(), sv["bg"].data_ptr(), sv["rgb"].data_ptr(), g_rgb.data_ptr(), _lib.ptr(g_alpha),
@@ -464,6 +490,13 @@ class RenderFunction(torch.autograd.Function):
                                             _lib.stream_handle()), "ego_march_backward")
         side = SideStream(plan.side, dev)
         try:
+            if not want_params:
+                head = _head_backward_tuned if plan.head_tuned else functools.partial(_head_backward_generic, model=model)
+                hb = head(plan, sc, sv=sv, dc=dc, g_app=None, side=side, scatter=False)
+                return (None, _ray_grad(plan, sc, model, sv, hb, dfeat, g_rgb, ctx.fine_pass), None, *([None] * (len(ctx.needs_input_grad) - 3)))
+            # keeps the channel-last strides of the parameters; the sorted scatters store every texel, the atomic ones add into zeros
+            g_dens = _zeros_like_many(table_params(model, "density"), zero=not plan.sorted_dens)
+            g_app = _zeros_like_many(table_params(model, "app"), zero=not plan.sorted_app)
             _scatter_tables(plan, sc, sv, side, "density", dfeat, g_dens)
             if plan.head_tuned:
                 hb = _head_backward_tuned(plan, sc, sv, dc, g_app, side)
@@ -474,8 +507,9 @@ class RenderFunction(torch.autograd.Function):
             grads = g_dens + g_app + wg
             if sv["env"] is not None:
                 grads.append(_envmap_grad(sc, model, sv, g_rgb))
+            g_rays = _ray_grad(plan, sc, model, sv, hb, dfeat, g_rgb, ctx.fine_pass) if want_rays else None
             side.join()  # the table gradients are complete
-            return (None, None, None, *grads)
+            return (None, g_rays, None, *grads)
         finally:
             # also when a call above raised: the main stream waits for the side stream before dfeat, dv / dfe (hb), coords and sort_ws
             # (sv) and the gradient buffers can go back to the main stream's allocator pool
@@ -559,6 +593,10 @@ class TrainSchedule:
         return int(self.it.item())
 
 
+_GRAPHED_RAY_GRADS = ("GraphedTrainStep copies its batch into static buffers: rays that require grad get no gradient through it "
+                      "(pose refinement runs the eager loop, egonerf_amd.poses.refine_poses)")
+
+
 class GraphedTrainStep:
     """One training iteration of train.py:245-330 — differentiable render of a ray batch, loss, backward, optimiser step with
     the per-step learning-rate decay, coarse-table refresh — captured once as a hipGraph and replayed.
@@ -606,6 +644,8 @@ class GraphedTrainStep:
             batch_source.seek(start_iteration)
         elif rays is None or target is None:
             raise ValueError("GraphedTrainStep needs an example batch (rays, target) or a batch_source")
+        if rays is not None and rays.requires_grad:
+            raise NotImplementedError(_GRAPHED_RAY_GRADS)
         self.model, self.opt, self.kw = model, optimizer, dict(render_kwargs)
         self.loss_fn = loss_fn or (lambda rgb, tgt, alpha: torch.mean((rgb - tgt) ** 2))
         # Explicit opt-in, not arity sniffing (a fourth parameter like reduction="mean" must not receive the schedule, a
@@ -663,6 +703,8 @@ class GraphedTrainStep:
         elif rays is None or target is None:
             raise ValueError("this GraphedTrainStep was built without a batch_source: call step(rays, target)")
         else:
+            if rays.requires_grad:
+                raise NotImplementedError(_GRAPHED_RAY_GRADS)
             self.rays.copy_(rays, non_blocking=True)
             self.target.copy_(target, non_blocking=True)
         self.graph.replay()

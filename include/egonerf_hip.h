@@ -737,6 +737,39 @@ int ego_feature2density_backward(const ego_scene* sc, const float* feat, int64_t
 int ego_raw2alpha_backward(const float* sigma, const float* dist, const float* alpha, int64_t N, int32_t S, const float* g_alpha, const float* g_weight,
                            const float* g_bg, float* d_sigma, float* d_dist, void* stream);
 
+/* ---- ray gradients (csrc/ego_ray_grad.hip; append-only additions, EGO_ABI_VERSION stays 17).  No reference counterpart:
+ * EgoNeRF.forward detaches the coordinates before grid_sample, so there the positional part of d loss / d rays is zero by construction. ---- */
+/* d loss / d viewdir of every sample through the head's first layer (tensorBase.py:68-75): with dx = W1^T dh1 restricted to the view columns,
+ * d_view[m][j] = dx[app_dim + j] + sum_f 2^f (cos(2^f d_j) dx[sin column] - sin(2^f d_j) dx[cos column]), d = rays[m / S][3..5], W1 =
+ * sc->mlp_w[0] (fp32, the reference's layout; the packed blob is not read).  dh1 [M][mlp_hidden] is the head backward's gradient at the first
+ * hidden layer, relu mask applied: dh_layout 0 = row-major fp32 (ego_shade_backward_generic's; 16-byte aligned, dh_scale unused), 2 =
+ * ego_shade_backward's scaled fp16 (dh_scale = row 1 of its dh_scale, [M]).  d_view [M][3] is written.  M = N S; M == 0 is a no-op; an RGB
+ * head (no network: the gradient is zero, pass d_view = NULL to ego_ray_grad instead) and other bad arguments return EGO_E_BADARG before
+ * anything is queued.  One launch, no atomics, no host synchronisation. */
+int ego_view_grad(const ego_scene* sc, const float* rays, int32_t S, int64_t M, const void* dh1, int32_t dh_layout, const float* dh_scale,
+                  float* d_view, void* stream);
+/* g_rays [N][6] = d loss / d (origin, direction) of the training render, WRITTEN (not accumulated).  The sample distances z [N][S] are
+ * constants, the chart of a sample is the forward's (coords [N][S][4], ego_march_density's coords_out; 16-byte aligned).  Per ray,
+ *   g_o = sum_s J_s^T q_s,   g_d = sum_s z_s J_s^T q_s + sum_s d_view[s] + e_n:
+ * q_s = d loss / d (r^, theta^, phi^) through both lookups - F.grid_sample's backward with respect to the grid (align_corners, zero padding:
+ *   per axis the weights' derivatives are -/+ (n - 1) / 2 on the taps that are in range) - with dfeat [M] (ego_march_backward's; the per-plane
+ *   relu mask of EgoNeRF.py:340,346 is applied here) and g_v = basis_g^T dfe re-derived per channel from dfe: [M][32] (ldfe 32,
+ *   ego_shade_backward's) or [M][64] (ldfe 64, ego_shade_backward_generic's dfe64; the half of the sample's own grid is read).  Either may
+ *   be NULL (that field contributes nothing).  The taps are re-gathered from the fp32 tables of sc->density / sc->app (n_comp a multiple of 4
+ *   up to 48, app_dim <= 32); app16 is not read.
+ * J_s = d (r^, theta^, phi^) / d xyz at xyz = o + z_s d for the chart coords.w names, the radius cell found as ego_normalize_coord finds it
+ *   (fine_pass != 0: on sc->r_lut_fine where the scene has one).  A sample with r = 0, with q_s = 0 (NaN or out-of-range coordinates mask
+ *   every tap) or a non-finite product contributes exactly 0.
+ * d_view [M][3] (ego_view_grad's) or NULL.  e_n: the envmap's direction term, d (bg_weight sigmoid(bilinear(emission, dir))) / d dir
+ *   through F.normalize, with ego_envmap_backward's clamp mask from rgb_raw; g_rgb, rgb_raw [N][3], bg_weight [N], env_map [N][3] - all
+ *   four or none (NULL without an envmap).
+ * d_xyz [M][3] optional (NULL in training): receives J_s^T q_s per sample.
+ * A ray's samples are summed in a fixed order inside one wave: no atomics, two calls return the same bits.  Any N >= 0 (0: no-op), any
+ * S >= 1, N S < 2^31; one launch, no host synchronisation. */
+int ego_ray_grad(const ego_scene* sc, const float* rays, const float* z, const float* coords, const float* dfeat, const float* dfe, int32_t ldfe,
+                 const float* d_view, const float* g_rgb, const float* rgb_raw, const float* bg_weight, const float* env_map, int64_t N, int32_t S,
+                 int32_t fine_pass, float* d_xyz, float* g_rays, void* stream);
+
 typedef struct ego_render_args {
   int32_t n_coarse, n_fine;
   int32_t resampling, use_coarse_sample;
