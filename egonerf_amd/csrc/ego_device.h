@@ -1,11 +1,13 @@
 // Device helpers shared by every kernel of libegonerf_hip.so (gfx950 only, wave64).
 // Arithmetic follows the reference's ATen op sequence rounding-by-rounding where that is cheap
 // (explicit __f*_rn so the compiler does not contract into FMAs the CPU path does not use).
+// The geometry of a vector-matrix lookup is defined here once: the axis maps and table sizes (vm_plane_x ... vm_line_elems, host and
+// device), the tap set-up with and without derivatives (lin_taps), the per-plane tap description of the fp32 tables (PlaneTaps), the
+// envmap's direction -> taps (envmap_taps) and row_sum16.  Host-side builders and checks of these structs: ego_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/egonerf_hip.h"
-#include "ego_host.h"   // ego_fail, for check_field
 
 #define EGO_WAVE 64
 
@@ -21,7 +23,7 @@ struct DevField {
   int32_t res[3];  // N_r, N_theta, N_phi
   // compact addressing for the forward gathers: the 12 tables of a field lie within 4 GB of `base` (the lowest of them), so a tap
   // is `base + 32-bit byte offset`: one scalar base register pair + one VGPR per address (global_load saddr form) instead of a
-  // per-lane 64-bit pointer select and 64-bit adds.  ego_field_is_compact() checks it on the host; the backward kernels keep
+  // per-lane 64-bit pointer select and 64-bit adds.  ego_field_is_compact() (ego_host.h) checks it on the host; the backward kernels keep
   // using the pointer arrays.
   const char* base;
   uint32_t poff[2][3];
@@ -35,65 +37,6 @@ struct DevCoords {
   int32_t n_lut;  // N_r + 1
   int32_t n_r;
 };
-
-__host__ inline DevField make_field(const ego_vm_field& f) {
-  DevField d;
-  uintptr_t lo = ~(uintptr_t)0;
-  for (int g = 0; g < 2; ++g)
-    for (int i = 0; i < 3; ++i) {
-      d.plane[g][i] = f.plane[g][i];
-      d.line[g][i] = f.line[g][i];
-      if (f.plane[g][i] && (uintptr_t)f.plane[g][i] < lo) lo = (uintptr_t)f.plane[g][i];
-      if (f.line[g][i] && (uintptr_t)f.line[g][i] < lo) lo = (uintptr_t)f.line[g][i];
-    }
-  for (int i = 0; i < 3; ++i) d.res[i] = f.res[i];
-  d.base = (const char*)lo;
-  for (int g = 0; g < 2; ++g)
-    for (int i = 0; i < 3; ++i) {
-      d.poff[g][i] = (uint32_t)((uintptr_t)f.plane[g][i] - lo);
-      d.loff[g][i] = (uint32_t)((uintptr_t)f.line[g][i] - lo);
-    }
-  return d;
-}
-
-// true iff every table of the field (elem_bytes per element, n_comp channels) ends within 4 GB of the lowest table address, i.e.
-// DevField's 32-bit byte offsets address all of it.  The host layer allocates the tables of a field from one buffer.
-__host__ inline bool ego_field_is_compact(const ego_vm_field& f, int elem_bytes) {
-  uintptr_t lo = ~(uintptr_t)0, hi = 0;
-  const int ax_x[3] = {0, 0, 1}, ax_y[3] = {1, 2, 2}, ax_l[3] = {2, 1, 0};
-  for (int g = 0; g < 2; ++g)
-    for (int i = 0; i < 3; ++i) {
-      if (!f.plane[g][i] || !f.line[g][i]) return false;
-      const uintptr_t p = (uintptr_t)f.plane[g][i], l = (uintptr_t)f.line[g][i];
-      const uintptr_t pe = p + (uintptr_t)f.res[ax_x[i]] * f.res[ax_y[i]] * f.n_comp * elem_bytes;
-      const uintptr_t le = l + (uintptr_t)f.res[ax_l[i]] * f.n_comp * elem_bytes;
-      lo = p < lo ? p : lo; lo = l < lo ? l : lo;
-      hi = pe > hi ? pe : hi; hi = le > hi ? le : hi;
-    }
-  return hi - lo < ((uintptr_t)1 << 32);
-}
-
-// what every forward gather of a density field asks of it (the entry points of ego_stages.hip and ego_march.hip)
-__host__ inline int check_field(const ego_vm_field& f, const char* what) {
-  for (int g = 0; g < 2; ++g)
-    for (int i = 0; i < 3; ++i)
-      if (!f.plane[g][i] || !f.line[g][i]) return ego_fail(EGO_E_BADARG, "%s: null table pointer", what);
-  if (f.res[0] < 2 || f.res[1] < 2 || f.res[2] < 2) return ego_fail(EGO_E_BADARG, "%s: resolution < 2", what);
-  if (!ego_field_is_compact(f, 4))
-    return ego_fail(EGO_E_BADARG, "%s: the 12 tables of a field must lie within 4 GB of each other (allocate them from one buffer): "
-                                  "the gathers address taps as base + 32-bit offset", what);
-  return EGO_OK;
-}
-
-__host__ inline DevCoords make_coords(const ego_scene& s, bool fine_pass = false) {
-  DevCoords c;
-  c.cx = s.center[0]; c.cy = s.center[1]; c.cz = s.center[2];
-  c.th_near = s.ang_near[0]; c.ph_near = s.ang_near[1];
-  c.th_inv = s.ang_inv[0]; c.ph_inv = s.ang_inv[1];
-  c.r_lut = s.r_lut; c.n_lut = s.n_r_lut; c.n_r = s.n_r;
-  if (fine_pass && s.r_lut_fine) { c.r_lut = s.r_lut_fine; c.n_lut = s.n_r_lut_fine; c.n_r = s.n_r_fine; }
-  return c;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Row A  — sample schedule -> points      models/EgoNeRF.py:56-87
@@ -171,21 +114,39 @@ struct Lin1 {
   float w0, w1;  // weights with the out-of-range taps zeroed
 };
 
-__device__ __forceinline__ Lin1 lin_setup(float xhat, int n) {
-  Lin1 t;
-  const float ix = __fmul_rn(__fadd_rn(xhat, 1.0f), 0.5f * (float)(n - 1));
+// ... plus the derivative of the two weights with respect to the normalised coordinate: -/+ (n - 1) / 2 where the tap is in range (the
+// ray gradients, csrc/ego_ray_grad.hip)
+struct LinD : Lin1 {
+  float d0, d1;
+};
+
+// The one body of the tap set-up; DERIV = false leaves d0 / d1 unset (and their instructions unwritten): lin_setup's callers
+template <bool DERIV>
+__device__ __forceinline__ LinD lin_taps(float xhat, int n) {
+  LinD t;
+  const float x1 = __fadd_rn(xhat, 1.0f), sc = 0.5f * (float)(n - 1);
+  const float ix = __fmul_rn(x1, sc);
   const float fl = floorf(ix);
   const float f = __fsub_rn(ix, fl);
   // ix may be NaN/huge for degenerate points: keep the int conversion defined and the taps masked (fmaxf(NaN, -2) = -2, so
   // a NaN lands on i0 = -2, i1 = -1: both out of range).  One unsigned compare per tap: 0 <= i < n.
   const float flc = fminf(fmaxf(fl, -2.0f), (float)n);
   const int i0 = (int)flc, i1 = i0 + 1;
-  t.w0 = ((unsigned)i0 < (unsigned)n) ? __fsub_rn(1.0f, f) : 0.0f;
-  t.w1 = ((unsigned)i1 < (unsigned)n) ? f : 0.0f;
+  const bool in0 = (unsigned)i0 < (unsigned)n;
+  t.w0 = in0 ? __fsub_rn(1.0f, f) : 0.0f;
+  const bool in1 = (unsigned)i1 < (unsigned)n;
+  t.w1 = in1 ? f : 0.0f;
+  if (DERIV) {
+    t.d0 = in0 ? -sc : 0.0f;
+    t.d1 = in1 ? sc : 0.0f;
+  }
   t.i0 = min(max(i0, 0), n - 1);
   t.i1 = min(max(i1, 0), n - 1);
   return t;
 }
+
+__device__ __forceinline__ Lin1 lin_setup(float xhat, int n) { return lin_taps<false>(xhat, n); }
+__device__ __forceinline__ LinD lind_setup(float xhat, int n) { return lin_taps<true>(xhat, n); }
 
 // The three (plane, line) lookups of one grid address these axes (matMode / vecMode, EgoNeRF.py:30-33):
 //   i=0: plane x=r (W=N_r), y=theta (H=N_theta); line = phi
@@ -203,9 +164,62 @@ __device__ __forceinline__ VMTaps vm_setup(float a_r, float a_th, float a_ph, co
   return t;
 }
 
-__device__ __forceinline__ constexpr int vm_plane_x(int i) { return i == 2 ? 1 : 0; }
-__device__ __forceinline__ constexpr int vm_plane_y(int i) { return i == 0 ? 1 : 2; }
-__device__ __forceinline__ constexpr int vm_line_ax(int i) { return 2 - i; }
+// The axis maps and table sizes, for host and device code alike: the ONE place that says which axes a table spans.  The maps are
+// expressions first (macros) and functions over them: k_scatter_generic (csrc/ego_generic_train.hip), where the plane index is a
+// run-time value, needs the expression in its own text - a call, even a force-inlined one, is folded later and its code comes out different.
+#define VM_PLANE_X(i) ((i) == 2 ? 1 : 0)
+#define VM_PLANE_Y(i) ((i) == 0 ? 1 : 2)
+#define VM_LINE_AX(i) (2 - (i))
+__host__ __device__ __forceinline__ constexpr int vm_plane_x(int i) { return VM_PLANE_X(i); }
+__host__ __device__ __forceinline__ constexpr int vm_plane_y(int i) { return VM_PLANE_Y(i); }
+__host__ __device__ __forceinline__ constexpr int vm_line_ax(int i) { return VM_LINE_AX(i); }
+// elements of plane i, [res[y axis]][res[x axis]][n_comp], and of line i, [res[line axis]][n_comp]
+__host__ __device__ __forceinline__ constexpr int64_t vm_plane_elems(const int32_t res[3], int n_comp, int i) {
+  return (int64_t)res[vm_plane_y(i)] * res[vm_plane_x(i)] * n_comp;
+}
+__host__ __device__ __forceinline__ constexpr int64_t vm_line_elems(const int32_t res[3], int n_comp, int i) {
+  return (int64_t)res[vm_line_ax(i)] * n_comp;
+}
+
+// Plane i of one sample's lookup in channel-last fp32 tables of C channels, described once for the fp32 compatibility, stage and
+// ray-gradient kernels, whatever their work split: the plane and line table of the sample's grid, the ELEMENT offsets of the four bilinear
+// taps (o<y><x>) and the two line taps (what a scatter applies to the gradient tables too), the same six taps as pointers (thread =
+// sample consumers step through them 16 bytes at a time), the four bilinear weights and the two line weights.  Channel c of a tap is
+// P[o + c] = p[c].  Nothing a consumer does not read costs an instruction.  The tuned shade / march / scatter / sorted-walk kernels
+// keep their own forms on purpose: base + 32-bit offset, run merging.
+struct PlaneTaps {
+  const float* P;
+  const float* L;
+  int64_t o00, o01, o10, o11, ol0, ol1;
+  const float *p00, *p01, *p10, *p11, *l0, *l1;
+  float w00, w01, w10, w11, wl0, wl1;
+};
+
+// channels c4 .. c4 + 3 of a tap as one 16-byte load (thread = sample consumers; C % 4 == 0, tables 16-byte aligned)
+__device__ __forceinline__ f32x4 tap4(const float* tap, int c4) { return *(const f32x4*)(tap + c4); }
+
+// X, Y, Ln = the taps of the plane's x axis, y axis and of the line's axis (Lin1, or LinD sliced); W = the plane's row length
+__device__ __forceinline__ PlaneTaps plane_taps(const Lin1 X, const Lin1 Y, const Lin1 Ln, int W, const float* P, const float* L, int C) {
+  PlaneTaps T;
+  T.P = P;
+  T.L = L;
+  T.o00 = ((int64_t)Y.i0 * W + X.i0) * C; T.p00 = T.P + T.o00;
+  T.o01 = ((int64_t)Y.i0 * W + X.i1) * C; T.p01 = T.P + T.o01;
+  T.o10 = ((int64_t)Y.i1 * W + X.i0) * C; T.p10 = T.P + T.o10;
+  T.o11 = ((int64_t)Y.i1 * W + X.i1) * C; T.p11 = T.P + T.o11;
+  T.ol0 = (int64_t)Ln.i0 * C; T.l0 = T.L + T.ol0;
+  T.ol1 = (int64_t)Ln.i1 * C; T.l1 = T.L + T.ol1;
+  T.w00 = __fmul_rn(Y.w0, X.w0); T.w01 = __fmul_rn(Y.w0, X.w1);
+  T.w10 = __fmul_rn(Y.w1, X.w0); T.w11 = __fmul_rn(Y.w1, X.w1);
+  T.wl0 = Ln.w0; T.wl1 = Ln.w1;
+  return T;
+}
+// ... of plane i of field F for a sample of grid g with the three axes' taps ax[3].  A macro: the field's loads have to stand in the
+// kernel's own text, after the copies of the axes - through a function that takes the field by reference, k_shade_generic and
+// k_app_bwd_prep select and hoist the table pointers differently and their code changes.
+#define EGO_PLANE_TAPS_OF(F, C, g, i, ax) \
+  plane_taps((ax)[vm_plane_x(i)], (ax)[vm_plane_y(i)], (ax)[vm_line_ax(i)], (F).res[vm_plane_x(i)], \
+             (g) ? (F).plane[1][i] : (F).plane[0][i], (g) ? (F).line[1][i] : (F).line[0][i], C)
 
 // ---------------------------------------------------------------------------------------------
 // Row M — occupancy lookup: trilinear F.grid_sample (align_corners, zeros) on a {0,1} volume [N_phi][N_theta][N_r]
@@ -243,14 +257,6 @@ __device__ __forceinline__ bool occ_occupied(const DevOcc& O, int g, float a_r, 
     }
   }
   return occ_sample(O, g, a_r, a_th, a_ph) > 0.f;
-}
-
-__host__ inline DevOcc make_occ(const ego_scene& sc, int coarse) {
-  DevOcc o;
-  o.vol = coarse ? nullptr : sc.occ;  // the coarse (proposal) pass always sees the full field
-  o.res[0] = sc.occ_res[0]; o.res[1] = sc.occ_res[1]; o.res[2] = sc.occ_res[2];
-  o.cell = (o.vol && o.res[0] >= 2 && o.res[1] >= 2 && o.res[2] >= 2) ? sc.occ_cell : nullptr;
-  return o;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -330,15 +336,29 @@ __device__ __forceinline__ float wave_scan_mul(float v, int /*lane*/) {
   return v;
 }
 
-// Row J - environment map (models/envmap.py:6-14, 26-34): bilinear lookup of the sigmoid-ed emission in direction (dx, dy, dz)
-__device__ __forceinline__ void envmap_lookup(const float* __restrict__ em, int h, float dx, float dy, float dz,
-                                              float out[3]) {
+// Row J - environment map (models/envmap.py:6-14, 26-34).  Direction -> taps in the emission [3][2h][h]: F.normalize, u = (n_z + 1) / 2
+// on the h-wide axis, v = (atan2(n_y, n_x) + pi) / 2 pi on the 2h axis.  One body for the lookup, its backward into the emission
+// (k_envmap_bwd, csrc/ego_stages.hip) and its direction gradient (csrc/ego_ray_grad.hip), which also reads n, |d| and the derivatives.
+struct EnvTaps {
+  float nx, ny, nz, nrm;
+  LinD X, Y;
+};
+
+__device__ __forceinline__ EnvTaps envmap_taps(float dx, float dy, float dz, int h) {
   const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), 1e-12f);
   const float nx = __fdiv_rn(dx, nrm), ny = __fdiv_rn(dy, nrm), nz = __fdiv_rn(dz, nrm);
   const float u = __fmul_rn(__fadd_rn(nz, 1.f), 0.5f);
   const float v = __fdiv_rn(__fadd_rn(atan2f(ny, nx), 3.14159265358979323846f), 6.28318530717958647692f);
-  const Lin1 X = lin_setup(__fsub_rn(__fmul_rn(u, 2.f), 1.f), h);       // u indexes the h-wide axis
-  const Lin1 Y = lin_setup(__fsub_rn(__fmul_rn(v, 2.f), 1.f), 2 * h);   // v indexes the 2h axis
+  return EnvTaps{nx, ny, nz, nrm,
+                 lind_setup(__fsub_rn(__fmul_rn(u, 2.f), 1.f), h),        // u indexes the h-wide axis
+                 lind_setup(__fsub_rn(__fmul_rn(v, 2.f), 1.f), 2 * h)};   // v indexes the 2h axis
+}
+
+// bilinear lookup of the sigmoid-ed emission in direction (dx, dy, dz)
+__device__ __forceinline__ void envmap_lookup(const float* __restrict__ em, int h, float dx, float dy, float dz,
+                                              float out[3]) {
+  const EnvTaps t = envmap_taps(dx, dy, dz, h);
+  const Lin1 &X = t.X, &Y = t.Y;
   const float w00 = __fmul_rn(Y.w0, X.w0), w01 = __fmul_rn(Y.w0, X.w1), w10 = __fmul_rn(Y.w1, X.w0),
               w11 = __fmul_rn(Y.w1, X.w1);
 #pragma unroll
@@ -372,5 +392,14 @@ __device__ __forceinline__ void erp_ray(int H, int W, int row, int col, const fl
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// sum over the 16 lanes of a row on the DPP path (every lane gets the total; a fixed order)
+__device__ __forceinline__ float row_sum16(float v) {
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // row_half_mirror
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));   // row_mirror
   return v;
 }

@@ -13,6 +13,5 @@ int ego_generic_mlp_fea(const ego_scene* sc, const float* viewdirs, const float*
 int ego_generic_march(const ego_scene* sc, const ego_vm_field& f, bool fine_lut, const float* rays, int64_t N, int32_t S, const float* z_in,
                       const float* r_sched, const float* jitter, float near_, const uint8_t* occ, float* z_out, float* alpha, int32_t alpha_stride,
                       float* weight, float* bg_weight, float* coords_out, float* sigma_out, uint8_t* tile_active, void* stream);
-// the envelope of the any-shape kernels (defined in ego_generic.hip, asked by the entry points of all three sources): EGO_OK or the refusal
-int check_generic_n_comp(int C, const char* who, const char* which = "");   // a table's component count: a multiple of 4 up to 48
+// the envelope of the any-shape kernels (ego_generic.hip, over the shared checks of ego_host.h; asked by all three sources): EGO_OK or the refusal
 int check_generic_shape(const ego_scene* sc, const char* who, bool need_tables, bool need_mlp, bool need_packed = true);

@@ -138,21 +138,10 @@ __global__ __launch_bounds__(128) void k_shade_generic(GenShadeArgs A) {
       const GenGridMask gm = gen_grid_mask(g, l31);
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const Lin1 X = t.ax[vm_plane_x(i)], Y = t.ax[vm_plane_y(i)], Ln = t.ax[vm_line_ax(i)];
-        const int W = A.F.res[vm_plane_x(i)];
-        const float* P = g ? A.F.plane[1][i] : A.F.plane[0][i];
-        const float* Lp = g ? A.F.line[1][i] : A.F.line[0][i];
-        const float* p00 = P + ((int64_t)Y.i0 * W + X.i0) * C;
-        const float* p01 = P + ((int64_t)Y.i0 * W + X.i1) * C;
-        const float* p10 = P + ((int64_t)Y.i1 * W + X.i0) * C;
-        const float* p11 = P + ((int64_t)Y.i1 * W + X.i1) * C;
-        const float* l0 = Lp + (int64_t)Ln.i0 * C;
-        const float* l1 = Lp + (int64_t)Ln.i1 * C;
-        const float w00 = __fmul_rn(Y.w0, X.w0), w01 = __fmul_rn(Y.w0, X.w1), w10 = __fmul_rn(Y.w1, X.w0), w11 = __fmul_rn(Y.w1, X.w1);
+        const PlaneTaps T = EGO_PLANE_TAPS_OF(A.F, C, g, i, t.ax);
         for (int c4 = 0; c4 < C; c4 += 4) {
-          const f32x4 pv = *(const f32x4*)(p00 + c4) * w00 + *(const f32x4*)(p01 + c4) * w01 + *(const f32x4*)(p10 + c4) * w10 +
-                           *(const f32x4*)(p11 + c4) * w11;
-          const f32x4 lv = *(const f32x4*)(l0 + c4) * Ln.w0 + *(const f32x4*)(l1 + c4) * Ln.w1;
+          const f32x4 pv = tap4(T.p00, c4) * T.w00 + tap4(T.p01, c4) * T.w01 + tap4(T.p10, c4) * T.w10 + tap4(T.p11, c4) * T.w11;
+          const f32x4 lv = tap4(T.l0, c4) * T.wl0 + tap4(T.l1, c4) * T.wl1;
           const f32x4 pr = pv * lv;
           if (DUMP && valid) *(f32x4*)(dump_v + m * A.ldv + i * C + c4) = pr;
 #pragma unroll
@@ -333,33 +322,18 @@ __global__ __launch_bounds__(128) void k_shade_generic(GenShadeArgs A) {
 
 }  // namespace
 
-int check_generic_n_comp(int C, const char* who, const char* which) {
-  if (C < 4 || C > 48 || (C & 3)) return ego_fail(EGO_E_UNSUPPORTED, "%s: %sn_comp %d (supported: multiples of 4 up to 48)", who, which, C);
-  return EGO_OK;
-}
-
 int check_generic_shape(const ego_scene* sc, const char* who, bool need_tables, bool need_mlp, bool need_packed) {
   if (!sc) return ego_fail(EGO_E_BADARG, "%s: null scene", who);
-  if (sc->app_dim < 1 || sc->app_dim > 32) return ego_fail(EGO_E_UNSUPPORTED, "%s: app_dim %d (supported: 1..32)", who, sc->app_dim);
+  const bool rgb_head = sc->head == EGO_HEAD_RGB;   // tensorBase.py:194-196: `assert self.app_dim == 3`; no MLP
+  if (int e = check_head_shape(sc, who, EGO_E_UNSUPPORTED, !rgb_head, need_mlp)) return e;
   if (int e = check_generic_n_comp(sc->app.n_comp, who, "appearance ")) return e;
-  if (sc->head != EGO_HEAD_MLP_FEA && sc->head != EGO_HEAD_RGB) return ego_fail(EGO_E_BADARG, "%s: scene.head %d (EGO_HEAD_MLP_FEA or EGO_HEAD_RGB)", who, sc->head);
-  if (sc->head == EGO_HEAD_RGB) {   // tensorBase.py:194-196: `assert self.app_dim == 3`; no MLP
+  if (sc->head != EGO_HEAD_MLP_FEA && !rgb_head) return ego_fail(EGO_E_BADARG, "%s: scene.head %d (EGO_HEAD_MLP_FEA or EGO_HEAD_RGB)", who, sc->head);
+  if (rgb_head) {
     if (sc->app_dim != 3) return ego_fail(EGO_E_BADARG, "%s: the RGB head needs app_dim == 3 (got %d)", who, sc->app_dim);
     if (sc->mlp_in != 0 || sc->mlp_hidden != 0) return ego_fail(EGO_E_BADARG, "%s: the RGB head has no MLP (mlp_in / mlp_hidden must be 0)", who);
-    need_mlp = false;
-  } else if (sc->mlp_hidden != 64 && sc->mlp_hidden != 128) return ego_fail(EGO_E_UNSUPPORTED, "%s: featureC %d (supported: 64, 128)", who, sc->mlp_hidden);
-  if (need_tables) {
-    for (int g = 0; g < 2; ++g)
-      for (int i = 0; i < 3; ++i)
-        if (!sc->app.plane[g][i] || !sc->app.line[g][i]) return ego_fail(EGO_E_BADARG, "%s: null appearance table", who);
-    if (sc->app.res[0] < 2 || sc->app.res[1] < 2 || sc->app.res[2] < 2) return ego_fail(EGO_E_BADARG, "%s: appearance resolution < 2", who);
   }
-  if (need_mlp) {
-    if (sc->view_pe < 0 || sc->view_pe > 8 || sc->fea_pe < 0 || sc->fea_pe > 8)
-      return ego_fail(EGO_E_UNSUPPORTED, "%s: view_pe %d / fea_pe %d (supported: 0..8)", who, sc->view_pe, sc->fea_pe);
-    const int in_c = 2 * sc->view_pe * 3 + 2 * sc->fea_pe * sc->app_dim + 3 + sc->app_dim;
-    if (sc->mlp_in != in_c) return ego_fail(EGO_E_BADARG, "%s: mlp_in %d does not match the encoding widths (%d)", who, sc->mlp_in, in_c);
-  }
+  if (need_tables)
+    if (int e = check_vm_field(sc->app, who, "appearance ", false, false)) return e;
   if (need_packed && !sc->packed) return ego_fail(EGO_E_BADARG, "%s: scene.packed is null (call ego_pack_mlp first)", who);
   return EGO_OK;
 }

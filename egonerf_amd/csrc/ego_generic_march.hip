@@ -58,27 +58,18 @@ __global__ __launch_bounds__(256) void k_march_generic(GenMarchArgs A) {
     float sg = 0.f;
     if (occupied) {
 #pragma clang fp contract(fast)
+      // density_lookup (csrc/ego_stages.hip) with C at run time; spelled out: called as one shared body this kernel's tap loads are
+      // scheduled differently (125 VGPRs and 35 spilled SGPRs where this form has 145 and 4), as with sched_z above
       const VMTaps t = vm_setup(a_r, a_th, a_ph, A.F.res);
       const int g = y.yang;
       float feat = 0.f;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const Lin1 X = t.ax[vm_plane_x(i)], Y = t.ax[vm_plane_y(i)], Ln = t.ax[vm_line_ax(i)];
-        const int W = A.F.res[vm_plane_x(i)];
-        const float* P = g ? A.F.plane[1][i] : A.F.plane[0][i];
-        const float* Lp = g ? A.F.line[1][i] : A.F.line[0][i];
-        const float* p00 = P + ((int64_t)Y.i0 * W + X.i0) * C;
-        const float* p01 = P + ((int64_t)Y.i0 * W + X.i1) * C;
-        const float* p10 = P + ((int64_t)Y.i1 * W + X.i0) * C;
-        const float* p11 = P + ((int64_t)Y.i1 * W + X.i1) * C;
-        const float* l0 = Lp + (int64_t)Ln.i0 * C;
-        const float* l1 = Lp + (int64_t)Ln.i1 * C;
-        const float w00 = __fmul_rn(Y.w0, X.w0), w01 = __fmul_rn(Y.w0, X.w1), w10 = __fmul_rn(Y.w1, X.w0), w11 = __fmul_rn(Y.w1, X.w1);
+        const PlaneTaps T = EGO_PLANE_TAPS_OF(A.F, C, g, i, t.ax);
         float dot = 0.f;
         for (int c4 = 0; c4 < C; c4 += 4) {
-          const f32x4 pv = *(const f32x4*)(p00 + c4) * w00 + *(const f32x4*)(p01 + c4) * w01 + *(const f32x4*)(p10 + c4) * w10 +
-                           *(const f32x4*)(p11 + c4) * w11;
-          const f32x4 lv = *(const f32x4*)(l0 + c4) * Ln.w0 + *(const f32x4*)(l1 + c4) * Ln.w1;
+          const f32x4 pv = tap4(T.p00, c4) * T.w00 + tap4(T.p01, c4) * T.w01 + tap4(T.p10, c4) * T.w10 + tap4(T.p11, c4) * T.w11;
+          const f32x4 lv = tap4(T.l0, c4) * T.wl0 + tap4(T.l1, c4) * T.wl1;
           const f32x4 mm = pv * lv;
           dot += (mm.x + mm.y) + (mm.z + mm.w);
         }

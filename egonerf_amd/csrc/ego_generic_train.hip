@@ -1,5 +1,6 @@
 // libegonerf_hip.so, part 7 (ego_generic.hip), training of the other model shapes: backward of rows F, G (k_shade_generic_bwd) and of
-// the VM lookups (k_scatter_generic), plain fp32; the training forward is the dumping k_shade_generic of ego_generic.hip.
+// the VM lookups (k_scatter_generic), plain fp32; the training forward is the dumping k_shade_generic of ego_generic.hip.  Tap addresses
+// and weights: PlaneTaps (ego_device.h), as in the forward; the field and head checks: ego_host.h.
 #include "ego_device.h"
 #include "ego_host.h"
 #include "ego_generic.h"
@@ -246,15 +247,6 @@ struct GenScatterArgs {
   int32_t C, ldd;
 };
 
-// sum over the 16 lanes of a row on the DPP path (every lane gets the total)
-__device__ __forceinline__ float gen_row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));   // row_mirror
-  return v;
-}
-
 // A 16-lane group per (sample, plane), lane = channel (16 at a time): every gather and every atomic of a group is one 64-byte line, as in
 // the tuned k_vm_scatter (ego_train.hip) but without its run merging.  (Rounds 2-5 had a THREAD per (sample, plane): 64 lanes = 64 texels
 // = 64 lines per atomic instruction, 105 ms for the shipped tables at 8192 x 256 - 71 % of a training step of the other heads.)
@@ -274,44 +266,40 @@ __global__ __launch_bounds__(256) void k_scatter_generic(GenScatterArgs A) {
     const f32x4 cc = ((const f32x4*)A.coords)[m];
     const int g = cc.w != 0.f;
     const VMTaps t = vm_setup(cc.x, cc.y, cc.z, A.F.res);
-    const Lin1 X = t.ax[i == 2 ? 1 : 0], Y = t.ax[i == 0 ? 1 : 2], Ln = t.ax[2 - i];
-    const int W = A.F.res[i == 2 ? 1 : 0];
-    const float* P = g ? A.F.plane[1][i] : A.F.plane[0][i];
-    const float* Lp = g ? A.F.line[1][i] : A.F.line[0][i];
+    // (i is a run-time value here: the axis maps as expressions, ego_device.h)
+    const PlaneTaps T = plane_taps(t.ax[VM_PLANE_X(i)], t.ax[VM_PLANE_Y(i)], t.ax[VM_LINE_AX(i)], A.F.res[VM_PLANE_X(i)],
+                                   g ? A.F.plane[1][i] : A.F.plane[0][i], g ? A.F.line[1][i] : A.F.line[0][i], C);
     float* GP = g ? A.gplane[1][i] : A.gplane[0][i];
     float* GL = g ? A.gline[1][i] : A.gline[0][i];
-    const int64_t o00 = ((int64_t)Y.i0 * W + X.i0) * C, o01 = ((int64_t)Y.i0 * W + X.i1) * C, o10 = ((int64_t)Y.i1 * W + X.i0) * C,
-                  o11 = ((int64_t)Y.i1 * W + X.i1) * C, ol0 = (int64_t)Ln.i0 * C, ol1 = (int64_t)Ln.i1 * C;
-    const float w00 = __fmul_rn(Y.w0, X.w0), w01 = __fmul_rn(Y.w0, X.w1), w10 = __fmul_rn(Y.w1, X.w0), w11 = __fmul_rn(Y.w1, X.w1);
     if (dens) {   // relu per plane (EgoNeRF.py:340,346): the gradient passes where this plane's sum over channels is positive
       float dot = 0.f;
       for (int c0 = 0; c0 < C; c0 += 16) {
         const int ch = c0 + c16;
         if (ch < C) {
-          const float pv = P[o00 + ch] * w00 + P[o01 + ch] * w01 + P[o10 + ch] * w10 + P[o11 + ch] * w11;
-          const float lv = Lp[ol0 + ch] * Ln.w0 + Lp[ol1 + ch] * Ln.w1;
+          const float pv = T.P[T.o00 + ch] * T.w00 + T.P[T.o01 + ch] * T.w01 + T.P[T.o10 + ch] * T.w10 + T.P[T.o11 + ch] * T.w11;
+          const float lv = T.L[T.ol0 + ch] * T.wl0 + T.L[T.ol1 + ch] * T.wl1;
           dot += pv * lv;
         }
       }
-      dot = gen_row_sum16(dot);
+      dot = row_sum16(dot);
       if (!(dot > 0.f)) continue;
     }
     for (int c0 = 0; c0 < C; c0 += 16) {
       const int ch = c0 + c16;
       if (ch >= C) continue;
-      const float pv = P[o00 + ch] * w00 + P[o01 + ch] * w01 + P[o10 + ch] * w10 + P[o11 + ch] * w11;
-      const float lv = Lp[ol0 + ch] * Ln.w0 + Lp[ol1 + ch] * Ln.w1;
+      const float pv = T.P[T.o00 + ch] * T.w00 + T.P[T.o01 + ch] * T.w01 + T.P[T.o10 + ch] * T.w10 + T.P[T.o11 + ch] * T.w11;
+      const float lv = T.L[T.ol0 + ch] * T.wl0 + T.L[T.ol1 + ch] * T.wl1;
       const float di = dens ? ds : A.d[m * A.ldd + i * C + ch];
       const float gp = di * lv, gl = di * pv;
       if (gp != 0.f) {
-        if (w00 != 0.f) unsafeAtomicAdd(GP + o00 + ch, gp * w00);
-        if (w01 != 0.f) unsafeAtomicAdd(GP + o01 + ch, gp * w01);
-        if (w10 != 0.f) unsafeAtomicAdd(GP + o10 + ch, gp * w10);
-        if (w11 != 0.f) unsafeAtomicAdd(GP + o11 + ch, gp * w11);
+        if (T.w00 != 0.f) unsafeAtomicAdd(GP + T.o00 + ch, gp * T.w00);
+        if (T.w01 != 0.f) unsafeAtomicAdd(GP + T.o01 + ch, gp * T.w01);
+        if (T.w10 != 0.f) unsafeAtomicAdd(GP + T.o10 + ch, gp * T.w10);
+        if (T.w11 != 0.f) unsafeAtomicAdd(GP + T.o11 + ch, gp * T.w11);
       }
       if (gl != 0.f) {
-        if (Ln.w0 != 0.f) unsafeAtomicAdd(GL + ol0 + ch, gl * Ln.w0);
-        if (Ln.w1 != 0.f) unsafeAtomicAdd(GL + ol1 + ch, gl * Ln.w1);
+        if (T.wl0 != 0.f) unsafeAtomicAdd(GL + T.ol0 + ch, gl * T.wl0);
+        if (T.wl1 != 0.f) unsafeAtomicAdd(GL + T.ol1 + ch, gl * T.wl1);
       }
     }
   }
@@ -350,15 +338,13 @@ int ego_scatter_generic(const ego_vm_field* field, const ego_vm_grad* grad, cons
   if (N == 0) return EGO_OK;
   EGO_REQUIRE(coords && d, "scatter_generic: null argument");
   const int C = field->n_comp;
-  if (int e = check_generic_n_comp(C, "scatter_generic")) return e;
+  if (int e = check_vm_field(*field, "scatter_generic", "", false, true, false)) return e;   // (any resolution, as ever)
+  EGO_REQUIRE(vm_tables_complete(*grad), "scatter_generic: null table");
   EGO_REQUIRE(ldd == 0 || (ldd >= 3 * C && (ldd & 3) == 0 && ((uintptr_t)d & 15) == 0), "scatter_generic: ldd must be 0 (density) or >= 3 C, a multiple of 4");
   GenScatterArgs a{};
   a.F = make_field(*field);
   for (int g = 0; g < 2; ++g)
-    for (int i = 0; i < 3; ++i) {
-      EGO_REQUIRE(field->plane[g][i] && field->line[g][i] && grad->plane[g][i] && grad->line[g][i], "scatter_generic: null table");
-      a.gplane[g][i] = grad->plane[g][i]; a.gline[g][i] = grad->line[g][i];
-    }
+    for (int i = 0; i < 3; ++i) { a.gplane[g][i] = grad->plane[g][i]; a.gline[g][i] = grad->line[g][i]; }
   a.coords = coords; a.d = d; a.M = N * (int64_t)S; a.C = C; a.ldd = ldd;
   const int64_t n = a.M * 3, blocks = (n + 15) / 16;   // 16 groups of 16 lanes per workgroup
   k_scatter_generic<<<(unsigned)(blocks < (1 << 20) ? (blocks > 0 ? blocks : 1) : (1 << 20)), 256, 0, (hipStream_t)stream>>>(a);

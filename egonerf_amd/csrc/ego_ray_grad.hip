@@ -3,45 +3,12 @@
 //   k_view_grad  d loss / d viewdir per sample through the head's first layer and the view encodings (tensorBase.py:68-75)
 //   k_ray_grad   d loss / d (r^, theta^, phi^) per sample through both VM lookups (F.grid_sample's backward with respect to the grid),
 //                the chart's Jacobian back to xyz, and the per-ray sums; the envmap's direction term
+// lind_setup, PlaneTaps, envmap_taps and row_sum16 are ego_device.h's: the same definitions the forward lookups use.
 #include "ego_device.h"
 #include "ego_host.h"
 #include "ego_generic.h"
 
 namespace {
-
-// lin_setup (ego_device.h) plus the derivative of the two weights with respect to the normalised coordinate: -/+ (n - 1) / 2 where
-// the tap is in range, with lin_setup's own masks (a NaN lands on i0 = -2, i1 = -1: everything masked)
-struct LinD {
-  int i0, i1;
-  float w0, w1, d0, d1;
-};
-
-__device__ __forceinline__ LinD lind_setup(float xhat, int n) {
-  LinD t;
-  const float sc = 0.5f * (float)(n - 1);
-  const float ix = __fmul_rn(__fadd_rn(xhat, 1.0f), sc);
-  const float fl = floorf(ix);
-  const float f = __fsub_rn(ix, fl);
-  const float flc = fminf(fmaxf(fl, -2.0f), (float)n);
-  const int i0 = (int)flc, i1 = i0 + 1;
-  const bool in0 = (unsigned)i0 < (unsigned)n, in1 = (unsigned)i1 < (unsigned)n;
-  t.w0 = in0 ? __fsub_rn(1.0f, f) : 0.0f;
-  t.w1 = in1 ? f : 0.0f;
-  t.d0 = in0 ? -sc : 0.0f;
-  t.d1 = in1 ? sc : 0.0f;
-  t.i0 = min(max(i0, 0), n - 1);
-  t.i1 = min(max(i1, 0), n - 1);
-  return t;
-}
-
-// sum over the 16 lanes of a row on the DPP path (every lane gets the total; a fixed order)
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));   // row_mirror
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // d loss / d viewdir.  x = [feat | view | sin, cos(feat pe) | sin, cos(view pe)] (tensorBase.py:68-75), dx = W1^T dh1, and
@@ -151,16 +118,12 @@ template <bool DENS>
 __device__ __forceinline__ float plane_terms(const DevField& F, int C, int g, int i, const LinD (&ax)[3], int c16, const float* basis_g,
                                              const f32x4 (&dk)[8], float (&q)[3]) {
   const LinD X = ax[vm_plane_x(i)], Y = ax[vm_plane_y(i)], Ln = ax[vm_line_ax(i)];
-  const int W = F.res[vm_plane_x(i)];
-  const float* P = g ? F.plane[1][i] : F.plane[0][i];
-  const float* Lp = g ? F.line[1][i] : F.line[0][i];
-  const int64_t o00 = ((int64_t)Y.i0 * W + X.i0) * C, o01 = ((int64_t)Y.i0 * W + X.i1) * C, o10 = ((int64_t)Y.i1 * W + X.i0) * C,
-                o11 = ((int64_t)Y.i1 * W + X.i1) * C, ol0 = (int64_t)Ln.i0 * C, ol1 = (int64_t)Ln.i1 * C;
+  const PlaneTaps T = EGO_PLANE_TAPS_OF(F, C, g, i, ax);
   float dot = 0.f;
   for (int c0 = 0; c0 < C; c0 += 16) {
     const int ch = c0 + c16;
     if (ch >= C) continue;
-    const float p00 = P[o00 + ch], p01 = P[o01 + ch], p10 = P[o10 + ch], p11 = P[o11 + ch], l0 = Lp[ol0 + ch], l1 = Lp[ol1 + ch];
+    const float p00 = T.P[T.o00 + ch], p01 = T.P[T.o01 + ch], p10 = T.P[T.o10 + ch], p11 = T.P[T.o11 + ch], l0 = T.L[T.ol0 + ch], l1 = T.L[T.ol1 + ch];
     float gv = 1.f;
     if (!DENS) {
       gv = 0.f;
@@ -220,11 +183,9 @@ __device__ __forceinline__ void envmap_dir_grad(const RayGradArgs& A, int64_t n,
   out[0] = out[1] = out[2] = 0.f;
   const int h = A.envmap_h;
   const float dx = A.rays[n * 6 + 3], dy = A.rays[n * 6 + 4], dz = A.rays[n * 6 + 5];
-  const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), 1e-12f);
-  const float nx = __fdiv_rn(dx, nrm), ny = __fdiv_rn(dy, nrm), nz = __fdiv_rn(dz, nrm);
-  const float u = __fmul_rn(__fadd_rn(nz, 1.f), 0.5f);
-  const float v = __fdiv_rn(__fadd_rn(atan2f(ny, nx), 3.14159265358979323846f), 6.28318530717958647692f);
-  const LinD X = lind_setup(__fsub_rn(__fmul_rn(u, 2.f), 1.f), h), Y = lind_setup(__fsub_rn(__fmul_rn(v, 2.f), 1.f), 2 * h);
+  const EnvTaps t = envmap_taps(dx, dy, dz, h);
+  const float nx = t.nx, ny = t.ny, nz = t.nz, nrm = t.nrm;
+  const LinD &X = t.X, &Y = t.Y;
   const float b = A.bg_weight[n];
   float gx = 0.f, gy = 0.f;   // d / d (x^, y^) of the lookup
 #pragma unroll
@@ -366,9 +327,7 @@ int ego_view_grad(const ego_scene* sc, const float* rays, int32_t S, int64_t M, 
   EGO_REQUIRE(rays && dh1 && d_view, "view_grad: null argument");
   EGO_REQUIRE(sc->head == EGO_HEAD_MLP_FEA && sc->mlp_w[0], "view_grad: the head has no network (RGB head: the view gradient is zero)");
   EGO_REQUIRE(dh_layout == 0 || dh_layout == 2, "view_grad: dh_layout must be 0 (row-major fp32) or 2 (ego_shade_backward's scaled fp16)");
-  EGO_REQUIRE((sc->mlp_hidden == 64 || sc->mlp_hidden == 128) && sc->view_pe >= 0 && sc->view_pe <= 8 && sc->fea_pe >= 0 && sc->app_dim >= 1 &&
-                  sc->mlp_in == sc->app_dim + 3 + 2 * sc->app_dim * sc->fea_pe + 6 * sc->view_pe,
-              "view_grad: unsupported head shape");
+  if (int e = check_head_shape(sc, "view_grad", EGO_E_BADARG)) return e;
   EGO_REQUIRE(dh_layout == 0 || (sc->mlp_hidden == 128 && dh_scale && ((uintptr_t)dh1 & 15) == 0),
               "view_grad: layout 2 needs 128 hidden units, dh_scale and a 16-byte aligned dh1");
   EGO_REQUIRE(dh_layout == 2 || ((uintptr_t)dh1 & 15) == 0, "view_grad: dh1 must be 16-byte aligned");
@@ -398,13 +357,11 @@ int ego_ray_grad(const ego_scene* sc, const float* rays, const float* z, const f
   EGO_REQUIRE(envs == 0 || (envs == 4 && sc->envmap && sc->envmap_h >= 2), "ray_grad: the four envmap arguments come together, with a scene that has an envmap");
   RayGradArgs a{};
   if (dfeat) {
-    if (int e = check_generic_n_comp(sc->density.n_comp, "ray_grad", "density ")) return e;
-    if (int e = check_field(sc->density, "ray_grad (density)")) return e;
+    if (int e = check_vm_field(sc->density, "ray_grad", "density ", true, true)) return e;
     a.dens = make_field(sc->density); a.Cd = sc->density.n_comp;
   }
   if (dfe) {
-    if (int e = check_generic_n_comp(sc->app.n_comp, "ray_grad", "appearance ")) return e;
-    if (int e = check_field(sc->app, "ray_grad (appearance)")) return e;
+    if (int e = check_vm_field(sc->app, "ray_grad", "appearance ", true, true)) return e;
     EGO_REQUIRE(sc->basis[0] && sc->basis[1] && sc->app_dim >= 1 && sc->app_dim <= 32, "ray_grad: basis matrices missing or app_dim > 32");
     EGO_REQUIRE(ldfe == 32 || ldfe == 64, "ray_grad: ldfe must be 32 (ego_shade_backward's dfe) or 64 (ego_shade_backward_generic's dfe64)");
     EGO_REQUIRE(((uintptr_t)dfe & 15) == 0, "ray_grad: dfe must be 16-byte aligned");

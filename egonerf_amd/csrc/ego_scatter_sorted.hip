@@ -639,15 +639,6 @@ __device__ __forceinline__ void walk_deal(const FusedArgs& F, WalkDealLds* D) {
   __syncthreads();
 }
 
-// sum over the 16 lanes of a row on the DPP path (every lane gets the total): quad_perm xor 1, xor 2, row_half_mirror, row_mirror
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));   // row_mirror
-  return v;
-}
-
 // x = hi + lo + O(2^-17 |x|) as two bf16: hi = the top 16 bits of x as they are (truncation - the residual x - hi is exact in fp32 and
 // carries what was cut), lo = that residual rounded to its top 16 bits (+ 0x8000).  Four VALU per value (and, sub, add, half a v_perm per
 // packed pair and term) where rounding both terms to nearest even takes ten: the walk is bound by VALU issue.
@@ -1176,7 +1167,7 @@ struct FinalGrids {
 inline FinalGrids final_grids(const SortGeom& G, int C) {
   int64_t texmax = 0, linemax = 0;
   for (int i = 0; i < 3; ++i) {
-    const int64_t tex = (int64_t)2 * G.res[i == 2 ? 1 : 0] * G.res[i == 0 ? 1 : 2] * (C / 4);   // plane i: x axis, y axis (vm_plane_x / _y)
+    const int64_t tex = 2 * vm_plane_elems(G.res, C / 4, i);
     texmax = tex > texmax ? tex : texmax;
     const int64_t ln = (int64_t)2 * G.res[i] * C;
     linemax = ln > linemax ? ln : linemax;
@@ -1233,7 +1224,7 @@ int launch_walk(SortedArgs a, const SortGeom& G, char* base, int64_t M, const fl
     AbsmaxArgs ab{};
     for (int g = 0; g < 2; ++g)
       for (int i = 0; i < 3; ++i) ab.plane[g][i] = a.F.plane[g][i];
-    for (int i = 0; i < 3; ++i) ab.n_plane[i] = (int64_t)G.res[i == 2 ? 1 : 0] * G.res[i == 0 ? 1 : 2] * C;
+    for (int i = 0; i < 3; ++i) ab.n_plane[i] = vm_plane_elems(G.res, C, i);
     ab.fx = fx;
     ab.part = (uint32_t*)(base + G.fx + 256);
     if (!dmax_ext) {
@@ -1304,10 +1295,10 @@ int launch_walk(SortedArgs a, const SortGeom& G, char* base, int64_t M, const fl
 // come from torch.empty in the sorted mode)
 int zero_tables(const ego_vm_field& f, const ego_vm_grad* grad, int C, hipStream_t st, const char* who) {
   if (!grad) return ego_fail(EGO_E_BADARG, "%s: null gradient struct", who);
+  if (!vm_tables_complete(*grad)) return ego_fail(EGO_E_BADARG, "%s: null table", who);
   for (int g = 0; g < 2; ++g)
     for (int i = 0; i < 3; ++i) {
-      if (!grad->plane[g][i] || !grad->line[g][i]) return ego_fail(EGO_E_BADARG, "%s: null table", who);
-      const size_t np = (size_t)f.res[i == 2 ? 1 : 0] * f.res[i == 0 ? 1 : 2] * C * 4, nl = (size_t)f.res[2 - i] * C * 4;
+      const size_t np = (size_t)vm_plane_elems(f.res, C, i) * 4, nl = (size_t)vm_line_elems(f.res, C, i) * 4;
       if (const hipError_t e = hipMemsetAsync(grad->plane[g][i], 0, np, st)) return ego_fail((int)e, "%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
       if (const hipError_t e = hipMemsetAsync(grad->line[g][i], 0, nl, st)) return ego_fail((int)e, "%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
     }

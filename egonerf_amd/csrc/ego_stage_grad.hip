@@ -12,7 +12,8 @@
 // The table gradients reuse the training step's scatters: the sorted, bit-reproducible walk (csrc/ego_scatter_sorted.hip) where the
 // tables have the shipped shape (16 density / 48 appearance components), ego_scatter_generic's float atomics otherwise.  Coordinates
 // [M][7] are turned into the scatters' [M][4] (own grid's normalised r, theta, phi + grid flag) by a small adaptor; the forward's
-// N x S samples become M x 1.  Weight gradients are ego_weight_grad_det products over row-major per-sample buffers.
+// N x S samples become M x 1.  Weight gradients are ego_weight_grad_det products over row-major per-sample buffers.  Table sizes, axis
+// maps and the tap description are ego_device.h's; the field / head / null-table checks ego_host.h's.
 #include "ego_device.h"
 #include "ego_host.h"
 #include <algorithm>
@@ -21,10 +22,6 @@ namespace {
 
 inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 constexpr int LD = 160;        // row width of the weight-gradient B operands (ego_weight_grad_det's 5 column blocks)
-// host copies of ego_device.h's axis maps (matMode / vecMode, EgoNeRF.py:30-33)
-inline int px(int i) { return i == 2 ? 1 : 0; }
-inline int py(int i) { return i == 0 ? 1 : 2; }
-inline int lax(int i) { return 2 - i; }
 
 // c7n [M][7] -> coords [M][4] = (r, theta, phi) of the sample's own grid + grid flag (EgoNeRF.py:292-296: yin iff the last column is 0)
 __global__ void k_c7n_to_coords(const float* __restrict__ c7n, int64_t M, float* __restrict__ coords) {
@@ -87,20 +84,10 @@ __global__ __launch_bounds__(256) void k_app_bwd_prep(DevField F, const float* _
   const VMTaps t = vm_setup(a0, a1, a2, F.res);
   float* vr = v + m * LD;
   for (int i = 0; i < 3; ++i) {
-    const Lin1 X = t.ax[vm_plane_x(i)], Y = t.ax[vm_plane_y(i)], Ln = t.ax[vm_line_ax(i)];
-    const int W = F.res[vm_plane_x(i)];
-    const float* P = F.plane[gr][i];
-    const float* Lp = F.line[gr][i];
-    const float* p00 = P + ((int64_t)Y.i0 * W + X.i0) * C;
-    const float* p01 = P + ((int64_t)Y.i0 * W + X.i1) * C;
-    const float* p10 = P + ((int64_t)Y.i1 * W + X.i0) * C;
-    const float* p11 = P + ((int64_t)Y.i1 * W + X.i1) * C;
-    const float* l0 = Lp + (int64_t)Ln.i0 * C;
-    const float* l1 = Lp + (int64_t)Ln.i1 * C;
-    const float w00 = __fmul_rn(Y.w0, X.w0), w01 = __fmul_rn(Y.w0, X.w1), w10 = __fmul_rn(Y.w1, X.w0), w11 = __fmul_rn(Y.w1, X.w1);
+    const PlaneTaps T = EGO_PLANE_TAPS_OF(F, C, gr, i, t.ax);
     for (int c = 0; c < C; ++c) {
-      const float pv = p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11;
-      const float lv = l0[c] * Ln.w0 + l1[c] * Ln.w1;
+      const float pv = T.p00[c] * T.w00 + T.p01[c] * T.w01 + T.p10[c] * T.w10 + T.p11[c] * T.w11;
+      const float lv = T.l0[c] * T.wl0 + T.l1[c] * T.wl1;
       const int col = i * C + c;
       vr[col] = pv * lv;
       float s = 0.f;
@@ -374,8 +361,8 @@ __global__ void k_raw2alpha_bwd(const float* __restrict__ sigma, const float* __
   }
 }
 
-int table_floats(const ego_vm_field& f, int plane, int i) {
-  return plane ? f.res[py(i)] * f.res[px(i)] * f.n_comp : f.res[lax(i)] * f.n_comp;
+int64_t table_floats(const ego_vm_field& f, int plane, int i) {
+  return plane ? vm_plane_elems(f.res, f.n_comp, i) : vm_line_elems(f.res, f.n_comp, i);
 }
 
 int zero_grad(const ego_vm_field& f, const ego_vm_grad* g, hipStream_t st) {
@@ -388,19 +375,8 @@ int zero_grad(const ego_vm_field& f, const ego_vm_grad* g, hipStream_t st) {
   return EGO_OK;
 }
 
-bool grad_complete(const ego_vm_grad* g) {
-  for (int gr = 0; gr < 2; ++gr)
-    for (int i = 0; i < 3; ++i)
-      if (!g->plane[gr][i] || !g->line[gr][i]) return false;
-  return true;
-}
-
-bool field_complete(const ego_vm_field& f) {
-  for (int gr = 0; gr < 2; ++gr)
-    for (int i = 0; i < 3; ++i)
-      if (!f.plane[gr][i] || !f.line[gr][i]) return false;
-  return f.n_comp >= 4 && f.n_comp <= 48 && (f.n_comp & 3) == 0 && f.res[0] >= 2 && f.res[1] >= 2 && f.res[2] >= 2;
-}
+// all tables, a component count of the any-shape envelope, resolutions >= 2 (the refusals are the callers': EGO_E_BADARG, their words)
+bool field_complete(const ego_vm_field& f) { return vm_field_fault(f, false, true) == 0; }
 
 // the sorted (bit-reproducible) walks serve the shipped table shapes
 bool density_sorted(const ego_scene* sc, int64_t M, int32_t coarse) { return !coarse && sc->density.n_comp == 16 && M < (1ll << 31); }
@@ -415,7 +391,7 @@ DensityWs density_ws(const ego_scene* sc, int64_t M, int32_t coarse) {
   if (density_sorted(sc, M, coarse)) { w.sort_bytes = ego_scatter_sorted_workspace_bytes(sc, M > 0 ? M : 1, 1); o += al256(w.sort_bytes); }
   for (int t = 0; t < 12; ++t) {
     w.coarse[t] = o;
-    if (coarse) o += al256((int64_t)table_floats(sc->density_coarse, t % 6 < 3, t % 3) * 4);
+    if (coarse) o += al256(table_floats(sc->density_coarse, t % 6 < 3, t % 3) * 4);
   }
   w.total = o;
   return w;
@@ -473,10 +449,7 @@ int check_mlp(const ego_scene* sc, int64_t M, const char* who) {
   if (!sc) return ego_fail(EGO_E_BADARG, "%s: null scene", who);
   if (M < 0 || M >= (1ll << 31)) return ego_fail(EGO_E_BADARG, "%s: bad size (0 <= M < 2^31)", who);
   if (sc->head != EGO_HEAD_MLP_FEA) return ego_fail(EGO_E_BADARG, "%s: the scene has no MLP head", who);
-  const int D = sc->app_dim;
-  if (D < 1 || D > 32 || (sc->mlp_hidden != 64 && sc->mlp_hidden != 128) || sc->view_pe < 0 || sc->view_pe > 8 || sc->fea_pe < 0 ||
-      sc->fea_pe > 8 || sc->mlp_in != D + 3 + 2 * D * sc->fea_pe + 6 * sc->view_pe)
-    return ego_fail(EGO_E_BADARG, "%s: unsupported head shape (app_dim <= 32, featureC 64 | 128, view_pe / fea_pe <= 8)", who);
+  if (int e = check_head_shape(sc, who, EGO_E_BADARG)) return e;
   for (int l = 0; l < 3; ++l)
     if (!sc->mlp_w[l] || !sc->mlp_b[l]) return ego_fail(EGO_E_BADARG, "%s: null MLP weight", who);
   return EGO_OK;
@@ -495,7 +468,7 @@ int ego_density_feature_backward(const ego_scene* sc, const float* c7n, int64_t 
                                  void* workspace, int64_t workspace_bytes, void* stream) {
   EGO_TRACE("ego_density_feature_backward");
   if (int e = check_density(sc, M, coarse, "density_feature_backward")) return e;
-  EGO_REQUIRE(gdensity && grad_complete(gdensity), "density_feature_backward: null gradient table");
+  EGO_REQUIRE(gdensity && vm_tables_complete(*gdensity), "density_feature_backward: null gradient table");
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) return zero_grad(sc->density, gdensity, st);
   EGO_REQUIRE(c7n && g && workspace && ((uintptr_t)workspace & 255) == 0, "density_feature_backward: null argument or workspace not 256-byte aligned");
@@ -523,9 +496,9 @@ int ego_density_feature_backward(const ego_scene* sc, const float* c7n, int64_t 
   for (int t = 0; t < 12; ++t) {
     const bool plane = t % 6 < 3;
     const int gr = t / 6, i = t % 3;
-    const int H = plane ? F.res[py(i)] : F.res[lax(i)], Wd = plane ? F.res[px(i)] : 1;
-    const int Hc = plane ? sc->density_coarse.res[py(i)] : sc->density_coarse.res[lax(i)];
-    const int Wc = plane ? sc->density_coarse.res[px(i)] : 1;
+    const int H = plane ? F.res[vm_plane_y(i)] : F.res[vm_line_ax(i)], Wd = plane ? F.res[vm_plane_x(i)] : 1;
+    const int Hc = plane ? sc->density_coarse.res[vm_plane_y(i)] : sc->density_coarse.res[vm_line_ax(i)];
+    const int Wc = plane ? sc->density_coarse.res[vm_plane_x(i)] : 1;
     EGO_REQUIRE(Hc == H / 2 && Wc == (plane ? Wd / 2 : 1), "density_feature_backward: density_coarse.res must be density.res / 2");
     const int64_t n = (int64_t)H * Wd * F.n_comp;
     float* dst = plane ? gdensity->plane[gr][i] : gdensity->line[gr][i];
@@ -545,7 +518,7 @@ int ego_app_feature_backward(const ego_scene* sc, const float* c7n, int64_t M, c
                              void* workspace, int64_t workspace_bytes, void* stream) {
   EGO_TRACE("ego_app_feature_backward");
   if (int e = check_app(sc, M, "app_feature_backward")) return e;
-  EGO_REQUIRE(gapp && grad_complete(gapp) && gbasis && ldg >= LD, "app_feature_backward: null gradient output or ldg < 160");
+  EGO_REQUIRE(gapp && vm_tables_complete(*gapp) && gbasis && ldg >= LD, "app_feature_backward: null gradient output or ldg < 160");
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) {
     if (hipMemsetAsync(gbasis, 0, (size_t)64 * ldg * 4, st) != hipSuccess) return ego_fail(EGO_E_BADARG, "app_feature_backward: zero fill failed");

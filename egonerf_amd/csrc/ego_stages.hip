@@ -52,7 +52,8 @@ __global__ void k_normalize_coord(DevCoords c, const float* __restrict__ c7, int
 
 // =============================================================================================
 // Row D / D' — density feature: sum_i relu(sum_c P_ic * L_ic)      models/EgoNeRF.py:291-347, 232-289
-// lane = sample; one bilinear tap = C contiguous floats (C/4 x 16-byte loads).
+// lane = sample; one bilinear tap = C contiguous floats (C/4 x 16-byte loads).  (k_march_generic, csrc/ego_generic_march.hip, holds the
+// same sum with C at run time: called from there, this body changes that kernel's load schedule.)
 // =============================================================================================
 template <int C>
 __device__ __forceinline__ float density_lookup(const DevField& F, int g, float a_r, float a_th, float a_ph) {
@@ -61,23 +62,12 @@ __device__ __forceinline__ float density_lookup(const DevField& F, int g, float 
   float feat = 0.f;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const Lin1 X = t.ax[vm_plane_x(i)], Y = t.ax[vm_plane_y(i)], Ln = t.ax[vm_line_ax(i)];
-    const int W = F.res[vm_plane_x(i)];
-    const float* P = g ? F.plane[1][i] : F.plane[0][i];
-    const float* L = g ? F.line[1][i] : F.line[0][i];
-    const f32x4* p00 = (const f32x4*)(P + ((int64_t)Y.i0 * W + X.i0) * C);
-    const f32x4* p01 = (const f32x4*)(P + ((int64_t)Y.i0 * W + X.i1) * C);
-    const f32x4* p10 = (const f32x4*)(P + ((int64_t)Y.i1 * W + X.i0) * C);
-    const f32x4* p11 = (const f32x4*)(P + ((int64_t)Y.i1 * W + X.i1) * C);
-    const f32x4* l0 = (const f32x4*)(L + (int64_t)Ln.i0 * C);
-    const f32x4* l1 = (const f32x4*)(L + (int64_t)Ln.i1 * C);
-    const float w00 = __fmul_rn(Y.w0, X.w0), w01 = __fmul_rn(Y.w0, X.w1);
-    const float w10 = __fmul_rn(Y.w1, X.w0), w11 = __fmul_rn(Y.w1, X.w1);
+    const PlaneTaps T = EGO_PLANE_TAPS_OF(F, C, g, i, t.ax);
     float dot = 0.f;
 #pragma unroll
-    for (int q = 0; q < C / 4; ++q) {
-      const f32x4 pv = p00[q] * w00 + p01[q] * w01 + p10[q] * w10 + p11[q] * w11;
-      const f32x4 lv = l0[q] * Ln.w0 + l1[q] * Ln.w1;
+    for (int c4 = 0; c4 < C; c4 += 4) {
+      const f32x4 pv = tap4(T.p00, c4) * T.w00 + tap4(T.p01, c4) * T.w01 + tap4(T.p10, c4) * T.w10 + tap4(T.p11, c4) * T.w11;
+      const f32x4 lv = tap4(T.l0, c4) * T.wl0 + tap4(T.l1, c4) * T.wl1;
       const f32x4 m = pv * lv;
       dot += (m.x + m.y) + (m.z + m.w);
     }
@@ -160,12 +150,8 @@ __global__ void k_envmap_bwd(int h, const float* __restrict__ dirs, int dstride,
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const float dx = dirs[i * dstride], dy = dirs[i * dstride + 1], dz = dirs[i * dstride + 2];
-  const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), 1e-12f);
-  const float nx = __fdiv_rn(dx, nrm), ny = __fdiv_rn(dy, nrm), nz = __fdiv_rn(dz, nrm);
-  const float u = __fmul_rn(__fadd_rn(nz, 1.f), 0.5f);
-  const float v = __fdiv_rn(__fadd_rn(atan2f(ny, nx), 3.14159265358979323846f), 6.28318530717958647692f);
-  const Lin1 X = lin_setup(__fsub_rn(__fmul_rn(u, 2.f), 1.f), h);
-  const Lin1 Y = lin_setup(__fsub_rn(__fmul_rn(v, 2.f), 1.f), 2 * h);
+  const EnvTaps t = envmap_taps(dx, dy, dz, h);
+  const Lin1 &X = t.X, &Y = t.Y;
   const float b = bgw[i];
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
@@ -456,14 +442,14 @@ int ego_avgpool_table(const float* src, int32_t H, int32_t W, int32_t C, float* 
 int ego_avgpool_field(const ego_vm_field* src, const ego_vm_field* dst, void* stream) {
   EGO_TRACE("ego_avgpool_field");
   EGO_REQUIRE(src && dst && src->n_comp >= 1 && dst->n_comp == src->n_comp, "avgpool_field: null field or component counts differ");
+  EGO_REQUIRE(vm_tables_complete(*src) && vm_tables_complete(*dst), "avgpool_field: null table");
   PoolJobs J{};
   J.C = src->n_comp; J.n = 12;
   int64_t most = 0;
   for (int g = 0; g < 2; ++g)
     for (int i = 0; i < 3; ++i) {
-      // plane i: [res[y axis]][res[x axis]][C]; line i: [res[line axis]][C] (vm_plane_x / vm_plane_y / vm_line_ax of ego_device.h)
-      const int px = i == 2 ? 1 : 0, py = i == 0 ? 1 : 2, la = 2 - i;
-      EGO_REQUIRE(src->plane[g][i] && src->line[g][i] && dst->plane[g][i] && dst->line[g][i], "avgpool_field: null table");
+      // plane i: [res[y axis]][res[x axis]][C]; line i: [res[line axis]][C]
+      const int px = vm_plane_x(i), py = vm_plane_y(i), la = vm_line_ax(i);
       EGO_REQUIRE(dst->res[0] == src->res[0] / 2 && dst->res[1] == src->res[1] / 2 && dst->res[2] == src->res[2] / 2 && dst->res[0] >= 1 &&
                   dst->res[1] >= 1 && dst->res[2] >= 1, "avgpool_field: dst.res must be src.res / 2");
       const int a = g * 6 + i, b = g * 6 + 3 + i;

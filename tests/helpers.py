@@ -13,8 +13,20 @@ def make_coords(cfg, device):
 
 
 def make_model(cfg, weights, device="cuda"):
-    """egonerf_amd EgoNeRF with the reference's ctor kwargs (train.py:163-171 resolved values)."""
-    return synth.build_model(cfg, weights, device)
+    """egonerf_amd EgoNeRF with the reference's ctor kwargs (train.py:163-171 resolved values).  A `cfg.grid` other than the one the
+    voxel count resolves to (three unequal axis resolutions, an odd one: what tells an axis mix-up) is set on the coordinates first, as
+    train.py:376-377 does after an upsampling."""
+    if list(cfg.grid) == synth.n_to_reso(cfg.n_voxel):
+        return synth.build_model(cfg, weights, device)
+    from unittest import mock
+    build_coords = synth.build_coords
+
+    def coords_at_grid(c, dev):
+        coords = build_coords(c, dev)
+        coords.set_resolution(list(c.grid), r0=c.r0)
+        return coords
+    with mock.patch.object(synth, "build_coords", coords_at_grid):
+        return synth.build_model(cfg, weights, device)
 
 
 def make_oracle(cfg, weights, dtype=torch.float32):

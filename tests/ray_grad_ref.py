@@ -32,6 +32,10 @@ CASES = {
     "other_n_comp": (dict(n_voxel=20 ** 3, density_n_comp=(20,) * 3, app_n_comp=(36,) * 3, app_dim=23, view_pe=3, fea_pe=1), 1234, 7, 64,
                      dict(n_coarse=16, n_fine=16, resampling=True)),
     "fine_only": (dict(n_voxel=20 ** 3), 1234, 7, 64, dict(n_coarse=16, n_fine=32, resampling=True, use_coarse_sample=False)),
+    # three unequal axis resolutions, one odd (every grid above has N_r = N_theta or even axes only: an axis mix-up in the taps or in the
+    # derivative factors hides there); 4 / 20 components: idle lanes and a partial second pass of a row's 16 channels
+    "odd_grid": (dict(n_voxel=20 ** 3, grid=[6, 5, 8], density_n_comp=(4,) * 3, app_n_comp=(20,) * 3), 4321, 17, 130,
+                 dict(n_coarse=16, n_fine=16, resampling=True)),
 }
 WELL_CONDITIONED = ("tiny_other_seeds", "grid30", "grid24")   # nothing excused, 5 x inside the bound
 

@@ -81,8 +81,16 @@ def _slot_order(dfe27):
 
 
 def test_per_sample_gradient_on_hand_placed_points():
+    # the tiny scene, and one with three unequal axis resolutions, one of them odd: a mixed-up axis in the kernel's tap addresses or
+    # in the derivative's factor (n - 1) / 2 shows only there (the tiny scene has N_r = N_theta).  Its 4 density components leave 12 of
+    # a row's 16 lanes idle in plane_terms, its 20 appearance components need a second, partial pass of 16.
+    for cfg in (synth.SceneConfig(n_voxel=20 ** 3),
+                synth.SceneConfig(n_voxel=20 ** 3, grid=[6, 5, 8], density_n_comp=(4, 4, 4), app_n_comp=(20, 20, 20))):
+        _per_sample_gradient(cfg)
+
+
+def _per_sample_gradient(cfg):
     from egonerf_amd import _lib
-    cfg = synth.SceneConfig(n_voxel=20 ** 3)
     w = synth.make_weights(cfg, seed=1234)
     o64, o32 = make_oracle(cfg, w, dtype=torch.float64), make_oracle(cfg, w)
     xyz, yang = ref.hand_placed_points(o64)

@@ -91,23 +91,29 @@ def test_sorted_scatter_equals_the_atomic_one_and_itself(n_voxel, N, S, spread):
 
 
 def test_an_empty_batch_zero_fills_the_tables():
-    """the sorted scatters promise 'every texel is written' and train.py allocates the gradient tables with torch.empty."""
-    cfg = synth.SceneConfig(n_voxel=20 ** 3)
-    model = make_model(cfg, synth.make_weights(cfg, seed=21), DEV)
-    lib, st = _lib.load(), _lib.stream_handle()
-    sc = model.scene(training=True)
-    gd = [torch.full_like(p, float("nan")) for p in table_params(model, "density")]
-    ga = [torch.full_like(p, float("nan")) for p in table_params(model, "app")]
-    sd, sa = _grad_struct(gd), _grad_struct(ga)
-    nbytes = lib.ego_scatter_sorted_workspace_bytes(sc, 0, 8)
-    assert nbytes > 0
-    ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
-    _lib.check(lib.ego_scatter_sort(sc, None, 0, 8, ws.data_ptr(), nbytes, st), "scatter_sort")
-    _lib.check(lib.ego_scatter_density_sorted(sc, C.byref(sd), None, None, 0, 8, ws.data_ptr(), nbytes, st), "density_sorted")
-    _lib.check(lib.ego_scatter_app_sorted(sc, C.byref(sa), None, None, None, None, None, 0, 0, 8, ws.data_ptr(), nbytes, st), "app_sorted")
-    torch.cuda.synchronize()
-    for g in gd + ga:
-        assert float(g.abs().max()) == 0.0
+    """the sorted scatters promise 'every texel is written' and train.py allocates the gradient tables with torch.empty.
+    The tiny scene, and one with three unequal axis resolutions, one of them odd: there no two planes and no two lines of a field have
+    one size, so a table size taken from the wrong axes (vm_plane_elems / vm_line_elems, csrc/ego_device.h) leaves texels unwritten or
+    writes into the guard floats on either side of a table."""
+    for cfg in (synth.SceneConfig(n_voxel=20 ** 3), synth.SceneConfig(n_voxel=20 ** 3, grid=[6, 5, 8])):
+        model = make_model(cfg, synth.make_weights(cfg, seed=21), DEV)
+        lib, st = _lib.load(), _lib.stream_handle()
+        sc = model.scene(training=True)
+        GUARD = 64
+        bufs = {kind: [torch.full((p.numel() + 2 * GUARD,), float("nan"), device=DEV) for p in table_params(model, kind)] for kind in ("density", "app")}
+        gd, ga = ([b[GUARD:-GUARD] for b in bufs[kind]] for kind in ("density", "app"))
+        sd, sa = _grad_struct(gd), _grad_struct(ga)
+        nbytes = lib.ego_scatter_sorted_workspace_bytes(sc, 0, 8)
+        assert nbytes > 0
+        ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
+        _lib.check(lib.ego_scatter_sort(sc, None, 0, 8, ws.data_ptr(), nbytes, st), "scatter_sort")
+        _lib.check(lib.ego_scatter_density_sorted(sc, C.byref(sd), None, None, 0, 8, ws.data_ptr(), nbytes, st), "density_sorted")
+        _lib.check(lib.ego_scatter_app_sorted(sc, C.byref(sa), None, None, None, None, None, 0, 0, 8, ws.data_ptr(), nbytes, st), "app_sorted")
+        torch.cuda.synchronize()
+        for g in gd + ga:
+            assert float(g.abs().max()) == 0.0
+        for b in bufs["density"] + bufs["app"]:   # and not a float beyond a table
+            assert bool(torch.isnan(b[:GUARD]).all()) and bool(torch.isnan(b[-GUARD:]).all()), cfg.grid
 
 
 def _float64_grid_sample_gradients(cfg, weights, coords, dfeat, dv_ref, dtype=torch.float64):

@@ -274,20 +274,33 @@ def test_sparsity_term(tiny, scene):
 
 # ---- 6: another model shape and the MLP head -------------------------------------------------------------------------------------
 def test_other_shape_and_mlp_head():
-    cfg = synth.SceneConfig(n_voxel=20 ** 3, density_n_comp=(8, 8, 8), app_n_comp=(12, 12, 12), app_dim=16, featureC=64, view_pe=3, fea_pe=1,
-                            shadingMode="MLP")
+    # Three unequal axis resolutions, one of them odd: a mixed-up axis in a table size or a tap address (vm_plane_x / _y / vm_line_ax,
+    # vm_plane_elems / vm_line_elems of csrc/ego_device.h) shows here and nowhere on a grid with equal axes.  The pooled field is
+    # (3, 2, 4): floor-mode pooling drops the odd axis's last row.  4 density components leave 12 of a row's 16 lanes idle in
+    # k_scatter_generic, 20 appearance components need a second, partial pass; 3000 samples are no multiple of 64.
+    cfg = synth.SceneConfig(n_voxel=20 ** 3, grid=[6, 5, 8], density_n_comp=(4, 4, 4), app_n_comp=(20, 20, 20), app_dim=16, featureC=64,
+                            view_pe=3, fea_pe=1, shadingMode="MLP")
     w = synth.make_weights(cfg, seed=21)
     model = make_model(cfg, w, DEV)
+    assert model.gridSize.tolist() == [6, 5, 8] and tuple(model.coarse_sigma_plane_yin[0].shape[2:]) == (2, 3)
     rng = np.random.default_rng(12)
     c = rng.uniform(-1.1, 1.1, (3000, 7)).astype(np.float32)
     c[:, 6] = rng.integers(0, 2, 3000)
     gd, ga = rng.normal(size=3000).astype(np.float32), rng.normal(size=(3000, 16)).astype(np.float32)
-    zero_grads(model)
-    ((model.compute_densityfeature(T(c)) * T(gd)).sum() + (model.compute_appfeature(T(c)) * T(ga)).sum()).backward()
     keys = DENSITY + APP
-    ref = oracle_grads(cfg, w, keys, lambda o, dt: (o.density_feature(torch.from_numpy(c).to(dt)) * torch.from_numpy(gd).to(dt)).sum()
-                       + (o.app_feature(torch.from_numpy(c).to(dt)) * torch.from_numpy(ga).to(dt)).sum())
-    check(model, {}, ref, keys)
+
+    def oracle_loss(coarse):
+        def fn(o, dt):
+            if coarse:
+                o.update_coarse_sigma_grid()
+            return ((o.density_feature(torch.from_numpy(c).to(dt), coarse=coarse) * torch.from_numpy(gd).to(dt)).sum()
+                    + (o.app_feature(torch.from_numpy(c).to(dt)) * torch.from_numpy(ga).to(dt)).sum())
+        return fn
+    for coarse in (False, True):   # the full tables, then the pooled ones (the scatter at the pooled resolution + the pooling's backward)
+        zero_grads(model)
+        density = (model.compute_coarse_densityfeature if coarse else model.compute_densityfeature)(T(c))
+        ((density * T(gd)).sum() + (model.compute_appfeature(T(c)) * T(ga)).sum()).backward()
+        check(model, {}, oracle_grads(cfg, w, keys, oracle_loss(coarse)), keys)
     _mlp_case(model, cfg, w, 13)
 
 
