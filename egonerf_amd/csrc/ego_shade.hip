@@ -107,6 +107,14 @@ __device__ __forceinline__ void basis_mixed(const f32x4* __restrict__ BAS, int l
   basis_mfma(a, v, g != 0, fe);
 }
 
+// a layer's accumulators start from its bias: B = [4 m][2 h][16 r] as float4 quads (OFF_B1 / OFF_B2 of the LDS image), hw = the lane half.
+// A macro, used by k_shade and k_shade_h: as a function it hands the kernels another address form and seven of k_shade_h's instances change
+#define EGO_LOAD_BIAS(B, ACC)                                                                                      \
+  _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) _Pragma("unroll") for (int q = 0; q < 4; ++q) {                \
+    const f32x4 b = (B)[(mt * 2 + hw) * 4 + q];                                                                    \
+    ACC[mt][q * 4 + 0] = b.x; ACC[mt][q * 4 + 1] = b.y; ACC[mt][q * 4 + 2] = b.z; ACC[mt][q * 4 + 3] = b.w;        \
+  }
+
 template <int MODE, bool COMPACT = false>
 __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
   static_assert(!COMPACT || MODE == MODE_SHADE, "the live-sample list is an input of the shade only");
@@ -218,26 +226,12 @@ __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
 
     // ---- view-direction slots (3 raw + 12 encodings, 8 per lane half) -------------------------------
     float vw[8];
-    {
-      float sa0, ca0, sb0, cb0, sa1, ca1, sb1, cb1, sa2, ca2, sb2, cb2;
-      sincos_f32(vd0, sa0, ca0); sincos_f32(__fmul_rn(vd0, 2.f), sb0, cb0);
-      sincos_f32(vd1, sa1, ca1); sincos_f32(__fmul_rn(vd1, 2.f), sb1, cb1);
-      sincos_f32(vd2, sa2, ca2); sincos_f32(__fmul_rn(vd2, 2.f), sb2, cb2);
-      // half 0: d0 d1 d2 sin(d0) sin(2d0) sin(d1) sin(2d1) sin(d2) | half 1: sin(2d2) cos(d0) cos(2d0) ... cos(2d2) 0
-      vw[0] = h ? sb2 : vd0; vw[1] = h ? ca0 : vd1; vw[2] = h ? cb0 : vd2; vw[3] = h ? ca1 : sa0;
-      vw[4] = h ? cb1 : sb0; vw[5] = h ? ca2 : sa1; vw[6] = h ? cb2 : sb1; vw[7] = h ? 0.f : sa2;
-    }
+    view_slots<EncF32>(vd0, vd1, vd2, h, vw);
 
     // ---- layer 1: 150 -> 128.  K-outer: four accumulators (one per 32-unit M-tile) stay live, the
     // B operand of k-step kk is produced right before it is consumed -------------------------------
     f32x16 H[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 b = B1[(mt * 2 + hw) * 4 + q];
-        H[mt][q * 4 + 0] = b.x; H[mt][q * 4 + 1] = b.y; H[mt][q * 4 + 2] = b.z; H[mt][q * 4 + 3] = b.w;
-      }
+    EGO_LOAD_BIAS(B1, H)
     {
       f32x4 a[4];
       float s1 = 0.f, c1 = 0.f, s2 = 0.f, c2 = 0.f;
@@ -247,19 +241,7 @@ __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt) a[mt] = W1[((kk >> 2) * 4 + mt) * 64 + lw];
         }
-        float x;
-        if (kk < 5 * NSLOT) {
-          const int r = kk / 5, kind = kk % 5;
-          if (kind == 0) {
-            sincos_f32(fe[r], s1, c1);
-            sincos_f32(__fmul_rn(fe[r], 2.f), s2, c2);
-          }
-          x = kind == 0 ? fe[r] : (kind == 1 ? s1 : (kind == 2 ? s2 : (kind == 3 ? c1 : c2)));
-        } else if (kk < 5 * NSLOT + 8) {
-          x = vw[kk - 5 * NSLOT];
-        } else {
-          x = 0.f;
-        }
+        const float x = layer1_value<EncF32>(kk, fe, vw, s1, c1, s2, c2);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) H[mt] = MFMA(a[mt][kk & 3], x, H[mt]);
       }
@@ -271,13 +253,7 @@ __global__ __launch_bounds__(512) void k_shade(ShadeArgs A) {
 
     // ---- layer 2: 128 -> 128 (K-outer again), then layer 3: 128 -> 3 on the VALU -----------------------
     f32x16 G[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 b = B2[(mt * 2 + hw) * 4 + q];
-        G[mt][q * 4 + 0] = b.x; G[mt][q * 4 + 1] = b.y; G[mt][q * 4 + 2] = b.z; G[mt][q * 4 + 3] = b.w;
-      }
+    EGO_LOAD_BIAS(B2, G)
     {
       f32x4 a[4];
 #pragma unroll
@@ -430,18 +406,6 @@ __device__ __forceinline__ u32x6 cvt_2xpk16_fp6_f32(const f32x16& a, const f32x1
   return r;
 }
 
-// 8 fp32 values -> 8 halves, round to nearest: one k-step of an activation dump (ego_shade_dump's x / h1 / h2)
-__device__ __forceinline__ u32x4 pack8_rn(const float x[8]) {
-  u32x4 o;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    o[q] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2v{x[2 * q], x[2 * q + 1]}, h2v));
-  }
-  return o;
-}
-
 struct B6 {
   v8i x, r;   // fp6 operands of the two correction terms (dwords 6, 7 unused)
   int sb;     // B's block scale byte (biased exponent of the group's largest |x|)
@@ -531,6 +495,131 @@ __device__ __forceinline__ void group_mfma6(const float* lds, const F6Bases& fb,
   H[2] = MFMA6(a6_operand(hd[2], tl[2], 1), b.r, H[2], (int)sa.y, 2, b.sb);
   H[3] = MFMA6(a6_operand(hd[3], tl[3], 1), b.r, H[3], (int)sa.y, 3, b.sb);
 }
+
+// ---- one MLP layer of k_shade_h per arithmetic (K-outer: KH1 / KH2 steps of 8 values per lane half, the four accumulators ACC stay
+// live).  LAYER (1 or 2) picks the step count and the LDS region; SRC(step, xs) fills the step's eight values; `step` is a constant
+// after unrolling everywhere.  Macros, expanded in k_shade_h and speaking of its locals (lds, lw, lane, tile, valid, A, DUMP):
+// these kernels are tuned to the register, and as functions the bodies reach them in another instruction order (the layer-2
+// fragment loads of f16x3 came out reversed) and their code changes.
+// The two operand sources: the layer-1 generator (ego_tuned.h) over the kernel's fe / vw / s1 .. c2, and registers of layer 1's H
+#define EGO_X_LAYER1(step, xs)                                              \
+  _Pragma("unroll") for (int e = 0; e < 8; ++e) {                           \
+    const int kk = (step) * 8 + e;                                          \
+    if (layer1_slot_head(kk)) EncHw::enc(fe[kk / 5], s1, c1, s2, c2);       \
+    xs[e] = EGO_LAYER1_PICK(kk, fe[kk / 5], s1, c1, s2, c2, vw);            \
+  }
+#define EGO_X_LAYER2(step, xs) \
+  _Pragma("unroll") for (int e = 0; e < 8; ++e) xs[e] = H[((step) * 8 + e) >> 4][((step) * 8 + e) & 15];
+
+// f16x3: A fragments [step][m-tile][hi|lo][lane] of the current / next k-step (LDS reads issued one step ahead).  The x dump of the
+// training forward ([tile][k-step][lane][8 halves]) is optional (r05): ego_weight_grad_x re-derives x from the feature slots and
+// the view direction
+#define EGO_MLP_LAYER_F16X3(LAYER, W, ACC, SRC)                                                                                  \
+  {                                                                                                                              \
+    constexpr int KH = (LAYER) == 1 ? KH1 : KH2;                                                                                 \
+    h8 ah[4], al[4], nh[4], nl[4];                                                                                               \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                                                           \
+      nh[mt] = __builtin_bit_cast(h8, (W)[(mt * 2 + 0) * 64 + lw]);                                                              \
+      nl[mt] = __builtin_bit_cast(h8, (W)[(mt * 2 + 1) * 64 + lw]);                                                              \
+    }                                                                                                                            \
+    _Pragma("unroll") for (int step = 0; step < KH; ++step) {                                                                    \
+      float xs[8];                                                                                                               \
+      SRC(step, xs);                                                                                                             \
+      const HL b = split8(xs, true);                                                                                             \
+      if (DUMP && (LAYER) == 1 && valid && A.dump_x)                                                                             \
+        __builtin_nontemporal_store(pack8_rn(xs), &((u32x4*)A.dump_x)[(tile * KH1 + step) * 64 + lane]);                        \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) { ah[mt] = nh[mt]; al[mt] = nl[mt]; }                                      \
+      if (step + 1 < KH) {                                                                                                       \
+        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                                                       \
+          nh[mt] = __builtin_bit_cast(h8, (W)[(((step + 1) * 4 + mt) * 2 + 0) * 64 + lw]);                                       \
+          nl[mt] = __builtin_bit_cast(h8, (W)[(((step + 1) * 4 + mt) * 2 + 1) * 64 + lw]);                                       \
+        }                                                                                                                        \
+      }                                                                                                                          \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ACC[mt] = MFMAH(ah[mt], b.hi, ACC[mt]);                                    \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ACC[mt] = MFMAH(al[mt], b.hi, ACC[mt]);                                    \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ACC[mt] = MFMAH(ah[mt], b.lo, ACC[mt]);                                    \
+    }                                                                                                                            \
+  }
+
+// f16f8: W = the layer's region, hi fragments [step][m-tile][lane] first, the fp8 fragments [pair][m-tile][part][lane] behind them
+#define EGO_MLP_LAYER_F8(LAYER, W, ACC, SRC)                                                                                     \
+  {                                                                                                                              \
+    constexpr int KH = (LAYER) == 1 ? KH1 : KH2;                                                                                 \
+    const u32x4* WF = (W) + ((LAYER) == 1 ? F8_HI1 : F8_HI2) / 4;                                                                \
+    h8 ah[4], nh[4];                                                                                                             \
+    v8i a8[4], b8;                                                                                                               \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) nh[mt] = __builtin_bit_cast(h8, (W)[mt * 64 + lw]);                         \
+    _Pragma("unroll") for (int step = 0; step < KH; ++step) {                                                                    \
+      float xs[8];                                                                                                               \
+      SRC(step, xs);                                                                                                             \
+      const h8 bh = split8_f8(xs, b8, step & 1);                                                                                 \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ah[mt] = nh[mt];                                                          \
+      if (step + 1 < KH) {                                                                                                       \
+        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) nh[mt] = __builtin_bit_cast(h8, (W)[((step + 1) * 4 + mt) * 64 + lw]);  \
+      }                                                                                                                          \
+      if ((step & 1) == 0) { /* the pair's fp8 fragments: needed after the second step's main-term MFMAs */                      \
+        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) a8[mt] = load_a8(WF, step >> 1, mt, lw);                                \
+      }                                                                                                                          \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ACC[mt] = MFMAH(ah[mt], bh, ACC[mt]);                                      \
+      if (step & 1) {                                                                                                            \
+        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ACC[mt] = MFMA8(a8[mt], b8, ACC[mt]);                                    \
+      }                                                                                                                          \
+    }                                                                                                                            \
+  }
+
+// f16f6: groups of four steps; layer 1's last group holds only steps 8, 9 (xl = their 16 values).  The block maximum only has to
+// look at layer 1's unbounded values: every one of its groups holds cosines of magnitude ~1 and nothing else above 1, so its
+// running maximum starts at 1.  Step-outer / value-inner on purpose: a flat loop over the values exceeds the unroller's size limit
+// with the group code in its body, and a rolled loop indexes the register arrays through scratch.
+#define EGO_MLP_LAYER_F6(LAYER, ACC, SRC)                                                                                        \
+  {                                                                                                                              \
+    constexpr int KH = (LAYER) == 1 ? KH1 : KH2;                                                                                 \
+    constexpr bool L2 = (LAYER) == 2;                                                                                            \
+    constexpr float amax0 = L2 ? 0.f : 1.f;                                                                                      \
+    const F6Bases fb = f6_bases(lw);                                                                                             \
+    h8 ah[4], nh[4];                                                                                                             \
+    uint32_t hp[16];                                                                                                             \
+    float res[32], xl[16];                                                                                                       \
+    float amax = amax0;                                                                                                          \
+    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) nh[mt] = f6_hi(lds, fb, L2, 0, mt);                                         \
+    _Pragma("unroll") for (int step = 0; step < KH; ++step) {                                                                    \
+      float xs[8];                                                                                                               \
+      SRC(step, xs);                                                                                                             \
+      int mmask = L2 ? 0xff : 0;                                                                                                 \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                                            \
+        if (!L2 && step >= 8) xl[(step - 8) * 8 + e] = xs[e];                                                                    \
+        if (!L2 && layer1_unbounded(step * 8 + e)) mmask |= 1 << e;                                                              \
+      }                                                                                                                          \
+      const int sg = step & 3;                                                                                                   \
+      const h8 bh = split8_f6(xs, hp + 4 * sg, res + 8 * sg, amax, mmask);                                                       \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ah[mt] = nh[mt];                                                          \
+      if (step + 1 < KH) {                                                                                                       \
+        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) nh[mt] = f6_hi(lds, fb, L2, step + 1, mt);                              \
+      }                                                                                                                          \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) ACC[mt] = MFMAH(ah[mt], bh, ACC[mt]);                                      \
+      if (sg == 3) {                                                                                                             \
+        const B6 b6 = group6(hp, res, amax);                                                                                     \
+        group_mfma6(lds, fb, L2, step >> 2, b6, ACC);                                                                            \
+        amax = amax0;                                                                                                            \
+      } else if (!L2 && step == KH - 1) {                                                                                        \
+        const B6 b6 = group6_half(xl, res, amax);                                                                                \
+        group_mfma6(lds, fb, L2, G6_1 - 1, b6, ACC);                                                                             \
+      }                                                                                                                          \
+    }                                                                                                                            \
+  }
+
+// training forward: a layer's output (after the ReLU) as KH2 k-steps of the next layer, [tile][k-step][lane][8 halves], plus the
+// ReLU masks as bits: what the shade backward needs of h1 / h2 (it would otherwise re-read both dumps, 1 KB per sample).
+// Layer 1's accumulators arrive rectified, layer 2's do not.
+#define EGO_DUMP_HIDDEN(LAYER, ACC, DUMP_H)                                                                                      \
+  {                                                                                                                              \
+    _Pragma("unroll") for (int st = 0; st < KH2; ++st) { /* k-step st of the next layer = registers 8 (st & 1) .. + 7 of m-tile st >> 1 */ \
+      float v8[8];                                                                                                               \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) v8[e] = (LAYER) == 1 ? ACC[st >> 1][8 * (st & 1) + e] : relu_f(ACC[st >> 1][8 * (st & 1) + e]); \
+      __builtin_nontemporal_store(pack8_rn(v8), &((u32x4*)(DUMP_H))[(tile * KH2 + st) * 64 + lane]);                            \
+    }                                                                                                                            \
+    __builtin_nontemporal_store(relu_bits(ACC), &((u32x2*)A.dump_bits)[(tile * 2 + ((LAYER) - 1)) * 64 + lane]);                \
+  }
 
 struct BasisFrag {
 
@@ -1072,293 +1161,30 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
       for (int q = 0; q < 4; ++q) __builtin_nontemporal_store(f32x4{fe[4 * q], fe[4 * q + 1], fe[4 * q + 2], fe[4 * q + 3]}, &((f32x4*)A.dump_fe)[(tile * 4 + q) * 64 + lane]);
     }
     float vw[8];
-    {
-      float sa0, ca0, sb0, cb0, sa1, ca1, sb1, cb1, sa2, ca2, sb2, cb2;
-      sincos_x_2x_hw(vd0, sa0, ca0, sb0, cb0);
-      sincos_x_2x_hw(vd1, sa1, ca1, sb1, cb1);
-      sincos_x_2x_hw(vd2, sa2, ca2, sb2, cb2);
-      vw[0] = h ? sb2 : vd0; vw[1] = h ? ca0 : vd1; vw[2] = h ? cb0 : vd2; vw[3] = h ? ca1 : sa0;
-      vw[4] = h ? cb1 : sb0; vw[5] = h ? ca2 : sa1; vw[6] = h ? cb2 : sb1; vw[7] = h ? 0.f : sa2;
-    }
+    view_slots<EncHw>(vd0, vd1, vd2, h, vw);
 
-    // ---- layer 1 (K-outer, 10 steps of 8 values per lane half) ----------------------------------------------
+    // ---- layer 1 (10 steps of 8 values per lane half) ----------------------------------------------------------
     f32x16 H[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 b = B1[(mt * 2 + hw) * 4 + q];
-        H[mt][q * 4 + 0] = b.x; H[mt][q * 4 + 1] = b.y; H[mt][q * 4 + 2] = b.z; H[mt][q * 4 + 3] = b.w;
-      }
-    if (P8) {
-      float s1 = 0.f, c1 = 0.f, s2 = 0.f, c2 = 0.f;
-      float xs[8];
-      const u32x4* W1F = W1 + F8_HI1 / 4;   // fp8 fragments [pair][mt][part][lane]
-      h8 ah[4], nh[4];
-      v8i a8[4], b8;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) nh[mt] = __builtin_bit_cast(h8, W1[mt * 64 + lw]);
-#pragma unroll
-      for (int kk = 0; kk < KS1; ++kk) {
-        float x;
-        if (kk < 5 * NSLOT) {
-          const int r = kk / 5, kind = kk % 5;
-          if (kind == 0) sincos_x_2x_hw(fe[r], s1, c1, s2, c2);
-          x = kind == 0 ? fe[r] : (kind == 1 ? s1 : (kind == 2 ? s2 : (kind == 3 ? c1 : c2)));
-        } else if (kk < 5 * NSLOT + 8) {
-          x = vw[kk - 5 * NSLOT];
-        } else {
-          x = 0.f;
-        }
-        xs[kk & 7] = x;
-        if ((kk & 7) == 7) {
-          const int step = kk >> 3;
-          const h8 bh = split8_f8(xs, b8, step & 1);
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) ah[mt] = nh[mt];
-          if (step + 1 < KH1) {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) nh[mt] = __builtin_bit_cast(h8, W1[((step + 1) * 4 + mt) * 64 + lw]);
-          }
-          if ((step & 1) == 0) {  // the pair's fp8 fragments: needed after the second step's main-term MFMAs
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) a8[mt] = load_a8(W1F, step >> 1, mt, lw);
-          }
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) H[mt] = MFMAH(ah[mt], bh, H[mt]);
-          if (step & 1) {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) H[mt] = MFMA8(a8[mt], b8, H[mt]);
-          }
-        }
-      }
-    } else if (P6) {
-      float s1 = 0.f, c1 = 0.f, s2 = 0.f, c2 = 0.f;
-      const F6Bases fb = f6_bases(lw);
-      h8 ah[4], nh[4];
-      uint32_t hp[16];
-      float res[32], xl[16];
-      float amax = 1.f;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) nh[mt] = f6_hi(lds, fb, false, 0, mt);
-      // step-outer / value-inner: the flat 80-iteration form of the other arithmetics exceeds the unroller's size limit with the group
-      // code in its body, and a rolled loop indexes the register arrays through scratch
-#pragma unroll
-      for (int step = 0; step < KH1; ++step) {
-        float xs[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int kk = step * 8 + e;
-          float x;
-          if (kk < 5 * NSLOT) {
-            const int r = kk / 5, kind = kk % 5;
-            if (kind == 0) sincos_x_2x_hw(fe[r], s1, c1, s2, c2);
-            x = kind == 0 ? fe[r] : (kind == 1 ? s1 : (kind == 2 ? s2 : (kind == 3 ? c1 : c2)));
-          } else if (kk < 5 * NSLOT + 8) {
-            x = vw[kk - 5 * NSLOT];
-          } else {
-            x = 0.f;
-          }
-          xs[e] = x;
-          if (kk >= 64) xl[kk - 64] = x;
-        }
-        const int sg = step & 3;
-        // the block maximum only has to look at the unbounded values (features, raw view direction): every group holds cosines of
-        // magnitude ~1 and nothing else above 1, so the running maximum starts at 1
-        int mmask = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int kk = step * 8 + e;
-          if ((kk < 5 * NSLOT && kk % 5 == 0) || (kk >= 5 * NSLOT && kk < 5 * NSLOT + 3)) mmask |= 1 << e;
-        }
-        const h8 bh = split8_f6(xs, hp + 4 * sg, res + 8 * sg, amax, mmask);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) ah[mt] = nh[mt];
-        if (step + 1 < KH1) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) nh[mt] = f6_hi(lds, fb, false, step + 1, mt);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) H[mt] = MFMAH(ah[mt], bh, H[mt]);
-        if (sg == 3) {
-          const B6 b6 = group6(hp, res, amax);
-          group_mfma6(lds, fb, false, step >> 2, b6, H);
-          amax = 1.f;
-        } else if (step == KH1 - 1) {
-          const B6 b6 = group6_half(xl, res, amax);
-          group_mfma6(lds, fb, false, G6_1 - 1, b6, H);
-        }
-      }
-    } else
+    EGO_LOAD_BIAS(B1, H)
     {
-      float s1 = 0.f, c1 = 0.f, s2 = 0.f, c2 = 0.f;
-      float xs[8];
-      h8 ah[4], al[4], nh[4], nl[4];  // A fragments of the current / next k-step (LDS reads issued one step ahead)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        nh[mt] = __builtin_bit_cast(h8, W1[(mt * 2 + 0) * 64 + lw]);
-        nl[mt] = __builtin_bit_cast(h8, W1[(mt * 2 + 1) * 64 + lw]);
-      }
-#pragma unroll
-      for (int kk = 0; kk < KS1; ++kk) {
-        float x;
-        if (kk < 5 * NSLOT) {
-          const int r = kk / 5, kind = kk % 5;
-          if (kind == 0) sincos_x_2x_hw(fe[r], s1, c1, s2, c2);
-          x = kind == 0 ? fe[r] : (kind == 1 ? s1 : (kind == 2 ? s2 : (kind == 3 ? c1 : c2)));
-        } else if (kk < 5 * NSLOT + 8) {
-          x = vw[kk - 5 * NSLOT];
-        } else {
-          x = 0.f;
-        }
-        xs[kk & 7] = x;
-        if ((kk & 7) == 7) {
-          const int step = kk >> 3;
-          const HL b = split8(xs, true);
-          // [tile][k-step][lane][8 halves]; optional (r05): ego_weight_grad_x re-derives x from the feature slots and the view direction
-          if (DUMP && valid && A.dump_x) __builtin_nontemporal_store(pack8_rn(xs), &((u32x4*)A.dump_x)[(tile * KH1 + step) * 64 + lane]);
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) { ah[mt] = nh[mt]; al[mt] = nl[mt]; }
-          if (step + 1 < KH1) {
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-              nh[mt] = __builtin_bit_cast(h8, W1[(((step + 1) * 4 + mt) * 2 + 0) * 64 + lw]);
-              nl[mt] = __builtin_bit_cast(h8, W1[(((step + 1) * 4 + mt) * 2 + 1) * 64 + lw]);
-            }
-          }
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) H[mt] = MFMAH(ah[mt], b.hi, H[mt]);
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) H[mt] = MFMAH(al[mt], b.hi, H[mt]);
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) H[mt] = MFMAH(ah[mt], b.lo, H[mt]);
-        }
-      }
+      float s1 = 0.f, c1 = 0.f, s2 = 0.f, c2 = 0.f;   // the encodings of the feature slot the generator stands in
+      if (P8) EGO_MLP_LAYER_F8(1, W1, H, EGO_X_LAYER1)
+      else if (P6) EGO_MLP_LAYER_F6(1, H, EGO_X_LAYER1)
+      else EGO_MLP_LAYER_F16X3(1, W1, H, EGO_X_LAYER1)
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) H[mt][r] = relu_f(H[mt][r]);
-    if (DUMP && valid) {
-#pragma unroll
-      for (int st = 0; st < KH2; ++st) {   // k-step st of the next layer = registers 8 (st & 1) .. + 7 of m-tile st >> 1
-        float v8[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v8[e] = H[st >> 1][8 * (st & 1) + e];
-        __builtin_nontemporal_store(pack8_rn(v8), &((u32x4*)A.dump_h1)[(tile * KH2 + st) * 64 + lane]);
-      }
-      // the ReLU masks as bits: what the shade backward needs of h1 / h2 (it would otherwise re-read both dumps, 1 KB per sample)
-      __builtin_nontemporal_store(relu_bits(H), &((u32x2*)A.dump_bits)[(tile * 2 + 0) * 64 + lane]);
-    }
+    if (DUMP && valid) EGO_DUMP_HIDDEN(1, H, A.dump_h1)
 
-    // ---- layer 2 (8 steps), layer 3 on the VALU ----------------------------------------------------------------
+    // ---- layer 2 (8 steps: registers of H), layer 3 on the VALU ------------------------------------------------
     f32x16 G[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 b = B2[(mt * 2 + hw) * 4 + q];
-        G[mt][q * 4 + 0] = b.x; G[mt][q * 4 + 1] = b.y; G[mt][q * 4 + 2] = b.z; G[mt][q * 4 + 3] = b.w;
-      }
-    if (P8) {
-      const u32x4* W2F = W2 + F8_HI2 / 4;
-      h8 ah[4], nh[4];
-      v8i a8[4], b8;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) nh[mt] = __builtin_bit_cast(h8, W2[mt * 64 + lw]);
-#pragma unroll
-      for (int step = 0; step < KH2; ++step) {
-        float xs[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) xs[e] = H[(step * 8 + e) >> 4][(step * 8 + e) & 15];
-        const h8 bh = split8_f8(xs, b8, step & 1);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) ah[mt] = nh[mt];
-        if (step + 1 < KH2) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) nh[mt] = __builtin_bit_cast(h8, W2[((step + 1) * 4 + mt) * 64 + lw]);
-        }
-        if ((step & 1) == 0) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) a8[mt] = load_a8(W2F, step >> 1, mt, lw);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) G[mt] = MFMAH(ah[mt], bh, G[mt]);
-        if (step & 1) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) G[mt] = MFMA8(a8[mt], b8, G[mt]);
-        }
-      }
-    } else if (P6) {
-      const F6Bases fb = f6_bases(lw);
-      h8 ah[4], nh[4];
-      uint32_t hp[16];
-      float res[32];
-      float amax = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) nh[mt] = f6_hi(lds, fb, true, 0, mt);
-#pragma unroll
-      for (int step = 0; step < KH2; ++step) {
-        float xs[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) xs[e] = H[(step * 8 + e) >> 4][(step * 8 + e) & 15];
-        const int sg = step & 3;
-        const h8 bh = split8_f6(xs, hp + 4 * sg, res + 8 * sg, amax);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) ah[mt] = nh[mt];
-        if (step + 1 < KH2) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) nh[mt] = f6_hi(lds, fb, true, step + 1, mt);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) G[mt] = MFMAH(ah[mt], bh, G[mt]);
-        if (sg == 3) {
-          const B6 b6 = group6(hp, res, amax);
-          group_mfma6(lds, fb, true, step >> 2, b6, G);
-          amax = 0.f;
-        }
-      }
-    } else
-    {
-      h8 ah[4], al[4], nh[4], nl[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        nh[mt] = __builtin_bit_cast(h8, W2[(mt * 2 + 0) * 64 + lw]);
-        nl[mt] = __builtin_bit_cast(h8, W2[(mt * 2 + 1) * 64 + lw]);
-      }
-#pragma unroll
-      for (int step = 0; step < KH2; ++step) {
-        float xs[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) xs[e] = H[(step * 8 + e) >> 4][(step * 8 + e) & 15];
-        const HL b = split8(xs, true);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) { ah[mt] = nh[mt]; al[mt] = nl[mt]; }
-        if (step + 1 < KH2) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            nh[mt] = __builtin_bit_cast(h8, W2[(((step + 1) * 4 + mt) * 2 + 0) * 64 + lw]);
-            nl[mt] = __builtin_bit_cast(h8, W2[(((step + 1) * 4 + mt) * 2 + 1) * 64 + lw]);
-          }
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) G[mt] = MFMAH(ah[mt], b.hi, G[mt]);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) G[mt] = MFMAH(al[mt], b.hi, G[mt]);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) G[mt] = MFMAH(ah[mt], b.lo, G[mt]);
-      }
-    }
-    if (DUMP && valid) {
-#pragma unroll
-      for (int st = 0; st < KH2; ++st) {
-        float v8[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v8[e] = relu_f(G[st >> 1][8 * (st & 1) + e]);
-        __builtin_nontemporal_store(pack8_rn(v8), &((u32x4*)A.dump_h2)[(tile * KH2 + st) * 64 + lane]);
-      }
-      __builtin_nontemporal_store(relu_bits(G), &((u32x2*)A.dump_bits)[(tile * 2 + 1) * 64 + lane]);
-    }
+    EGO_LOAD_BIAS(B2, G)
+    if (P8) EGO_MLP_LAYER_F8(2, W2, G, EGO_X_LAYER2)
+    else if (P6) EGO_MLP_LAYER_F6(2, G, EGO_X_LAYER2)
+    else EGO_MLP_LAYER_F16X3(2, W2, G, EGO_X_LAYER2)
+    if (DUMP && valid) EGO_DUMP_HIDDEN(2, G, A.dump_h2)
     float o0 = 0.f, o1 = 0.f, o2 = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
@@ -1427,6 +1253,13 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
     __syncthreads();
   }
 }
+#undef EGO_X_LAYER1
+#undef EGO_X_LAYER2
+#undef EGO_MLP_LAYER_F16X3
+#undef EGO_MLP_LAYER_F8
+#undef EGO_MLP_LAYER_F6
+#undef EGO_DUMP_HIDDEN
+#undef EGO_LOAD_BIAS
 
 // ---- host side: one function fills the common launch arguments, one picks the kernel instance --------------------------------
 ShadeArgs shade_args(const ego_scene* sc, int64_t M, int32_t S) {   // (the tables go in with the instance: launch_shade)

@@ -607,17 +607,7 @@ int ego_train_layout(int32_t which, int32_t* out, int32_t n) {
   if (which == 0) {  // x dump column -> reference MLP input column (-1: padding)
     EGO_REQUIRE(n == 2 * KS1, "train_layout(0): n must be 160");
     for (int h = 0; h < 2; ++h)
-      for (int kk = 0; kk < KS1; ++kk) {
-        int ch = -1;
-        if (kk < 5 * NSLOT) {
-          const int kind = kk % 5, r = kk / 5, f = 2 * r + h;
-          if (f < APP_DIM) ch = kind == 0 ? f : (kind == 1 ? 30 + 2 * f : (kind == 2 ? 31 + 2 * f : (kind == 3 ? 84 + 2 * f : 85 + 2 * f)));
-        } else if (kk < 5 * NSLOT + 8) {
-          const int t = kk - 5 * NSLOT + 8 * h;
-          ch = t < 3 ? APP_DIM + t : (t < 15 ? 138 + (t - 3) : -1);
-        }
-        out[dump_col(kk, h)] = ch;
-      }
+      for (int kk = 0; kk < KS1; ++kk) out[dump_col(kk, h)] = x_channel(kk, h);
   } else if (which == 1) {  // h1 / h2 / dh1 / dh2 dump column -> hidden unit
     EGO_REQUIRE(n == HID, "train_layout(1): n must be 128");
     for (int h = 0; h < 2; ++h)

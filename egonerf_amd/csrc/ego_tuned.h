@@ -12,8 +12,7 @@
 // activations.  The price is a fixed K-order per lane half, which ego_pack_mlp bakes into the weights:
 //   * lane half h gathers appearance channels [24h, 24h+24) of each of the 3 planes  (72 k-steps)
 //   * basis rows are permuted so half h receives features f = 2r + h in register r   (14 slots)
-//   * layer-1 k-steps: 14 slots x (f, sin f, sin 2f, cos f, cos 2f) + 8 view slots + 2 zero pads = 80
-//     (slot-major, so each encoding is produced right before the MFMAs that consume it)
+//   * layer-1 k-steps: 80 per half, slot-major; the order is defined once, at x_channel() below
 //   * layer-2 k-step m*16 + r consumes hidden unit m*32 + (r&3) + 8*(r>>2) + 4h
 // Layer 3 (128 -> 3) runs on the VALU from the layer-2 accumulators + one xor-32 exchange.
 #pragma once
@@ -69,9 +68,14 @@ __host__ __device__ constexpr int app_channel(int kk, int h) {
   return (kk / APP_HALF) * APP_C + ((kk % APP_HALF) / 4) * 8 + 4 * h + (kk % 4);
 }
 
+// ---- the layer-1 operand order: THE definition; the weight packers, the shade kernels, the weight-gradient pass and
+// ego_train_layout(0) all take it from here.  X register kk of lane half h: 14 feature slots r (feature f = 2r + h) x
+// (f, sin f, sin 2f, cos f, cos 2f), then the half's eight view slots, then two zero pads.
+constexpr int KX_FEAT = 5 * NSLOT;   // first view slot
+
 // reference MLP input column held by X register kk of lane half h (-1: zero weight)
-__device__ inline int x_channel(int kk, int h) {
-  if (kk < 5 * NSLOT) {
+__host__ __device__ constexpr int x_channel(int kk, int h) {
+  if (kk < KX_FEAT) {
     const int kind = kk % 5, r = kk / 5, f = 2 * r + h;
     if (f >= APP_DIM) return -1;
     const int pe0 = APP_DIM + 3;               // 30: sin block of the feature PE
@@ -84,12 +88,59 @@ __device__ inline int x_channel(int kk, int h) {
       default: return pe1 + 2 * f + 1;
     }
   }
-  if (kk < 5 * NSLOT + 8) {
-    const int t = (kk - 5 * NSLOT) + 8 * h;
+  if (kk < KX_FEAT + 8) {
+    const int t = (kk - KX_FEAT) + 8 * h;
     // d0 d1 d2 | sin d0, sin 2d0, sin d1, sin 2d1, sin d2, sin 2d2 | cos ... | pad
-    return t < 3 ? APP_DIM + t : (t < 15 ? 138 + (t - 3) : -1);
+    return t < 3 ? APP_DIM + t : (t < 15 ? APP_DIM + 3 + 4 * APP_DIM + (t - 3) : -1);
   }
   return -1;
+}
+
+// kk is the first value of a feature slot: the generator encodes the slot here
+__host__ __device__ constexpr bool layer1_slot_head(int kk) { return kk < KX_FEAT && kk % 5 == 0; }
+
+// values that are not bounded by 1 (features, raw view direction): all the f16f6 block maximum has to look at
+__host__ __device__ constexpr bool layer1_unbounded(int kk) {
+  return layer1_slot_head(kk) || (kk >= KX_FEAT && kk < KX_FEAT + 3);
+}
+
+// The two encoders of (sin x, cos x, sin 2x, cos 2x): hardware transcendentals (the f16 kernels and everything that re-derives
+// their operands) and the fp32 kernel's polynomial form
+struct EncHw {
+  static __device__ __forceinline__ void enc(float x, float& s1, float& c1, float& s2, float& c2) { sincos_x_2x_hw(x, s1, c1, s2, c2); }
+};
+struct EncF32 {
+  static __device__ __forceinline__ void enc(float x, float& s1, float& c1, float& s2, float& c2) {
+    sincos_f32(x, s1, c1);
+    sincos_f32(__fmul_rn(x, 2.f), s2, c2);
+  }
+};
+
+// the eight view slots of lane half h (3 raw + 12 encodings + 1 pad over the two halves)
+template <class ENC>
+__device__ __forceinline__ void view_slots(float d0, float d1, float d2, int h, float (&vw)[8]) {
+  float sa0, ca0, sb0, cb0, sa1, ca1, sb1, cb1, sa2, ca2, sb2, cb2;
+  ENC::enc(d0, sa0, ca0, sb0, cb0);
+  ENC::enc(d1, sa1, ca1, sb1, cb1);
+  ENC::enc(d2, sa2, ca2, sb2, cb2);
+  // half 0: d0 d1 d2 sin(d0) sin(2d0) sin(d1) sin(2d1) sin(d2) | half 1: sin(2d2) cos(d0) cos(2d0) ... cos(2d2) 0
+  vw[0] = h ? sb2 : d0; vw[1] = h ? ca0 : d1; vw[2] = h ? cb0 : d2; vw[3] = h ? ca1 : sa0;
+  vw[4] = h ? cb1 : sb0; vw[5] = h ? ca2 : sa1; vw[6] = h ? cb2 : sb1; vw[7] = h ? 0.f : sa2;
+}
+
+// X register kk (a constant after unrolling) of a lane half, picked from its slot's feature value f and encodings s1 .. c2, or from
+// the half's view slots vw.  An expression: ego_wgrad.hip's x_make encodes its slots ahead of the loads' arrival and picks from
+// arrays, and through a function its kernel's code changes.  The operands of the other branches are not evaluated.
+#define EGO_LAYER1_PICK(kk, f, s1, c1, s2, c2, vw)                                                                              \
+  ((kk) < KX_FEAT ? ((kk) % 5 == 0 ? (f) : ((kk) % 5 == 1 ? (s1) : ((kk) % 5 == 2 ? (s2) : ((kk) % 5 == 3 ? (c1) : (c2))))) \
+                  : ((kk) < KX_FEAT + 8 ? (vw)[(kk) - KX_FEAT] : 0.f))
+
+// The generator of the shade kernels: walk kk upwards; fe[r] = the half's feature slots.  Slot r is encoded into s1 .. c2 when its
+// first value is asked for, i.e. right before the MFMAs that consume it.
+template <class ENC, class FE>
+__device__ __forceinline__ float layer1_value(int kk, const FE& fe, const float (&vw)[8], float& s1, float& c1, float& s2, float& c2) {
+  if (layer1_slot_head(kk)) ENC::enc(fe[kk / 5], s1, c1, s2, c2);
+  return EGO_LAYER1_PICK(kk, fe[kk / 5], s1, c1, s2, c2, vw);
 }
 
 // ---- fp16-split ("f16x3") weight layout ------------------------------------------------------------------
@@ -191,6 +242,19 @@ __device__ __forceinline__ HL split8(const float x[8], bool keep) {
   HL o;
   o.hi = __builtin_bit_cast(h8, hi);
   o.lo = __builtin_bit_cast(h8, lo);
+  return o;
+}
+
+// 8 fp32 values -> 8 halves, round to nearest: one k-step of an activation dump (ego_shade_dump's x / h1 / h2), and of the x
+// that ego_weight_grad_x re-derives
+__device__ __forceinline__ u32x4 pack8_rn(const float x[8]) {
+  u32x4 o;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+    o[q] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2v{x[2 * q], x[2 * q + 1]}, h2v));
+  }
   return o;
 }
 

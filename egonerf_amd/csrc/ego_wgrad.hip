@@ -295,22 +295,10 @@ struct HTile {   // one operand's rows [row0, row0 + 32): up to two (k-step, lan
 
 // ---- B = the layer-1 input x, re-derived instead of read back (round 5) ----------------------------------------------------------------
 // x is a pure function of the 14 feature slots of a lane half and the ray's view direction (tensorBase.py:68-75: [features, viewdirs,
-// PE(features), PE(viewdirs)] in the shade kernels' K order: slot r -> columns 5 r .. 5 r + 4 = f, sin f, sin 2f, cos f, cos 2f; then the
-// eight view values of the half; then two zeros).  The training forward used to dump it as 160 halves per sample (0.67 GB written, 0.67 GB
+// PE(features), PE(viewdirs)] in the shade kernels' K order, which ego_tuned.h defines).  The training forward used to dump it as 160 halves per sample (0.67 GB written, 0.67 GB
 // read back per 8192 x 256 step) only for d(W1) = dh1^T x; the feature slots are dumped anyway (128 B per sample, the shade backward needs
-// them), so this fetch builds the same 8 halves per (k-step, lane half, sample) with the forward's own instructions (sincos_x_2x_hw,
-// round-to-nearest pack): bit-identical operands, 192 B per sample less to read and 320 B less to write.
-__device__ __forceinline__ u32x4 pack8_rn_w(const float x[8]) {
-  u32x4 o;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    o[q] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2v{x[2 * q], x[2 * q + 1]}, h2v));
-  }
-  return o;
-}
-
+// them), so this fetch builds the same 8 halves per (k-step, lane half, sample) with the forward's own code (view_slots, EGO_LAYER1_PICK,
+// pack8_rn of ego_tuned.h): bit-identical operands, 192 B per sample less to read and 320 B less to write.
 // One k-step (compile-time STEP) of a sample's lane half hw, in two parts so that the loads travel while the previous step multiplies:
 // x_load = the (at most three) feature slots the step's eight values come from (fe_lane = the half's slot dump, &fe[(tile * 4) * 64 + lane]
 // as floats, quad q 256 floats further on); x_make = the eight values from them and the ray's direction, packed as the forward packs them.
@@ -331,29 +319,13 @@ __device__ __forceinline__ u32x4 x_make(const float f[3], const float dir[3], in
 #pragma unroll
   for (int k = 0; k < 3; ++k)
     if (r_first + k < NSLOT && (r_first + k) * 5 <= STEP * 8 + 7) sincos_x_2x_hw(f[k], s1[k], c1[k], s2[k], c2[k]);
-  if (STEP >= 8) {   // the view values live in the last two steps
-    float sa0, ca0, sb0, cb0, sa1, ca1, sb1, cb1, sa2, ca2, sb2, cb2;
-    sincos_x_2x_hw(dir[0], sa0, ca0, sb0, cb0);
-    sincos_x_2x_hw(dir[1], sa1, ca1, sb1, cb1);
-    sincos_x_2x_hw(dir[2], sa2, ca2, sb2, cb2);
-    vw[0] = hw ? sb2 : dir[0]; vw[1] = hw ? ca0 : dir[1]; vw[2] = hw ? cb0 : dir[2]; vw[3] = hw ? ca1 : sa0;
-    vw[4] = hw ? cb1 : sb0; vw[5] = hw ? ca2 : sa1; vw[6] = hw ? cb2 : sb1; vw[7] = hw ? 0.f : sa2;
-  }
+  if (STEP >= 8) view_slots<EncHw>(dir[0], dir[1], dir[2], hw, vw);   // the view values live in the last two steps
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const int kk = STEP * 8 + e;
-    float x;
-    if (kk < 5 * NSLOT) {
-      const int k = kk / 5 - r_first, kind = kk % 5;
-      x = kind == 0 ? f[k] : (kind == 1 ? s1[k] : (kind == 2 ? s2[k] : (kind == 3 ? c1[k] : c2[k])));
-    } else if (kk < 5 * NSLOT + 8) {
-      x = vw[kk - 5 * NSLOT];
-    } else {
-      x = 0.f;
-    }
-    xs[e] = x;
+    const int kk = STEP * 8 + e, k = kk / 5 - r_first;
+    xs[e] = EGO_LAYER1_PICK(kk, f[k], s1[k], c1[k], s2[k], c2[k], vw);
   }
-  return pack8_rn_w(xs);
+  return pack8_rn(xs);
 }
 #define EGO_X_CASES(CALL)                                                                                                        \
   switch (s) {                                                                                                                  \

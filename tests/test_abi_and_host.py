@@ -43,6 +43,50 @@ def test_argument_validation_needs_no_gpu():
     assert need >= 4 * 4096 * (128 * 2 + 256 * 2 + 1 + 256 * 3)
 
 
+def test_train_layout_is_the_reference_input_order():
+    """ego_train_layout(0) against a restatement of MLPRender_Fea's input (tensorBase.py:68-75, positional_encoding: feature-major
+    over the frequencies, sines before cosines) mapped through the kernels' per-half slot rule; layouts 1-3 against the values
+    recorded from the build before the layer-1 operand order got its single definition in ego_tuned.h."""
+    lib = _lib.load()
+
+    def layout(which, n):
+        buf = (ctypes.c_int32 * n)()
+        assert lib.ego_train_layout(which, buf, n) == 0
+        return list(buf)
+
+    D, PE = 27, 2  # app_dim, view_pe = fea_pe
+    names = [("fea", f) for f in range(D)] + [("dir", d) for d in range(3)]
+    names += [(fn, "fea", f, 2 ** j) for fn in ("sin", "cos") for f in range(D) for j in range(PE)]
+    names += [(fn, "dir", d, 2 ** j) for fn in ("sin", "cos") for d in range(3) for j in range(PE)]
+    assert len(names) == 150
+    col = {nm: i for i, nm in enumerate(names)}
+    # the 16 view slots over the two lane halves: the raw direction, then sin PE, then cos PE, then a pad
+    view = [("dir", d) for d in range(3)] + [(fn, "dir", d, m) for fn in ("sin", "cos") for d in range(3) for m in (1, 2)] + [None]
+    want = [None] * 160
+    for h in range(2):
+        for kk in range(80):
+            if kk < 70:  # 14 feature slots x (f, sin f, sin 2f, cos f, cos 2f); register r of half h holds feature 2r + h
+                f, kind = 2 * (kk // 5) + h, kk % 5
+                nm = [("fea", f), ("sin", "fea", f, 1), ("sin", "fea", f, 2), ("cos", "fea", f, 1), ("cos", "fea", f, 2)][kind] if f < D else None
+            else:
+                nm = view[8 * h + kk - 70] if kk < 78 else None
+            want[(kk >> 2) * 8 + h * 4 + (kk & 3)] = col[nm] if nm is not None else -1  # dump_col(kk, h)
+    got = layout(0, 160)
+    assert sorted(got) == [-1] * 10 + list(range(150))
+    assert got == want
+
+    assert layout(1, 128) == list(range(128))  # recorded: hidden unit = dump column
+    assert layout(2, 32) == [0, 2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, -1, -1,
+                             1, 3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23, 25, -1, -1, -1]
+    assert layout(3, 144) == [
+        0, 1, 2, 3, 4, 5, 6, 7, 16, 17, 18, 19, 20, 21, 22, 23, 32, 33, 34, 35, 36, 37, 38, 39,
+        8, 9, 10, 11, 12, 13, 14, 15, 24, 25, 26, 27, 28, 29, 30, 31, 40, 41, 42, 43, 44, 45, 46, 47,
+        48, 49, 50, 51, 52, 53, 54, 55, 64, 65, 66, 67, 68, 69, 70, 71, 80, 81, 82, 83, 84, 85, 86, 87,
+        56, 57, 58, 59, 60, 61, 62, 63, 72, 73, 74, 75, 76, 77, 78, 79, 88, 89, 90, 91, 92, 93, 94, 95,
+        96, 97, 98, 99, 100, 101, 102, 103, 112, 113, 114, 115, 116, 117, 118, 119, 128, 129, 130, 131, 132, 133, 134, 135,
+        104, 105, 106, 107, 108, 109, 110, 111, 120, 121, 122, 123, 124, 125, 126, 127, 136, 137, 138, 139, 140, 141, 142, 143]
+
+
 def test_resolution_rule_and_constants(golden):
     fx = golden("stages")
     cfg = synth.SceneConfig()
