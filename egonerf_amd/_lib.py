@@ -38,6 +38,7 @@ class Scene(C.Structure):
         ("occ", C.c_void_p), ("occ_res", C.c_int32 * 3), ("term_eps", C.c_float),
         ("app16", VmField), ("app_f16", C.c_int32), ("n_r_lut_fine", C.c_int32), ("r_lut_fine", C.c_void_p), ("n_r_fine", C.c_int32),
         ("weight_thres", C.c_float), ("occ_cell", C.c_void_p), ("head", C.c_int32),
+        ("density_dense", C.c_void_p), ("density_coarse_dense", C.c_void_p),
     ]
 
 
@@ -151,6 +152,7 @@ PROTOTYPES = {
     "ego_pack_mlp_for": (C.c_int, [SP, P, C.c_int32, P]),
     "ego_packed_floats_compat": (C.c_int64, [SP]),
     "ego_pack_mlp_compat": (C.c_int, [SP, P, P]),
+    "ego_bake_density_dense": (C.c_int, [C.POINTER(VmField), P, P]),
     "ego_march_density": (C.c_int, [SP, P, I64, I32, P, P, P, F32, I32, P, P, I32, P, P, P, P, P, P]),
     "ego_shade_kernel_info": (C.c_int, [I32, C.POINTER(C.c_int32), I32]),
     "ego_shade": (C.c_int, [SP, P, P, P, I64, I32, P, P, P, P]),

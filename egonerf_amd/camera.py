@@ -238,7 +238,10 @@ class FrameRenderer:
     graph=True captures the whole frame once (torch.cuda.graph, on a single stream: no side stream, no parallel branches) and replays
     it per pose; it needs exp_sampling=True (the other schedule inspects device values on the host).  The capture fixes shapes and the
     scene's tables: re-create the object after `upsample_volume_grid` or a change of the alpha mask (`updateAlphaMask`,
-    `use_alpha_mask`), the rule GraphedTrainStep documents for shapes.
+    `use_alpha_mask`), the rule GraphedTrainStep documents for shapes.  With the dense density route (`EgoNeRF.dense_density`) the capture
+    embeds the baked node grids, which are snapshots: after the density tables changed, call `model.scene()` before the next replay - it
+    bakes into the same buffers, which stay allocated while the model keeps its device and grid size - and re-create the object after
+    switching the route on or off.
 
     stereo="top_bottom" (camera="erp", ipd > 0 in scene units): an omnidirectional-stereo panorama for a headset player - the left
     eye's image on top of the right eye's in ONE image, so every product doubles in height ([2 H, W, 3], [2 H, W], `rgbd` [2 H, 2 W, 3]).

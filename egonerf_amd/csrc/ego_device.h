@@ -231,6 +231,8 @@ struct DevOcc {
   const uint8_t* cell; // optional [2][res2-1][res1-1][res0-1]: OR of the 8 corner voxels of every cell (ego_scene.occ_cell)
 };
 
+// (occ_occupied_taps below restates this evaluation and occ_occupied's decision for a caller that already holds the taps: a change here
+// is a change there; tests/test_hip_dense_density.py holds the two against each other on masked scenes)
 __device__ __forceinline__ float occ_sample(const DevOcc& O, int g, float a_r, float a_th, float a_ph) {
   const Lin1 X = lin_setup(a_r, O.res[0]), Y = lin_setup(a_th, O.res[1]), Z = lin_setup(a_ph, O.res[2]);
   const uint8_t* V = O.vol + (int64_t)g * O.res[0] * O.res[1] * O.res[2];
@@ -247,6 +249,7 @@ __device__ __forceinline__ float occ_sample(const DevOcc& O, int g, float a_r, f
 // "mask value > 0" (tensorBase.py:464-478) for the march: a sample strictly inside a cell (all six axis weights > 0, all taps in
 // range) has a positive trilinear value iff any of the cell's eight corner voxels is set - one byte of the per-cell OR volume instead
 // of eight dependent byte loads and the interpolation; samples on a lattice plane / outside the volume take the exact evaluation
+// (restated in occ_occupied_taps below: keep the two alike)
 __device__ __forceinline__ bool occ_occupied(const DevOcc& O, int g, float a_r, float a_th, float a_ph) {
   if (O.cell) {
     const Lin1 X = lin_setup(a_r, O.res[0]), Y = lin_setup(a_th, O.res[1]), Z = lin_setup(a_ph, O.res[2]);
@@ -257,6 +260,29 @@ __device__ __forceinline__ bool occ_occupied(const DevOcc& O, int g, float a_r, 
     }
   }
   return occ_sample(O, g, a_r, a_th, a_ph) > 0.f;
+}
+
+// occ_occupied from the three axes' taps at O.res, for a caller that has them already: the dense march needs the field's own taps in
+// its phase B, and a mask of the field's resolution (the usual one) then costs no second set-up.  Same decisions, same evaluation
+// order as occ_occupied / occ_sample above, which keep their own text: routed through here, the kernels built on them come out with
+// different code.
+__device__ __forceinline__ bool occ_occupied_taps(const DevOcc& O, int g, const Lin1 X, const Lin1 Y, const Lin1 Z) {
+  if (O.cell) {
+    const bool interior = fminf(fminf(fminf(X.w0, X.w1), fminf(Y.w0, Y.w1)), fminf(Z.w0, Z.w1)) > 0.f;
+    if (interior) {
+      const int64_t c0 = O.res[0] - 1, c1 = O.res[1] - 1, c2 = O.res[2] - 1;
+      return O.cell[(((int64_t)g * c2 + Z.i0) * c1 + Y.i0) * c0 + X.i0] != 0;
+    }
+  }
+  const uint8_t* V = O.vol + (int64_t)g * O.res[0] * O.res[1] * O.res[2];
+  float v = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int ix = (k & 1) ? X.i1 : X.i0, iy = (k & 2) ? Y.i1 : Y.i0, iz = (k & 4) ? Z.i1 : Z.i0;
+    const float w = ((k & 1) ? X.w1 : X.w0) * ((k & 2) ? Y.w1 : Y.w0) * ((k & 4) ? Z.w1 : Z.w0);
+    v += w * (float)V[((int64_t)iz * O.res[1] + iy) * O.res[0] + ix];
+  }
+  return v > 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------

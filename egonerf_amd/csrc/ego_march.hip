@@ -1,5 +1,6 @@
 // libegonerf_hip.so: the fused density march of the tuned shape (16 density components): rows A+B+C+D+E of SURVEY 8a for one ray
-// per wave (or two waves), and its entry point ego_march_density.  gfx950 only.
+// per wave (or two waves), in its factored form (18 table taps per sample) and its dense form (8 taps of a baked node grid,
+// csrc/ego_dense.hip), and its entry point ego_march_density.  gfx950 only.
 #include <atomic>
 #include <stdlib.h>
 #include "ego_device.h"
@@ -85,8 +86,20 @@ __device__ __forceinline__ float normalize_r_fast(float r, const float* lut, int
 // for) holds zeros there and the real coordinates in a deferred segment, which cannot know yet; those samples have weight 0, their
 // tiles are never shaded, and tests/test_hip_march_split.py compares coordinates where a colour is read.
 constexpr int MARCH_MAXP = 4;   // passes per deferred segment (LDS parking space)
-template <int C, bool OCC, int NSPLIT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_march_density(DevCoords c, DevField F, const float* __restrict__ rays,
+constexpr int MARCH_WAVES = 3;        // waves per SIMD of the factored form (167 VGPRs, see above)
+// ... and of the dense form (78-93 VGPRs, 4-12 KB of LDS per workgroup); march_nsplit counts the wave slots of the form it launches.
+// Measured, 4096 x 512 step in ms, two runs each: 3 waves 0.4977 / 0.4971, 4: 0.4895 / 0.4888, 5: 0.4878 / 0.4868, 6: 0.4865 / 0.4863
+// (factored form: 0.5313 / 0.5304); at 6 the masked one-wave instance spills 20 B per lane, so 5 (NOTEBOOK 12.1).
+constexpr int MARCH_DENSE_WAVES = 5;
+// DENSE (inference scenes that carry ego_scene.density_dense, csrc/ego_dense.hip): phase B reads the baked node grid instead of the
+// 18 table taps.  Per plane i the factored feature dot_i = sum_c bilerp(plane_i,c) * lerp(line_i,c) is the trilinear interpolation of
+// G_i[phi][theta][r] = sum_c plane_i,c[node] * line_i,c[node] - plane and line interpolate on one lattice along independent axes, and an
+// out-of-range tap has weight 0 in either form - so with lane = sample a pass needs 8 loads of 16 B per lane, one per cell corner
+// carrying (G_0, G_1, G_2, 0), and no LDS hand-over: no stage / fres slabs, no wave barriers, far fewer registers (WPE waves per SIMD
+// instead of 3).  Phases A and C, emit, the hand-over between segments and the early stop are the same text for both forms.
+template <int C, bool OCC, int NSPLIT, bool DENSE, int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_march_density(DevCoords c, DevField F, const char* __restrict__ dense,
+                                                       uint32_t dense_grid_bytes, const float* __restrict__ rays,
                                                        int64_t N, int S, const float* __restrict__ z_in,
                                                        const float* __restrict__ r_sched,
                                                        const float* __restrict__ jitter, float near_,
@@ -98,8 +111,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                        float shade_above, uint8_t* __restrict__ tile_active) {
   static_assert(C == 16, "one texel = one 64-byte line = the team's four float4 parts");
   __shared__ float lut[1024];
-  __shared__ __attribute__((aligned(16))) f32x4 stage[4][6][64];   // per wave: the pass's tap set-ups
-  __shared__ float fres[4][64];                                      // per wave: the pass's density features
+  __shared__ __attribute__((aligned(16))) f32x4 stage[DENSE ? 1 : 4][6][DENSE ? 1 : 64];   // per wave: the pass's tap set-ups
+  __shared__ float fres[DENSE ? 1 : 4][DENSE ? 1 : 64];              // per wave: the pass's density features (neither in the dense form)
   __shared__ float park[NSPLIT > 1 ? 4 : 1][NSPLIT > 1 ? MARCH_MAXP : 1][2][64];   // deferred segments: alpha, exclusive product
   __shared__ float park_tot[4][MARCH_MAXP];
   __shared__ float carry_slot[4];
@@ -219,11 +232,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const float a_th = normalize_ang(y.th, c.th_near, c.th_inv);
     const float a_ph = normalize_ang(y.ph, c.ph_near, c.ph_inv);
     // occupancy mask (opt-in): unoccupied samples keep sigma = 0
-    const bool occupied = !OCC || !occ.vol || occ_occupied(occ, y.yang, a_r, a_th, a_ph);
+    // (dense form: the field's own taps, which phase B needs anyway, serve the mask too where it has the field's resolution)
+    Lin1 Rr, Tt, Pp;
+    bool occupied;
+    if constexpr (DENSE) {
+      Rr = lin_setup(a_r, F.res[0]); Tt = lin_setup(a_th, F.res[1]); Pp = lin_setup(a_ph, F.res[2]);
+      const bool same_res = occ.res[0] == F.res[0] && occ.res[1] == F.res[1] && occ.res[2] == F.res[2];   // wave-uniform
+      occupied = !OCC || !occ.vol || (same_res ? occ_occupied_taps(occ, y.yang, Rr, Tt, Pp) : occ_occupied(occ, y.yang, a_r, a_th, a_ph));
+    } else {
+      occupied = !OCC || !occ.vol || occ_occupied(occ, y.yang, a_r, a_th, a_ph);
+    }
     // a pass whose 64 samples are ALL masked out skips the set-up hand-over and the whole gather (wave-uniform: the software
     // pipeline of phase B is either run completely or not at all, so its wait counts stay exact); sigma is 0 for every lane then
     const bool pass_occupied = !OCC || __ballot(occupied) != 0ull;
+    float fdense = 0.f;
     if (pass_occupied) {
+    if constexpr (DENSE) {
+      // ---- phase B, dense form: lane = sample.  The eight corners of the sample's cell as base + 32-bit byte offset, all eight loads
+      // issued before the first use; interpolation along r, then theta, then phi, with lin_setup's weights (out-of-range taps: clamped
+      // index, weight 0); relu per plane, planes summed in order.
+#pragma clang fp contract(fast)
+      const uint32_t nr16 = (uint32_t)F.res[0] * 16u, gb = y.yang != 0 ? dense_grid_bytes : 0u;
+      const uint32_t row00 = gb + ((uint32_t)Pp.i0 * (uint32_t)F.res[1] + (uint32_t)Tt.i0) * nr16;
+      const uint32_t row01 = gb + ((uint32_t)Pp.i0 * (uint32_t)F.res[1] + (uint32_t)Tt.i1) * nr16;
+      const uint32_t row10 = gb + ((uint32_t)Pp.i1 * (uint32_t)F.res[1] + (uint32_t)Tt.i0) * nr16;
+      const uint32_t row11 = gb + ((uint32_t)Pp.i1 * (uint32_t)F.res[1] + (uint32_t)Tt.i1) * nr16;
+      const uint32_t c0 = (uint32_t)Rr.i0 * 16u, c1 = (uint32_t)Rr.i1 * 16u;
+      const f32x4 g000 = *(const f32x4*)(dense + (row00 + c0)), g001 = *(const f32x4*)(dense + (row00 + c1));
+      const f32x4 g010 = *(const f32x4*)(dense + (row01 + c0)), g011 = *(const f32x4*)(dense + (row01 + c1));
+      const f32x4 g100 = *(const f32x4*)(dense + (row10 + c0)), g101 = *(const f32x4*)(dense + (row10 + c1));
+      const f32x4 g110 = *(const f32x4*)(dense + (row11 + c0)), g111 = *(const f32x4*)(dense + (row11 + c1));
+      // every weight in a register of its own (see `issue` below: a packed multiply must broadcast the LOW half of its operand pair)
+      float w6[6] = {Rr.w0, Rr.w1, Tt.w0, Tt.w1, Pp.w0, Pp.w1};
+#pragma unroll
+      for (int k = 0; k < 6; ++k) asm volatile("" : "+v"(w6[k]));
+      const f32x4 v00 = g000 * w6[0] + g001 * w6[1], v01 = g010 * w6[0] + g011 * w6[1];
+      const f32x4 v10 = g100 * w6[0] + g101 * w6[1], v11 = g110 * w6[0] + g111 * w6[1];
+      const f32x4 u0 = v00 * w6[2] + v01 * w6[3], u1 = v10 * w6[2] + v11 * w6[3];
+      const f32x4 d = u0 * w6[4] + u1 * w6[5];
+      fdense = (fmaxf(d.x, 0.f) + fmaxf(d.y, 0.f)) + fmaxf(d.z, 0.f);   // relu per plane (EgoNeRF.py:340,346)
+      if (OCC && !occupied) fdense = 0.f;                               // sample masked out: sigma stays 0 (feature unused)
+    } else {
     {
       // byte offsets of every tap row / line of the sample's grid (the grid's table offsets folded in here, once per sample, so
       // that phase B needs no per-lane table select) + column offsets + the six axis weights
@@ -313,9 +362,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }  // factored form
     }  // pass_occupied
     // ---- phase C: lane = sample ------------------------------------------------------------------------------------------
-    const float f = pass_occupied ? fres[wv][lane] : 0.f;
+    float f;
+    if constexpr (DENSE) f = fdense; else f = pass_occupied ? fres[wv][lane] : 0.f;
     float sg = 0.f;
     if (occupied) sg = softplus ? softplus_shift(f, shift) : fmaxf(f, 0.f);
     const float a = ok ? alpha_from(sg * __fmul_rn(dist, dscale)) : 0.f;
@@ -367,17 +418,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 // Rays split over two waves when one wave per ray would leave the launch quantised by wave slots (see k_march_density): fewer than
 // two rounds of slots and at least two passes per half (at most MARCH_MAXP in the deferred half).
-static int march_nsplit(int64_t N, int n_pass) {
-  // wave slots (3 per SIMD) of the CURRENT device, queried once per device; racing first calls store the same value
-  static std::atomic<int> slots_of[16];
+static int march_nsplit(int64_t N, int n_pass, int waves_per_simd) {
+  // wave slots (waves_per_simd of the variant that is launched, on 4 SIMDs per CU) of the CURRENT device; the CU count is queried once
+  // per device; racing first calls store the same value
+  static std::atomic<int> cus_of[16];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  int slots = slots_of[dev].load(std::memory_order_relaxed);
-  if (!slots) {
-    int cus = 0;
-    slots = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? cus * 12 : 3072;
-    slots_of[dev].store(slots, std::memory_order_relaxed);
+  int cus = cus_of[dev].load(std::memory_order_relaxed);
+  if (!cus) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    cus_of[dev].store(cus, std::memory_order_relaxed);
   }
+  const int slots = cus * 4 * waves_per_simd;
   int nsplit = ((double)N / slots < 2.0 && n_pass >= 4 && (n_pass + 1) / 2 <= MARCH_MAXP) ? 2 : 1;
   // experiments and tests/test_hip_march_split.py (which flips it between calls of one process, hence read per launch: a getenv is
   // ~50 ns against a 5 us launch): EGO_MARCH_SPLIT forces 1 or 2 where the shape allows it
@@ -407,17 +459,27 @@ int ego_march_density(const ego_scene* sc, const float* rays, int64_t N, int32_t
   if (f.n_comp != 16)   // any other component count: the compatibility kernel (csrc/ego_generic.hip)
     return ego_generic_march(sc, f, (coarse & 2) != 0, rays, N, S, z_in, r_sched, jitter, near_, o.vol, z_out, alpha, alpha_stride, weight, bg_weight,
                              coords_out, sigma_out, tile_active, stream);
-  const int nsplit = march_nsplit(N, (S + 63) / 64);
-#define EGO_LAUNCH_MARCH(OCC, NS)                                                                                                       \
-  k_march_density<16, OCC, NS><<<nblk(N, 4 / NS), 256, 0, (hipStream_t)stream>>>(                                                      \
-      make_coords(*sc, (coarse & 2) != 0), make_field(f), rays, N, S, z_in, r_sched, jitter, near_, sc->act_softplus, sc->density_shift, \
-      sc->distance_scale, z_out, alpha, alpha_stride, weight, bg_weight, coords_out, sigma_out, o, sc->term_eps,                          \
-      fmaxf(sc->weight_thres, 0.f), tile_active)
-  if (o.vol) {
-    if (nsplit == 2) EGO_LAUNCH_MARCH(true, 2); else EGO_LAUNCH_MARCH(true, 1);
-  } else {
-    if (nsplit == 2) EGO_LAUNCH_MARCH(false, 2); else EGO_LAUNCH_MARCH(false, 1);
+  // the dense form (k_march_density, DENSE): the scene carries the baked node grid of the field this call marches
+  const float* dense = (coarse & 1) ? sc->density_coarse_dense : sc->density_dense;
+  const uint64_t grid_bytes = (uint64_t)f.res[0] * (uint64_t)f.res[1] * (uint64_t)f.res[2] * 16u;
+  if (dense) {
+    EGO_REQUIRE(((uintptr_t)dense & 15) == 0, "march_density: the dense density grid must be 16-byte aligned");
+    EGO_REQUIRE(2 * grid_bytes < ((uint64_t)1 << 32), "march_density: the dense density grid must stay under 4 GB (32-bit byte offsets)");
   }
+  const int nsplit = march_nsplit(N, (S + 63) / 64, dense ? MARCH_DENSE_WAVES : MARCH_WAVES);
+#define EGO_LAUNCH_MARCH(OCC, NS, DENSE, WPE)                                                                                           \
+  k_march_density<16, OCC, NS, DENSE, WPE><<<nblk(N, 4 / NS), 256, 0, (hipStream_t)stream>>>(                                          \
+      make_coords(*sc, (coarse & 2) != 0), make_field(f), (const char*)dense, (uint32_t)grid_bytes, rays, N, S, z_in, r_sched, jitter,   \
+      near_, sc->act_softplus, sc->density_shift, sc->distance_scale, z_out, alpha, alpha_stride, weight, bg_weight, coords_out,          \
+      sigma_out, o, sc->term_eps, fmaxf(sc->weight_thres, 0.f), tile_active)
+#define EGO_LAUNCH_MARCH_NS(OCC, DENSE, WPE) \
+  do { if (nsplit == 2) EGO_LAUNCH_MARCH(OCC, 2, DENSE, WPE); else EGO_LAUNCH_MARCH(OCC, 1, DENSE, WPE); } while (0)
+  if (dense) {
+    if (o.vol) EGO_LAUNCH_MARCH_NS(true, true, MARCH_DENSE_WAVES); else EGO_LAUNCH_MARCH_NS(false, true, MARCH_DENSE_WAVES);
+  } else {
+    if (o.vol) EGO_LAUNCH_MARCH_NS(true, false, MARCH_WAVES); else EGO_LAUNCH_MARCH_NS(false, false, MARCH_WAVES);
+  }
+#undef EGO_LAUNCH_MARCH_NS
 #undef EGO_LAUNCH_MARCH
   return ego_launch_status("k_march_density");
 }

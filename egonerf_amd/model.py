@@ -343,7 +343,7 @@ class YinYangAlphaGridMask(torch.nn.Module):
 class _SceneEntry:
     """EgoNeRF's one cached ego_scene struct, with everything the struct points to that nobody else keeps alive."""
 
-    def __init__(self, blobs=None, app16=None):
+    def __init__(self, blobs=None, app16=None, dense=None):
         self.key = None      # EgoNeRF._scene_key() the struct was built for; None: nothing cached
         self.struct = None
         self.holds = ()      # detached MLP / basis weights behind mlp_w, mlp_b, basis
@@ -351,6 +351,8 @@ class _SceneEntry:
         self.mask = None     # model.alphaMask at build time: its packed() / cell_or() buffers are behind occ, occ_cell
         self.blobs = {} if blobs is None else blobs   # {training: packed MLP / basis image}; outlives an invalidation
         self.app16 = app16   # (appearance table versions, [12 half tables]) behind app16; outlives an invalidation
+        # {"full" / "coarse": (table versions, baked node grid)} behind density_dense / density_coarse_dense; outlives an invalidation
+        self.dense = dense
 
 
 class EgoNeRF(TensorBase):
@@ -381,6 +383,12 @@ class EgoNeRF(TensorBase):
         # at construction) = the float-atomic scatters of rounds 1-4 (run-to-run differences of ~1e-6 of the largest gradient).
         self.deterministic_scatter = os.environ.get("EGO_SCATTER", "sorted") != "atomic"
         self._app_table_dtype = "f32"   # "f16": inference gathers appearance taps from a half-precision copy of the tables
+        # Inference of the tuned shape marches its 16-component density field from its baked node grid (csrc/ego_dense.hip): 8 taps of 16 B
+        # per sample instead of 18 of 64 B, for 2 x N_r N_theta N_phi x 16 B of device memory (426 MB at [150, 172, 516]; the pooled
+        # field adds an eighth).  Part of the scene key.  EGO_DENSE_DENSITY=0|1 in the environment overrides the attribute; the grid is
+        # baked only while it fits EGO_DENSE_DENSITY_MAX_MB (default 1024) and a quarter of the free device memory - see _fill_dense.
+        self.dense_density = True
+        self._coarse_epoch = 0   # counts update_coarse_sigma_grid() calls: the pooled tables are rewritten behind torch's version counters
         # opt-in skipping (EgoNeRF.forward itself evaluates every sample; TensorBase.forward's semantics, tensorBase.py:464-487,
         # pinned to the reference by tests/golden/skip_semantics.npz; see include/egonerf_hip.h):
         self.use_alpha_mask = False          # apply self.alphaMask with TensorBase.forward's semantics (sigma = 0 where empty)
@@ -533,6 +541,7 @@ class EgoNeRF(TensorBase):
         self._fill_field(fs, "density")
         self._fill_field(fd, "density", coarse=True)
         _call("ego_avgpool_field", C.byref(fs), C.byref(fd), st)
+        self._coarse_epoch = getattr(self, "_coarse_epoch", 0) + 1
 
     @property
     def is_tuned_shape(self) -> bool:
@@ -618,9 +627,10 @@ class EgoNeRF(TensorBase):
         field_tables.fill_pointers(f, field_tables.tables(self, kind, coarse) if tensors is None else tensors)
 
     def invalidate_scene(self, moved: bool = False) -> None:
-        """The next scene() call builds the struct anew.  The per-mode packed blobs and the half tables stay (an earlier struct or a captured
-        graph may point into them; reused while device, size and table versions stand) unless the whole model `moved` (Module._apply)."""
-        self._scene = _SceneEntry() if moved else _SceneEntry(self._scene.blobs, self._scene.app16)
+        """The next scene() call builds the struct anew.  The per-mode packed blobs, the half tables and the baked density grids stay (an
+        earlier struct or a captured graph may point into them; reused while device, size and table versions stand) unless the whole
+        model `moved` (Module._apply)."""
+        self._scene = _SceneEntry() if moved else _SceneEntry(self._scene.blobs, self._scene.app16, self._scene.dense)
 
     def packed_blob(self, training: bool = False) -> Optional[torch.Tensor]:
         """The packed MLP / basis image of a mode as of the last scene(training) call (None before the first)."""
@@ -630,18 +640,49 @@ class EgoNeRF(TensorBase):
         co = self.coordinates
         return [co.lut_device(dev, 2)] + ([] if co.interval_th else [co.lut_device(dev, None)])
 
+    def _dense_wanted(self) -> bool:
+        """The dense density route is asked for (attribute, EGO_DENSE_DENSITY) and the model is one it serves: the tuned shape (16
+        density components and the tuned head, every shipped config).  The any-shape kernels keep the factored march: their eval
+        results are pinned bit for bit to a recorded build (tests/test_hip_shape_corners.py)."""
+        env = os.environ.get("EGO_DENSE_DENSITY", "")
+        on = bool(self.dense_density) if env == "" else env != "0"
+        return on and tuple(self.density_n_comp) == (16, 16, 16) and self.is_tuned_shape
+
+    def _dense_versions(self, coarse: bool) -> tuple:
+        """What a baked node grid is a function of: the (address, version) pairs of the field's 12 tables.  The pooled tables are also
+        rewritten in place behind torch's version counters: by update_coarse_sigma_grid(), which _coarse_epoch counts, and by a
+        replayed GraphedTrainStep that captured it, where no Python runs at all - but such a replay has stepped the full tables, whose
+        versions GraphedTrainStep bumps.  So the pooled grid's key holds the full field's pairs too: it is baked again (0.06 ms at
+        [75, 86, 258]) whenever the full grid is."""
+        pairs = lambda c: tuple((t.data_ptr(), t._version) for t in field_tables.tables(self, "density", c))
+        return pairs(True) + (self._coarse_epoch,) + pairs(False) if coarse else pairs(False)
+
+    @staticmethod
+    def _dense_cap_bytes() -> float:
+        raw = os.environ.get("EGO_DENSE_DENSITY_MAX_MB", "")
+        try:
+            return float(raw or 1024) * 2 ** 20
+        except ValueError:
+            raise ValueError(f"EGO_DENSE_DENSITY_MAX_MB must be a number of megabytes, not {raw!r}") from None
+
     def _scene_key(self, training: bool) -> tuple:
         """Everything the struct is a function of, as one tuple; no device work (the coordinates cache their LUTs).  Addresses stand for
-        allocations, (address, version) pairs for what is copied or packed at build time: the MLP / basis weights, and the appearance
-        tables while their half copy is in use.  id(alphaMask) is sound because the entry holds that mask: no other object can get its id."""
+        allocations, (address, version) pairs for what is copied or packed at build time: the MLP / basis weights, the appearance
+        tables while their half copy is in use, and the density tables (full and pooled) while the dense route is asked for, with the
+        switch and its cap.  id(alphaMask) is sound because the entry holds that mask: no other object can get its id."""
         co = self.coordinates
         copied = self._mlp_tensors() + (field_tables.tables(self, "app") if self._app_table_dtype == "f16" else [])
+        dense = ()
+        if not training and self._dense_wanted():
+            has_coarse = self.coarse_sigma_plane_yin[0] is not None
+            dense = (os.environ.get("EGO_DENSE_DENSITY_MAX_MB", ""), self._dense_versions(False),
+                     self._dense_versions(True) if has_coarse else None)
         return (tuple(p.data_ptr() for p in self.parameters()), tuple((t.data_ptr(), t._version) for t in copied),
                 None if self.envmap is None else self.envmap.emission.data_ptr(), self.use_alpha_mask, id(self.alphaMask),
                 float(self.early_termination_eps), float(self.rayMarch_weight_thres) if self.use_weight_thres else None,
                 bool(self.skip_zero_weight_tiles), co.N_r, float(co.r0), float(co.far[0]), tuple(co.center.tolist()),
                 tuple(t.data_ptr() for t in self._luts(self.density_plane_yin[0].device)), float(self.distance_scale),
-                float(self.density_shift), self.fea2denseAct, self._mlp_precision, self._app_table_dtype, bool(training))
+                float(self.density_shift), self.fea2denseAct, self._mlp_precision, self._app_table_dtype, bool(training), dense)
 
     @_lib.device_guard
     def scene(self, training: bool = False) -> "_lib.Scene":
@@ -656,7 +697,13 @@ class EgoNeRF(TensorBase):
         captured hipGraph that embeds it, reads the refreshed values (what GraphedTrainStep relies on).  The packed MLP / basis images
         are different: a SNAPSHOT taken by this call, one blob per mode (training / inference) - a struct returned earlier keeps reading
         the weights as of its own pack (a captured graph that contains the pack kernel re-packs on every replay); call scene() again
-        after the weights changed.  A holder that needs a frozen snapshot must copy the tables; re-allocation (another shape / device,
+        after the weights changed.  The baked node grids of the density fields (`dense_density`, inference structs only: density_dense
+        and density_coarse_dense, which ego_march_density then reads INSTEAD of the density tables) are SNAPSHOTS too: baked by this call
+        from the tables - the pooled ones as update_coarse_sigma_grid() last left them - and baked again by the next scene() call after
+        a density table changed in place or the pooled tables were refreshed; a holder of an older struct, or a captured graph that
+        embeds one, marches the field as last baked until scene() is called again (the bake rewrites the SAME buffers, so that call is
+        all it takes).  The buffers stay allocated until the model moves or the grid changes size (_fill_dense), whatever struct is
+        cached meanwhile.  A training struct never carries them.  A holder that needs a frozen snapshot must copy the tables; re-allocation (another shape / device,
         tables assigned one by one) invalidates the cached struct and the next scene() call builds a new one.  One struct is cached
         (not one per mode), together with everything it points to that nobody else keeps alive (_SceneEntry)."""
         dev = self.density_plane_yin[0].device
@@ -672,7 +719,7 @@ class EgoNeRF(TensorBase):
         for kind in ("density", "app"):
             if not field_tables.is_compact(field_tables.tables(self, kind)):
                 field_tables.recarve(self, kind, keep_parameters=True)
-        entry = _SceneEntry(self._scene.blobs, self._scene.app16)
+        entry = _SceneEntry(self._scene.blobs, self._scene.app16, self._scene.dense)
         sc = entry.struct = _lib.new_scene()
         entry.luts = self._luts(dev)
         self.coordinates.fill_scene(sc, dev)
@@ -686,6 +733,8 @@ class EgoNeRF(TensorBase):
         self._pack_head(sc, entry, training, dev)
         if self._app_table_dtype == "f16" and not training:
             self._fill_app16(sc, entry)
+        if not training and self._dense_wanted():
+            self._fill_dense(sc, entry, dev)   # (otherwise the pointers stay NULL; grids baked earlier stay allocated, see _fill_dense)
         entry.mask = self.alphaMask
         if self.use_alpha_mask and self.alphaMask is not None:
             self.alphaMask.fill_scene(sc)
@@ -739,6 +788,44 @@ class EgoNeRF(TensorBase):
             entry.app16 = (ver, halves)
         self._fill_field(sc.app16, "app", tensors=entry.app16[1])
         sc.app_f16 = 1
+
+    def _fill_dense(self, sc, entry, dev):
+        """The baked node grids behind density_dense / density_coarse_dense (ego_bake_density_dense), decided once per scene build:
+        baked while the full field's grid is at most EGO_DENSE_DENSITY_MAX_MB (default 1024; 32-bit offsets need it under 4 GB in
+        any case) and what has to be allocated is at most a quarter of the free device memory; otherwise the pointers stay NULL and
+        the march gathers from the tables as before.  A grid is kept across rebuilds and baked again, IN PLACE, when its field's versions
+        changed.  Lifetime: like the packed blobs and the half tables, a grid stays allocated while the model stays on its device and the
+        grid keeps its size - also while a training struct is the cached one, or the switch or the cap has turned the route off - because
+        an inference struct handed out earlier, or a captured graph (FrameRenderer(graph=True)), may still point into it.  It is
+        released only when the model moves (Module._apply) or when a grid of another size replaces it (upsample_volume_grid: the
+        holders of older structs must re-create them then anyway)."""
+        res = [int(v) for v in self.gridSize.tolist()]
+        has_coarse = self.coarse_sigma_plane_yin[0] is not None
+        plan = [("full", False, 32 * res[0] * res[1] * res[2])]
+        if has_coarse:
+            plan.append(("coarse", True, 32 * (res[0] // 2) * (res[1] // 2) * (res[2] // 2)))
+        cap = self._dense_cap_bytes()
+        held = entry.dense if entry.dense is not None else {}
+        fits = lambda h, nbytes: h is not None and h[1].device == dev and h[1].numel() * 4 == nbytes
+        fresh = sum(nbytes for name, _, nbytes in plan if not fits(held.get(name), nbytes))
+        if plan[0][2] > cap or plan[0][2] >= 2 ** 32 or (fresh and fresh > torch.cuda.mem_get_info(dev)[0] // 4):
+            return   # pointers stay NULL; what is held stays held
+        dense = dict(held)
+        for name, coarse, nbytes in plan:
+            h = held.get(name)
+            if not fits(h, nbytes):
+                h = (None, torch.empty(nbytes // 4, device=dev))
+            ver = self._dense_versions(coarse)
+            if h[0] != ver:
+                f = _lib.VmField()
+                self._fill_field(f, "density", coarse=coarse)
+                _call("ego_bake_density_dense", C.byref(f), h[1].data_ptr(), _lib.stream_handle())
+                h = (ver, h[1])
+            dense[name] = h
+        entry.dense = dense
+        sc.density_dense = dense["full"][1].data_ptr()
+        if has_coarse:
+            sc.density_coarse_dense = dense["coarse"][1].data_ptr()
 
     # -- stage methods (reference public API) ----------------------------------------------------------------
     def _sched(self, n_samples: int, device) -> torch.Tensor:

@@ -147,6 +147,13 @@ typedef struct ego_scene {
    * 3, mlp_in = mlp_hidden = 0, mlp_w / mlp_b unused).  'MLP_PE' cannot run in EgoNeRF.forward (it is handed 7-column coordinates for a
    * 3-column encoding), 'SH' crashes there too (its stage op is ego_sh_render). */
   int32_t head;
+  /* Optional baked node grids of the 16-component density fields (inference only; NULL = off; append-only, EGO_ABI_VERSION stays 17):
+   * what ego_bake_density_dense writes for `density` / `density_coarse`, [grid][N_phi][N_theta][N_r][4] float32 at that field's
+   * resolution, 16-byte aligned, both grids under 4 GB together.  ego_march_density then interpolates the field it was asked for from
+   * its grid (8 taps of 16 B per sample) instead of gathering the 18 table taps (1152 B).  A SNAPSHOT of the tables, like `packed`:
+   * bake again after the tables changed. */
+  const float* density_dense;
+  const float* density_coarse_dense;
 } ego_scene;
 
 /* number of floats ego_pack_mlp writes: the packed weight blob used by ego_shade / ego_mlp_fea / ego_app_feature
@@ -415,6 +422,15 @@ int ego_march_density(const ego_scene* sc, const float* rays, int64_t N, int32_t
                       const float* r_sched, const float* jitter, float near_, int32_t coarse, float* z_out,
                       float* alpha, int32_t alpha_stride, float* weight, float* bg_weight, float* coords_out, float* sigma_out,
                       uint8_t* tile_active, void* stream);
+
+/* The node grid behind ego_scene.density_dense / density_coarse_dense (csrc/ego_dense.hip; append-only addition, EGO_ABI_VERSION stays
+ * 17; no reference counterpart): for a 16-component field f, out [grid][N_phi][N_theta][N_r][4] float32 (dev, 16-byte aligned,
+ * 2 * N_r * N_theta * N_phi * 16 bytes < 4 GB) = (G_0, G_1, G_2, 0) with G_i = sum over c of plane[g][i][node] * line[g][i][node], the
+ * plane and line of lookup i read at the voxel's own indices along the axes they span.  The feature of EgoNeRF.compute_densityfeature
+ * (models/EgoNeRF.py:291-347), sum_i relu(sum_c bilerp(plane_i,c) * lerp(line_i,c)), is then sum_i relu(trilerp(G_i)): the plane and the
+ * line interpolate on one lattice along independent axes.  One thread per voxel; the sum over c runs in ascending order as one chain of
+ * fused multiply-adds from 0 (acc = fma(plane_c, line_c, acc), float32), so a bake is a pure function of the tables. */
+int ego_bake_density_dense(const ego_vm_field* f, float* out, void* stream);
 
 /* Per-sample activations the training forward keeps for the backward pass (all dev).  Logical matrices x [M][160] (layer-1
  * inputs), h1, h2 [M][128] (post-ReLU hidden activations), v [M][144] (plane x line products); element kk of lane half h
