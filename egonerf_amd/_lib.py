@@ -174,6 +174,7 @@ PROTOTYPES = {
     "ego_envmap_backward": (C.c_int, [SP, P, I32, P, P, P, P, I64, P, P]),
     "ego_view_grad": (C.c_int, [SP, P, I32, I64, P, I32, P, P, P]),
     "ego_ray_grad": (C.c_int, [SP, P, P, P, P, P, I32, P, P, P, P, P, I64, I32, I32, P, P, P]),
+    "ego_ray_geometry": (C.c_int, [SP, P, P, P, P, I64, I32, I32, F32, P, P, P, P, P]),
     "ego_shade_backward": (C.c_int, [SP, P, P, P, P, C.POINTER(ShadeDump), P, P, P, P, P, P, I64, I32, P]),
     "ego_sh_render": (C.c_int, [P, P, I64, P, P]),
     "ego_shade_train_generic": (C.c_int, [SP, P, P, I64, I32, P, P, I32, P, P, I32, P, I32, P]),

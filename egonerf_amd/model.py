@@ -1143,6 +1143,11 @@ class EgoNeRF(TensorBase):
               depth.data_ptr(), _lib.ptr(bg_map), _lib.ptr(env_map), None, st)
         return rgb_map, depth, bg_map, env_map, alpha
 
+    def render_geometry(self, rays, *args, **kwargs):
+        """Surface normals, accumulated weight and median depth of `rays`: geometry.render_geometry(self, rays, ...)."""
+        from .geometry import render_geometry
+        return render_geometry(self, rays, *args, **kwargs)
+
     # -- checkpoints (EgoNeRF.py:158-187) -----------------------------------------------------------------------------
     def save(self, path, global_step):
         ckpt = {"kwargs": self.get_kwargs(), "state_dict": {k: v.contiguous() for k, v in self.state_dict().items()},

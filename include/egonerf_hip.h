@@ -786,6 +786,27 @@ int ego_ray_grad(const ego_scene* sc, const float* rays, const float* z, const f
                  const float* d_view, const float* g_rgb, const float* rgb_raw, const float* bg_weight, const float* env_map, int64_t N, int32_t S,
                  int32_t fine_pass, float* d_xyz, float* g_rays, void* stream);
 
+/* ---- ray geometry (csrc/ego_geometry.hip; append-only addition, EGO_ABI_VERSION stays 17).  No reference counterpart: the
+ * reference's only geometric output is the expected depth sum_s w_s z_s. ---- */
+/* Surface normal, accumulated weight and quantile depth of N rays from the samples of a march: z, weight [N][S] and coords [N][S][4]
+ * (ego_march_density's z_out / weight / coords_out; coords 16-byte aligned, .w the chart the forward chose).
+ *   f = the density feature of the full-resolution tables of sc->density, sum_i relu(sum_c P_c L_c) (EgoNeRF.compute_densityfeature; n_comp a
+ *       multiple of 4 up to 48, any resolutions >= 2); g_s = grad_xyz f at o + d z_s in the chart coords.w names, the radius cell found on
+ *       sc->r_lut as ego_normalize_coord finds it: what ego_ray_grad computes for dfeat = 1, dfe = NULL.
+ *   n_s = -g_s / |g_s|, 0 where |g_s| is 0 or not finite (every plane dead, outside the grid, r = 0).
+ *   normal [N][3] = sum_s w_s n_s; with normalize != 0 divided by its length (0 stays 0), without it its length is <= acc and says how well
+ *       the ray's normals agree.
+ *   acc [N] = sum_s w_s.
+ *   z_quantile [N] = z of the first sample at which the running sum of w reaches `quantile` (in (0, 1); 0.5: the median depth); 0.0f for a
+ *       ray that never reaches it.
+ *   grad_out [N][S][3] = g_s.
+ * Each output may be NULL, at least one must not be.  A sample with w_s == 0 exactly adds exactly nothing to normal and is not gathered
+ * unless grad_out asks for it; normal has the same bits either way.  All sums run in one fixed order in float32 inside one wave: no atomics,
+ * two calls return the same bits.  Any N >= 0 (0: no-op), any S >= 1, N S < 2^31; bad arguments return EGO_E_BADARG before anything is
+ * queued.  One launch, no host synchronisation. */
+int ego_ray_geometry(const ego_scene* sc, const float* rays, const float* z, const float* coords, const float* weight, int64_t N, int32_t S,
+                     int32_t normalize, float quantile, float* normal, float* acc, float* z_quantile, float* grad_out, void* stream);
+
 typedef struct ego_render_args {
   int32_t n_coarse, n_fine;
   int32_t resampling, use_coarse_sample;
