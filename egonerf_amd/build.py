@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libegonerf_hip.so")
 SOURCES = ["ego_stages.hip", "ego_march.hip", "ego_resample.hip", "ego_runtime.hip", "ego_pack.hip", "ego_shade.hip", "ego_train.hip", "ego_render.hip", "ego_reg.hip", "ego_metrics.hip", "ego_wgrad.hip", "ego_generic.hip", "ego_generic_train.hip", "ego_generic_march.hip", "ego_selftest.hip", "ego_scatter_sorted.hip",
            "ego_scatter_sort.hip", "ego_stage_grad.hip", "ego_compact.hip", "ego_batch.hip", "ego_camera.hip", "ego_msi.hip", "ego_ray_grad.hip", "ego_dense.hip", "ego_geometry.hip"]
-HEADERS = ["ego_device.h", "ego_host.h", "ego_tuned.h", "variants.h", "ego_generic.h", "ego_generic_dev.h", "ego_sorted_geom.h", "ego_vm_grad.h", os.path.join("..", "..", "include", "egonerf_hip.h")]
+HEADERS = ["ego_device.h", "ego_host.h", "ego_tuned.h", "variants.h", "ego_generic.h", "ego_generic_dev.h", "ego_sorted_geom.h", "ego_vm_grad.h", "ego_march.h", os.path.join("..", "..", "include", "egonerf_hip.h")]
 
 
 def _hipcc() -> str:

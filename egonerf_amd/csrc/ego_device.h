@@ -265,22 +265,24 @@ __device__ __forceinline__ bool occ_occupied(const DevOcc& O, int g, float a_r, 
 // occ_occupied from the three axes' taps at O.res, for a caller that has them already: the dense march needs the field's own taps in
 // its phase B, and a mask of the field's resolution (the usual one) then costs no second set-up.  Same decisions, same evaluation
 // order as occ_occupied / occ_sample above, which keep their own text: routed through here, the kernels built on them come out with
-// different code.
+// different code.  The volume here has the resolution of a field whose dense grid the march addresses with 32-bit byte offsets (16 B per
+// voxel, both grids under 4 GB: ego_march_density checks it), so a voxel or cell index of either grid is below 2^28 and is computed in 32
+// bits: base + one VGPR per address instead of a 64-bit multiply chain per lane.
 __device__ __forceinline__ bool occ_occupied_taps(const DevOcc& O, int g, const Lin1 X, const Lin1 Y, const Lin1 Z) {
   if (O.cell) {
     const bool interior = fminf(fminf(fminf(X.w0, X.w1), fminf(Y.w0, Y.w1)), fminf(Z.w0, Z.w1)) > 0.f;
     if (interior) {
-      const int64_t c0 = O.res[0] - 1, c1 = O.res[1] - 1, c2 = O.res[2] - 1;
-      return O.cell[(((int64_t)g * c2 + Z.i0) * c1 + Y.i0) * c0 + X.i0] != 0;
+      const uint32_t c0 = O.res[0] - 1, c1 = O.res[1] - 1, c2 = O.res[2] - 1;
+      return O.cell[(((uint32_t)g * c2 + (uint32_t)Z.i0) * c1 + (uint32_t)Y.i0) * c0 + (uint32_t)X.i0] != 0;
     }
   }
-  const uint8_t* V = O.vol + (int64_t)g * O.res[0] * O.res[1] * O.res[2];
+  const uint32_t r0 = O.res[0], r1 = O.res[1], gv = (uint32_t)g * r0 * r1 * (uint32_t)O.res[2];
   float v = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int ix = (k & 1) ? X.i1 : X.i0, iy = (k & 2) ? Y.i1 : Y.i0, iz = (k & 4) ? Z.i1 : Z.i0;
     const float w = ((k & 1) ? X.w1 : X.w0) * ((k & 2) ? Y.w1 : Y.w0) * ((k & 4) ? Z.w1 : Z.w0);
-    v += w * (float)V[((int64_t)iz * O.res[1] + iy) * O.res[0] + ix];
+    v += w * (float)O.vol[gv + ((uint32_t)iz * r1 + (uint32_t)iy) * r0 + (uint32_t)ix];
   }
   return v > 0.f;
 }
@@ -360,6 +362,21 @@ __device__ __forceinline__ float wave_scan_mul(float v, int /*lane*/) {
   EGO_SCAN_STEP(0x143, 0xc);  // row_bcast:31 -> rows 2, 3
 #undef EGO_SCAN_STEP
   return v;
+}
+
+// The transmittance step of one 64-sample pass (lane = sample; tensorBase.py:22-27), the one body of k_raw2alpha (csrc/ego_stages.hip)
+// and both density marches: alpha from x = sigma * dist, the pass's exclusive product of (1 - alpha + 1e-10) and its total.  A lane
+// without a sample (`ok` false) has alpha 0 and the factor 1.  The transmittance in front of sample s is (carry in front of the pass) * exc.
+struct PassT {
+  float a, exc, tot;
+};
+__device__ __forceinline__ PassT transmittance_step(bool ok, float x, int lane) {
+  const float a = ok ? alpha_from(x) : 0.f;
+  const float t = ok ? __fadd_rn(__fsub_rn(1.f, a), 1e-10f) : 1.f;
+  const float inc = wave_scan_mul(t, lane);
+  float exc = __shfl_up(inc, 1, 64);
+  if (lane == 0) exc = 1.f;
+  return {a, exc, __shfl(inc, 63, 64)};
 }
 
 // Row J - environment map (models/envmap.py:6-14, 26-34).  Direction -> taps in the emission [3][2h][h]: F.normalize, u = (n_z + 1) / 2

@@ -10,8 +10,7 @@ int ego_generic_shade(const ego_scene* sc, const float* rays, const float* coord
                       void* stream);
 int ego_generic_app_feature(const ego_scene* sc, const float* c7n, int64_t M, float* out, void* stream);
 int ego_generic_mlp_fea(const ego_scene* sc, const float* viewdirs, const float* feat, int64_t M, float* rgb, void* stream);
-int ego_generic_march(const ego_scene* sc, const ego_vm_field& f, bool fine_lut, const float* rays, int64_t N, int32_t S, const float* z_in,
-                      const float* r_sched, const float* jitter, float near_, const uint8_t* occ, float* z_out, float* alpha, int32_t alpha_stride,
-                      float* weight, float* bg_weight, float* coords_out, float* sigma_out, uint8_t* tile_active, void* stream);
+struct MarchArgs;   // csrc/ego_march.h
+int ego_generic_march(const MarchArgs& a, void* stream);
 // the envelope of the any-shape kernels (ego_generic.hip, over the shared checks of ego_host.h; asked by all three sources): EGO_OK or the refusal
 int check_generic_shape(const ego_scene* sc, const char* who, bool need_tables, bool need_mlp, bool need_packed = true);

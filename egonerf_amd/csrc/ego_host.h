@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <atomic>
 #include "../../include/egonerf_hip.h"
 #include "ego_device.h"   // DevField, DevCoords, DevOcc; the axis maps and table sizes
 
@@ -44,6 +45,20 @@ inline int ego_launch_status(const char* kernel) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ego_fail((int)e, "%s: launch failed: %s", kernel, hipGetErrorString(e));
   return EGO_OK;
+}
+
+// compute units of the CURRENT device (what sizes a launch by wave slots: the march's split, the sorted walk's grid); queried once per
+// device; racing first calls store the same value
+inline int device_cus() {
+  static std::atomic<int> cus_of[16];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+  int cus = cus_of[dev].load(std::memory_order_relaxed);
+  if (!cus) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    cus_of[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
 }
 
 // ---- the scene's structs -> their kernel-argument copies (ego_device.h), and the checks in front of them ----------------------------

@@ -1188,18 +1188,6 @@ int launch_sorted(const SortedArgs& a, const SortGeom& G, hipStream_t st) {
   return ego_launch_status("k_sorted_line_final");
 }
 
-int device_cus() {
-  static std::atomic<int> cus_of[16];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  int cus = cus_of[dev].load(std::memory_order_relaxed);
-  if (!cus) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    cus_of[dev].store(cus, std::memory_order_relaxed);
-  }
-  return cus;
-}
-
 template <int C, bool DENS, int NW, int U, bool BAS = false, bool RDV = false>
 int launch_walk_nw(const FusedArgs& F, int wg_total, int lds_bytes, hipStream_t st) {
   static std::atomic<int> attr_set{0};

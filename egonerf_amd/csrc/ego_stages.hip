@@ -106,17 +106,12 @@ __global__ void k_raw2alpha(const float* __restrict__ sigma, const float* __rest
   for (int s0 = 0; s0 < S; s0 += 64) {
     const int s = s0 + lane;
     const bool ok = s < S;
-    const float a = ok ? alpha_from(sigma[ray * S + s] * dist[ray * S + s]) : 0.f;
-    const float t = ok ? __fadd_rn(__fsub_rn(1.f, a), 1e-10f) : 1.f;
-    const float inc = wave_scan_mul(t, lane);
-    float exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = 1.f;
-    const float T = carry * exc;
+    const PassT p = transmittance_step(ok, ok ? sigma[ray * S + s] * dist[ray * S + s] : 0.f, lane);
     if (ok) {
-      if (alpha) alpha[ray * S + s] = a;
-      if (weight) weight[ray * S + s] = a * T;
+      if (alpha) alpha[ray * S + s] = p.a;
+      if (weight) weight[ray * S + s] = p.a * (carry * p.exc);
     }
-    carry *= __shfl(inc, 63, 64);
+    carry *= p.tot;
   }
   if (bg && lane == 0) bg[ray] = carry;
 }

@@ -1,6 +1,10 @@
 """ego_march_density with a ray's passes dealt to two waves (few rounds of wave slots, long rays: the 4096 x 512 headline) must return
 the bits of the one-wave-per-ray form: weights, background weight, alpha, distances, tile flags (the coordinates of samples behind an
-exactly opaque prefix are the one documented difference: the one-wave form never evaluates them and writes zeros)."""
+exactly opaque prefix are the one documented difference: the one-wave form never evaluates them and writes zeros).  And every form of it
+(factored / dense, one / two waves per ray, the any-shape kernel) and ego_raw2alpha must return the bytes of a recorded build
+(tests/golden/march_digests.json)."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -51,6 +55,115 @@ def test_two_waves_per_ray_return_the_same_bits(S, n_rays, density_shift, with_a
     assert torch.equal(a[5][shaded], b[5][shaded])   # coordinates wherever a colour is read
     if density_shift is not None and not with_alpha:   # opaque field: the one-wave form stops behind exact zero transmittance
         assert bool((a[1] == 0).any())
+
+
+# ---- the march bit for bit against a recorded build -----------------------------------------------------------------------------------
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "march_digests.json")
+# (field, N, S, coarse, outputs, mask): every value of every column appears with both forms and, where the ray has two passes, both splits.
+#   field    "default" | "opaque" (density_shift 0.0: the transmittance reaches exactly 0, so a march that stores neither alpha nor sigma stops)
+#   N        5: the last workgroup holds one live ray at one wave per ray, and a dead ray pair that must still reach the barriers at two;  67
+#   S        2 (the minimum) | 65 (a one-lane tail pass; tiles straddle rays: the set-only flag rule) | 256 (whole tiles, split 2 + 2) |
+#            449 (8 passes = MARCH_MAXP per deferred half, ragged tail; marched with early_termination_eps = 1e-4)
+#   coarse   0 schedule + jitter | 1 the pooled tables (never masked) | 2 explicit distances, the fine LUT
+#   outputs  "all": alpha with the appended column (alpha_stride = S + 1) and sigma | "few": neither
+#   mask     None | "same": updateAlphaMask() at the field's resolution (the dense form's shared-tap test) | "other": at another one
+MARCH_CASES = [
+    ("default", 5, 2, 0, "all", None), ("default", 67, 65, 0, "all", "same"), ("default", 5, 256, 2, "all", "other"),
+    ("default", 67, 449, 1, "all", None), ("opaque", 5, 449, 0, "few", None), ("opaque", 67, 256, 0, "few", None),
+    ("default", 67, 256, 0, "few", "same"), ("default", 5, 65, 1, "few", None), ("default", 67, 2, 2, "few", "other"),
+    ("opaque", 5, 65, 2, "few", None), ("default", 5, 449, 2, "all", "same"), ("default", 67, 449, 0, "few", "other"),
+    ("opaque", 67, 65, 0, "all", None),
+]
+MASK_QUANTILE = 0.98   # the mask keeps the cells around the densest 2 % of the lattice (3 x 3 x 3 max-pool): a partial mask on any field
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def _digest_model(field, mask, **kw):
+    cfg = synth.SceneConfig(n_voxel=40 ** 3, **kw) if field == "default" else synth.SceneConfig(n_voxel=40 ** 3, density_shift=0.0, **kw)
+    model = synth.build_model(cfg, synth.make_weights(cfg, seed=7), "cuda")
+    if mask is not None:
+        n_r, n_th, n_ph = cfg.grid
+        grid = [n_r, n_th, n_ph] if mask == "same" else [n_r + 3, n_th + 2, n_ph - 3]
+        model.alphaMask_thres = float(torch.quantile(torch.cat([a.flatten() for a in model.getDenseAlpha(grid)]), MASK_QUANTILE))
+        kept = model.updateAlphaMask(grid)
+        assert 0.02 < kept < 0.98, (field, mask, kept)
+        model.use_alpha_mask = True
+    return cfg, model
+
+
+def _digest_march(model, cfg, dense, N, S, coarse, outputs):
+    """One ego_march_density with every output buffer zero-initialised -> {buffer: sha256 of all of it}"""
+    lib, st, dev = _lib.load(), _lib.stream_handle(), "cuda"
+    model.early_termination_eps = 1e-4 if S == 449 else 0.0
+    model.invalidate_scene()
+    sc = _lib.Scene.from_buffer_copy(model.scene())
+    if not dense:
+        sc.density_dense = sc.density_coarse_dense = None
+    assert bool(sc.density_coarse_dense if coarse & 1 else sc.density_dense) == dense
+    rays = torch.from_numpy(synth.make_rays(N, seed=5)).to(dev)
+    sched = model._sched(S, dev)
+    u = torch.from_numpy(synth.hash_uniform(31, S, N * S).reshape(N, S).astype(np.float32)).to(dev)
+    z_in = torch.sort(cfg.near + sched[None] + 0.01 * u, 1).values.contiguous() if coarse == 2 else None
+    jitter = u if coarse == 0 else None
+    z, w, bg, crd = torch.zeros(N, S, device=dev), torch.zeros(N, S, device=dev), torch.zeros(N, device=dev), torch.zeros(N, S, 4, device=dev)
+    alpha, sigma = (torch.zeros(N, S + 1, device=dev), torch.zeros(N, S, device=dev)) if outputs == "all" else (None, None)
+    act = torch.zeros((N * S + 31) // 32, device=dev, dtype=torch.uint8)
+    _lib.check(lib.ego_march_density(sc, rays.data_ptr(), N, S, _lib.ptr(z_in), None if coarse == 2 else sched.data_ptr(), _lib.ptr(jitter), cfg.near,
+                                     coarse, z.data_ptr(), _lib.ptr(alpha), S + 1 if alpha is not None else 0, w.data_ptr(), bg.data_ptr(),
+                                     crd.data_ptr(), _lib.ptr(sigma), act.data_ptr(), st), "march")
+    torch.cuda.synchronize()
+    print(f"  N={N} S={S} coarse={coarse} {outputs} dense={int(dense)} split={os.environ.get('EGO_MARCH_SPLIT')}: weight sum {float(w.sum()):.4f}, "
+          f"weights == 0: {float((w == 0).float().mean()):.3f}, tiles flagged {float(act.float().mean()):.3f}")
+    named = dict(z=z, weight=w, bg=bg, alpha=alpha, sigma=sigma, coords=crd, tile_flags=act)
+    return {k: _sha(t) for k, t in named.items() if t is not None}
+
+
+def march_digests():
+    """case -> {buffer: sha256 of its bytes}: MARCH_CASES through ego_march_density in the factored and the dense form, with one and
+    (two passes or more) two waves per ray; the same entry point on a field of 8 density components (k_march_generic) behind a mask;
+    ego_raw2alpha on 5 x 65.  tools/capture_digests.py records this from another build."""
+    out, models = {}, {}
+    old = os.environ.get("EGO_MARCH_SPLIT")
+    try:
+        for field, N, S, coarse, outputs, mask in MARCH_CASES:
+            if (field, mask) not in models:
+                models[field, mask] = _digest_model(field, mask)
+            cfg, model = models[field, mask]
+            for dense in (False, True):
+                for split in ("1", "2") if S > 64 else ("1",):
+                    os.environ["EGO_MARCH_SPLIT"] = split
+                    out[f"{field} N={N} S={S} coarse={coarse} {outputs} mask={mask} dense={int(dense)} split={split}"] = \
+                        _digest_march(model, cfg, dense, N, S, coarse, outputs)
+        os.environ.pop("EGO_MARCH_SPLIT", None)
+        cfg, model = _digest_model("default", "same", density_n_comp=(8, 8, 8))
+        out["8 components N=5 S=65 coarse=0 all mask=same"] = _digest_march(model, cfg, False, 5, 65, 0, "all")
+    finally:
+        os.environ.pop("EGO_MARCH_SPLIT", None)
+        if old is not None:
+            os.environ["EGO_MARCH_SPLIT"] = old
+    N, S = 5, 65
+    sigma = torch.from_numpy((synth.hash_uniform(32, 0, N * S) * 40.0).reshape(N, S).astype(np.float32)).cuda()
+    dist = torch.from_numpy((synth.hash_uniform(32, 1, N * S) * 0.05).reshape(N, S).astype(np.float32)).cuda()
+    alpha, w, bg = torch.zeros(N, S, device="cuda"), torch.zeros(N, S, device="cuda"), torch.zeros(N, device="cuda")
+    _lib.check(_lib.load().ego_raw2alpha(sigma.data_ptr(), dist.data_ptr(), N, S, alpha.data_ptr(), w.data_ptr(), bg.data_ptr(), _lib.stream_handle()),
+               "raw2alpha")
+    torch.cuda.synchronize()
+    out["raw2alpha N=5 S=65"] = dict(alpha=_sha(alpha), weight=_sha(w), bg=_sha(bg))
+    return out
+
+
+def test_march_bits_match_recorded():
+    """The march kernels have no atomics on their outputs, so a rewrite that keeps their arithmetic returns the recorded build's bytes:
+    equality, no tolerance.  The fixture names the commit it was recorded from (never the tree under test)."""
+    recorded = json.load(open(DIGESTS))["digests"]
+    got = march_digests()
+    n_tuned = sum(2 * (2 if S > 64 else 1) for _, _, S, *_ in MARCH_CASES)
+    assert len(got) == n_tuned + 2 and {c: sorted(d) for c, d in got.items()} == {c: sorted(d) for c, d in recorded.items()}
+    differs = [f"{case}: {name}" for case in got for name in got[case] if got[case][name] != recorded[case][name]]
+    assert not differs, differs
 
 
 @pytest.mark.parametrize("kw", [dict(n_coarse=512), dict(n_coarse=64, n_fine=64, resampling=True), dict(n_coarse=96)])

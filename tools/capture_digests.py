@@ -5,9 +5,11 @@ bit-equality test, from ANOTHER build of the library (the commit a rewrite of th
         [--digests tests.test_hip_resampling:sample_pdf_digests --out tests/golden/resample_digests.json]
     python tools/capture_digests.py PARENT.so --commit <hash> --digests tests.test_hip_shape_corners:generic_digests \
         --out tests/golden/generic_digests.json
+    python tools/capture_digests.py PARENT.so --commit <hash> --digests tests.test_hip_march_split:march_digests \
+        --out tests/golden/march_digests.json
 
-The cases, their inputs and the launches are the test module's own (test_sample_pdf_bits_match_recorded / test_generic_bits_match_recorded
-call the same function).  Every case is captured twice; the file is written only if the two captures agree (the kernels have no atomics:
+The cases, their inputs and the launches are the test module's own (test_sample_pdf_bits_match_recorded / test_generic_bits_match_recorded /
+test_march_bits_match_recorded call the same function).  Every case is captured twice; the file is written only if the two captures agree (the kernels have no atomics:
 a difference is a finding)."""
 from __future__ import annotations
 

@@ -11,6 +11,7 @@ Per kernel (matched by demangled name over all code objects of a library, so a k
     kernel itself.  The padding behind a kernel's last instruction is not part of the stream: zeros (printed as `...`), and the run of
     `s_nop 0` that closes a source's text section behind its last kernel (which kernel that is changes when kernels change sources).
 The compiler gives kernels of an anonymous namespace no per-file decoration in this (non-RDC) build, so names compare as they are.
+A kernel whose parameter list changed (and nothing else of its name) is matched with its predecessor and compared like any other.
 A kernel that differs is listed with the resource line of both builds.  Exit status 1 if the kernel sets differ or any kernel differs."""
 from __future__ import annotations
 
@@ -100,6 +101,26 @@ def kernels(lib: str) -> dict:
     return out
 
 
+def _without_parameters(name: str) -> str:
+    """`void k<16, true>(A, B (*)(C))` -> `void k<16, true>`: the demangled name up to its (balanced) trailing parameter list"""
+    depth = 0
+    for i in range(len(name) - 1, -1, -1):
+        depth += (name[i] == ")") - (name[i] == "(")
+        if depth == 0:
+            return name[:i] if name.endswith(")") else name
+    return name
+
+
+def pair_changed_signatures(old: dict, new: dict) -> None:
+    """A kernel whose parameter list changed keeps its name and template arguments: what is left unmatched on both sides is matched by
+    those, and listed under the new build's name."""
+    lone = {_without_parameters(n): n for n in old if n not in new}
+    for n in [n for n in new if n not in old]:
+        o = lone.get(_without_parameters(n))
+        if o is not None:
+            old[n] = old.pop(o)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old")
@@ -107,6 +128,7 @@ def main() -> int:
     ap.add_argument("-o", "--out")
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
+    pair_changed_signatures(old, new)
     lines, n_same, n_diff = [], 0, 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new or len(old[name]) != len(new[name]):

@@ -1,11 +1,37 @@
 """Event-timed ego_march_density in the three shapes the benches use (4096 x 512 headline; 16384 x 128 coarse on the pooled tables and
-16384 x 256 fine with explicit distances: the ERP chunk), plus a checksum of the outputs so that variants can be compared."""
+16384 x 256 fine with explicit distances: the ERP chunk), plus a checksum of the outputs so that variants can be compared.
+`masked`: instead, the masked instances: the fine march of bench.py's erp_masked chunk (carved field, updateAlphaMask(), 16384 x 256)
+with the mask off and on, three rounds of bench.erp_chunk_split with 60 repetitions each, and their ratio (tests/test_hip_multirank.py
+asks for less than 1.08 of one 12-repetition round).
+`--lib PATH`: time another build of the library (an A/B against a parent build: one process per build, alternated by the caller)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from egonerf_amd import _lib, synth
+if "--lib" in sys.argv:
+    i = sys.argv.index("--lib")
+    os.environ["EGO_ALLOW_STALE_LIB"] = "1"   # the timed build is not the tree's
+    _lib.LIB = os.path.abspath(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 lib, st = _lib.load(), _lib.stream_handle()
 dev = "cuda"
+if "masked" in sys.argv[1:]:
+    import bench
+    from egonerf_amd.renderer import erp_rays
+    cfg = synth.SceneConfig(**synth.RICOH)
+    model = synth.build_model(cfg, synth.carve_empty_space(synth.make_weights(cfg, seed=1234), cfg), dev)
+    rays_c = erp_rays(1024, 2048, bench.erp_pose(0, 2), dev, 1024 // 3, 8)[:16384].contiguous()
+    with torch.no_grad():
+        occupied, fine = model.updateAlphaMask(), {False: [], True: []}
+        for _ in range(3):
+            for on in (False, True):
+                model.use_alpha_mask = on
+                model.invalidate_scene()
+                fine[on].append(bench.erp_chunk_split(model, rays_c, reps=60)[0]["k_march_density(fine)"] * 1e3)
+    txt = lambda v: " ".join(f"{x:.1f}" for x in v)
+    print(f"march masked 16384x256 fine (occupied {occupied:.3f}) off {txt(fine[False])} us | on {txt(fine[True])} us | "
+          f"on / off {np.median(fine[True]) / np.median(fine[False]):.4f}")
+    sys.exit(0)
 cfg = synth.SceneConfig()
 model = synth.build_model(cfg, synth.make_weights(cfg, seed=1234), dev)
 sc = model.scene()
