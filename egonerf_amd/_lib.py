@@ -89,6 +89,13 @@ class RayBankStruct(C.Structure):
                 ("r0", C.c_int32), ("n_rows", C.c_int32), ("c0", C.c_int32), ("n_cols", C.c_int32), ("normalize", C.c_int32)]
 
 
+class LatticeStruct(C.Structure):
+    """ego_lattice: a box or panorama lattice of nodes (egonerf_amd.geometry.Lattice fills it)."""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32 * 3), ("origin", C.c_float * 3), ("step", C.c_float * 3), ("radii", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("c2w", C.c_float * 12), ("flip", C.c_int32), ("reserved", C.c_int32)]
+
+
+LATTICE_BOX, LATTICE_PANORAMA = 0, 1   # EGO_LATTICE_*
 BATCH_SIMPLE, BATCH_THETA = 0, 1   # EGO_BATCH_* of include/egonerf_hip.h
 CAM_ERP, CAM_PINHOLE, CAM_PINHOLE_BLENDER = 0, 1, 2   # EGO_CAM_*
 EYE_CENTRE, EYE_LEFT, EYE_RIGHT = 0, 1, 2   # EGO_EYE_*
@@ -175,6 +182,11 @@ PROTOTYPES = {
     "ego_view_grad": (C.c_int, [SP, P, I32, I64, P, I32, P, P, P]),
     "ego_ray_grad": (C.c_int, [SP, P, P, P, P, P, I32, P, P, P, P, P, I64, I32, I32, P, P, P]),
     "ego_ray_geometry": (C.c_int, [SP, P, P, P, P, I64, I32, I32, F32, P, P, P, P, P]),
+    "ego_mesh_field": (C.c_int, [SP, C.POINTER(LatticeStruct), P, P]),
+    "ego_mesh_workspace_bytes": (I64, [C.POINTER(LatticeStruct)]),
+    "ego_mesh_count": (C.c_int, [C.POINTER(LatticeStruct), P, F32, P, I64, P, P]),
+    "ego_mesh_emit": (C.c_int, [C.POINTER(LatticeStruct), P, F32, P, I64, I64, P, P, P]),
+    "ego_point_gradient": (C.c_int, [SP, P, I64, I32, P, P]),
     "ego_shade_backward": (C.c_int, [SP, P, P, P, P, C.POINTER(ShadeDump), P, P, P, P, P, P, I64, I32, P]),
     "ego_sh_render": (C.c_int, [P, P, I64, P, P]),
     "ego_shade_train_generic": (C.c_int, [SP, P, P, I64, I32, P, P, I32, P, P, I32, P, I32, P]),

@@ -38,20 +38,6 @@ __device__ __forceinline__ float wave_scan_add(float v) {
   return v;
 }
 
-// v / |v| without overflow or underflow in the squares: scaled by the largest component first.  0 for v = 0 and for anything not finite
-__device__ __forceinline__ void unit3(const float v[3], float out[3]) {
-  out[0] = out[1] = out[2] = 0.f;
-  const float big = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
-  const bool finite = fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY;   // false for NaN too
-  if (!(big > 0.f) || !finite) return;
-  // (reciprocal and reciprocal square root to 1 ulp, v_rcp_f32 / v_rsq_f32, as chart_jt: the IEEE divisions and the root were a
-  // seventh of the kernel's vector instructions)
-  const float rb = __frcp_rn(big);
-  const float a = __fmul_rn(v[0], rb), b = __fmul_rn(v[1], rb), c = __fmul_rn(v[2], rb);
-  const float rl = __builtin_amdgcn_rsqf(__fadd_rn(__fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)), __fmul_rn(c, c)));   // the sum is in [1, 3]
-  out[0] = __fmul_rn(a, rl); out[1] = __fmul_rn(b, rl); out[2] = __fmul_rn(c, rl);
-}
-
 // Work split: k_ray_grad's (a wave owns a ray, a 16-lane row a sample, lane = channel 16 at a time, row_sum16 over channels), behind a
 // lane = sample pass over each 64 samples of the ray: their weights, distances and coordinates are read coalesced (one 64 ahead) and
 // handed to the rows by cross-lane reads, the weights are scanned for the running sum (acc, the quantile) and balloted, and

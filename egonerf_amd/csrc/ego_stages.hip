@@ -2,6 +2,7 @@
 // camera rays.  gfx950 only.
 #include "ego_device.h"
 #include "ego_host.h"
+#include "ego_density.h"
 
 // =============================================================================================
 // Row A  — sample schedule -> points (sched_z: ego_device.h)      models/EgoNeRF.py:56-87
@@ -52,30 +53,8 @@ __global__ void k_normalize_coord(DevCoords c, const float* __restrict__ c7, int
 
 // =============================================================================================
 // Row D / D' — density feature: sum_i relu(sum_c P_ic * L_ic)      models/EgoNeRF.py:291-347, 232-289
-// lane = sample; one bilinear tap = C contiguous floats (C/4 x 16-byte loads).  (k_march_generic, csrc/ego_generic_march.hip, holds the
-// same sum with C at run time: called from there, this body changes that kernel's load schedule.)
+// lane = sample; the lookup itself is density_lookup<C> (ego_density.h).
 // =============================================================================================
-template <int C>
-__device__ __forceinline__ float density_lookup(const DevField& F, int g, float a_r, float a_th, float a_ph) {
-#pragma clang fp contract(fast)  // the library is built with -ffp-contract=off; interpolation may use FMAs
-  const VMTaps t = vm_setup(a_r, a_th, a_ph, F.res);
-  float feat = 0.f;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const PlaneTaps T = EGO_PLANE_TAPS_OF(F, C, g, i, t.ax);
-    float dot = 0.f;
-#pragma unroll
-    for (int c4 = 0; c4 < C; c4 += 4) {
-      const f32x4 pv = tap4(T.p00, c4) * T.w00 + tap4(T.p01, c4) * T.w01 + tap4(T.p10, c4) * T.w10 + tap4(T.p11, c4) * T.w11;
-      const f32x4 lv = tap4(T.l0, c4) * T.wl0 + tap4(T.l1, c4) * T.wl1;
-      const f32x4 m = pv * lv;
-      dot += (m.x + m.y) + (m.z + m.w);
-    }
-    feat += fmaxf(dot, 0.f);
-  }
-  return feat;
-}
-
 template <int C>
 __global__ void k_density_feature(DevField F, const float* __restrict__ c7n, int64_t M, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

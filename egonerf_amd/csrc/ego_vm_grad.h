@@ -1,6 +1,7 @@
-// The positional derivative of a vector-matrix lookup, shared by the ray gradients (csrc/ego_ray_grad.hip) and the ray
-// geometry (csrc/ego_geometry.hip): d (sum_c P_c L_c) / d (r^, theta^, phi^) per plane, and the chart's Jacobian back to xyz.
-// Work split of both callers: a 16-lane row owns a sample, lane = channel 16 at a time.
+// The positional derivative of a vector-matrix lookup, shared by the ray gradients (csrc/ego_ray_grad.hip), the ray
+// geometry (csrc/ego_geometry.hip) and the point gradients of the mesh extraction (csrc/ego_mesh.hip):
+// d (sum_c P_c L_c) / d (r^, theta^, phi^) per plane, the chart's Jacobian back to xyz, and the unit vector of the result.
+// Work split of every caller: a 16-lane row owns a sample, lane = channel 16 at a time.
 #pragma once
 #include "ego_device.h"
 
@@ -74,6 +75,20 @@ __device__ __forceinline__ void chart_jt(const DevCoords& c, const float* lut, i
   const float ox = yang ? -ga : ga, oy = yang ? gc : gb, oz = yang ? gb : gc;
   const bool ok = fabsf(ox) < INFINITY && fabsf(oy) < INFINITY && fabsf(oz) < INFINITY;   // false for NaN too
   if (ok) { out[0] = ox; out[1] = oy; out[2] = oz; }
+}
+
+// v / |v| without overflow or underflow in the squares: scaled by the largest component first.  0 for v = 0 and for anything not finite
+__device__ __forceinline__ void unit3(const float v[3], float out[3]) {
+  out[0] = out[1] = out[2] = 0.f;
+  const float big = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
+  const bool finite = fabsf(v[0]) < INFINITY && fabsf(v[1]) < INFINITY && fabsf(v[2]) < INFINITY;   // false for NaN too
+  if (!(big > 0.f) || !finite) return;
+  // (reciprocal and reciprocal square root to 1 ulp, v_rcp_f32 / v_rsq_f32, as chart_jt: the IEEE divisions and the root were a
+  // seventh of the kernel's vector instructions)
+  const float rb = __frcp_rn(big);
+  const float a = __fmul_rn(v[0], rb), b = __fmul_rn(v[1], rb), c = __fmul_rn(v[2], rb);
+  const float rl = __builtin_amdgcn_rsqf(__fadd_rn(__fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)), __fmul_rn(c, c)));   // the sum is in [1, 3]
+  out[0] = __fmul_rn(a, rl); out[1] = __fmul_rn(b, rl); out[2] = __fmul_rn(c, rl);
 }
 
 constexpr int RG_LUT_LDS = 1024;  // radius LUTs up to this many entries are walked in LDS

@@ -1148,6 +1148,11 @@ class EgoNeRF(TensorBase):
         from .geometry import render_geometry
         return render_geometry(self, rays, *args, **kwargs)
 
+    def extract_mesh(self, lattice, level, **kwargs):
+        """The triangle mesh of the surface sigma = level on `lattice`: geometry.extract_mesh(self, lattice, level, ...)."""
+        from .geometry import extract_mesh
+        return extract_mesh(self, lattice, level, **kwargs)
+
     # -- checkpoints (EgoNeRF.py:158-187) -----------------------------------------------------------------------------
     def save(self, path, global_step):
         ckpt = {"kwargs": self.get_kwargs(), "state_dict": {k: v.contiguous() for k, v in self.state_dict().items()},

@@ -807,6 +807,57 @@ int ego_ray_grad(const ego_scene* sc, const float* rays, const float* z, const f
 int ego_ray_geometry(const ego_scene* sc, const float* rays, const float* z, const float* coords, const float* weight, int64_t N, int32_t S,
                      int32_t normalize, float quantile, float* normal, float* acc, float* z_quantile, float* grad_out, void* stream);
 
+/* ---- triangle meshes (csrc/ego_mesh.hip; append-only addition, EGO_ABI_VERSION stays 17).  The reference meshes with
+ * skimage's marching cubes on a Cartesian alpha volume (--export_mesh); this is the field on a lattice and an extractor on the device. ---- */
+#define EGO_LATTICE_BOX 0
+#define EGO_LATTICE_PANORAMA 1
+/* A lattice of n[0] x n[1] x n[2] nodes, axis 0 fastest: node id = (i2 n[1] + i1) n[0] + i0, below 2^31; every n >= 2.
+ *   box:      axes (x, y, z); position = fadd(origin, fmul((float)i, step)) per axis, every operation rounded once.
+ *   panorama: axes (radius index, row, col), n = (number of radii, H, W), W >= 3; position = fadd(o, fmul(radii[i0], d)) with (o, d) the
+ *             ego_erp_rays ray of pixel (row, col) of an H x W panorama with pose c2w, normalize = 1: the pixel centres, no node on a pole.
+ *             radii: dev [n[0]], strictly increasing, > 0.  Axis 2 wraps: the cells of column W - 1 have column 0 as their far side (W
+ *             cells along the axis); the two polar caps, half a pixel wide, stay open.
+ * flip: 1 when (axis 0, axis 1, axis 2) is a left-handed frame (panorama: rows run down, columns clockwise seen from above), else 0. */
+typedef struct ego_lattice {
+  int32_t kind; /* EGO_LATTICE_* */
+  int32_t n[3];
+  float origin[3], step[3]; /* box */
+  const float* radii;       /* panorama */
+  int32_t H, W;
+  float c2w[12]; /* 3x4 row-major */
+  int32_t flip;
+  int32_t reserved;
+} ego_lattice;
+
+/* values[node] = sigma at the node: ego_from_cartesian -> ego_normalize_coord -> ego_density_feature(coarse = 0) -> ego_feature2density in one
+ * kernel, lane = node, on the full-resolution factored tables of sc->density (every n_comp ego_density_feature takes).  values: dev [count]. */
+int ego_mesh_field(const ego_scene* sc, const ego_lattice* lat, float* values, void* stream);
+
+/* The iso-surface value = level of any float32 array values [count] on the lattice: marching tetrahedra on the Kuhn decomposition.
+ *   A cell's corners are the bit triples b (bit a = one step along axis a) over its low node; its six tetrahedra, for the axis
+ *   permutations p = (0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0) in this order, have the corners 000, e_p0, e_p0 + e_p1, 111.
+ *   Every tetrahedron edge runs from a corner a to a corner b that contains it and is OWNED by the node at a, local index
+ *   k = bits(b - a) - 1 in 0..6 (three axis edges, three face diagonals, the body diagonal); far nodes on a wrapping axis modulo W.
+ *   A node is inside when value >= level (NaN: outside); an owned edge carries a vertex when exactly one end is inside, at
+ *   pa + t (pb - pa), t = (level - fa) / (fb - fa) clamped to [0, 1], 0.5 when not finite, a = the owner, float32 operations rounded once.
+ *   Vertex ids increase with (node id, k); faces are ordered by (cell id = id of its low node, tetrahedron, triangle), a tetrahedron
+ *   giving 0, 1 or 2; (v1 - v0) x (v2 - v0) points to the outside (lower values).  tests/mesh_ref.py restates all of it in numpy.
+ * ego_mesh_count classifies the nodes, marks every node's crossing owned edges, counts the triangles per cell, scans both counts
+ *   (per-workgroup sums, one scan of the sums; the offsets are applied by ego_mesh_emit) and writes counts_dev[0] = V, counts_dev[1] = F
+ *   (dev int64 [2]).  workspace: dev, 256-byte aligned, ego_mesh_workspace_bytes(lat) bytes (-1: bad lattice), about 6 bytes per node.
+ * ego_mesh_emit, after the caller has read V and F back (the one host synchronisation of an extraction), writes vertices [V][3] float32 and
+ *   faces [F][3] int32 from the same values, level and workspace; V and F below 2^31; V = F = 0 queues nothing.
+ * No atomics: two calls return the same bits.  Bad arguments return EGO_E_BADARG before anything is queued. */
+int64_t ego_mesh_workspace_bytes(const ego_lattice* lat);
+int ego_mesh_count(const ego_lattice* lat, const float* values, float level, void* workspace, int64_t bytes, int64_t* counts_dev, void* stream);
+int ego_mesh_emit(const ego_lattice* lat, const float* values, float level, const void* workspace, int64_t V, int64_t F, float* vertices,
+                  int32_t* faces, void* stream);
+
+/* out [M][3] = grad_xyz f of the density feature (ego_ray_geometry's f and g_s) at M arbitrary points xyz [M][3], the chart chosen as
+ * ego_from_cartesian chooses it; with normalize != 0, -grad f / |grad f| instead.  0 where the gradient is 0 or not finite.  One 16-lane
+ * row per point, a fixed summation order: two calls return the same bits.  Any M >= 0 (0: no-op); one launch, no host synchronisation. */
+int ego_point_gradient(const ego_scene* sc, const float* xyz, int64_t M, int32_t normalize, float* out, void* stream);
+
 typedef struct ego_render_args {
   int32_t n_coarse, n_fine;
   int32_t resampling, use_coarse_sample;
