@@ -2,6 +2,7 @@
 weight threshold, only the live samples (weight > max(weight_thres, 0), tensorBase.py:480-487's app_mask) are shaded, in tiles cut
 from a list of them.  It must return the bits of the tile path (EGO_RENDER_COMPACT=0) and of the folded path where that applies, and
 report exactly the live count as the number of shaded samples."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -244,3 +245,37 @@ def test_mlp_head_falls_back():
     a, _ = render(model, rays, "0", n_coarse=128)
     b, _ = render(model, rays, "1", n_coarse=128)
     assert_same(a, b, "MLP head")
+
+
+def test_compact_scan_with_runs_of_two_blocks():
+    """65 537 rays make 1025 blocks of the live count: every thread of the one-workgroup scan then owns a run of two entries, and the last
+    run holds one.  The list must still be the tile path's samples in the tile path's order, and its length the live count."""
+    model = scene_model("thres", False)
+    model.mlp_precision = "f16f6"
+    N, S = 65537, 16
+    rays = erp_rays(257, 256, np.eye(4, dtype=np.float32)[:3], DEV)[:N].contiguous()
+    assert rays.shape[0] == N and (N + 63) // 64 == 1025
+    lib = _lib.load()
+    with _env(EGO_RENDER_COMPACT=None):
+        assert lib.ego_render_forward_compacts(model.scene(), N, S) == 1
+    tiles, n_tiles = render(model, rays, "0", n_coarse=S)
+    # The render's workspace comes from torch's caching allocator: a second render of the same size gets the block of the first, the
+    # tile path's colours still in it, and a sample missing from the list would find its colour already there.  So let the model drop
+    # that block (a small render replaces the workspace it keeps) and fill the free blocks of that size with NaN.
+    render(model, rays[:64].contiguous(), "0", n_coarse=S)
+    args = _lib.RenderArgs(n_coarse=S, n_fine=0, resampling=0, use_coarse_sample=1)
+    ws_floats = int(lib.ego_render_workspace_bytes(N, C.byref(args))) // 4
+    assert ws_floats > N * S * 9
+    poison = [torch.full((ws_floats,), float("nan"), device=DEV) for _ in range(2)]
+    torch.cuda.synchronize()
+    del poison
+    comp, n_live = render(model, rays, "1", n_coarse=S)
+    assert_same(tiles, comp, "compact vs tiles, 1025 blocks")
+    thr = max(float(model.scene().weight_thres), 0.0)
+    w = marched_weights(model, rays, S, 0, False)
+    print(f"live {n_live} of {N * S}")
+    assert n_live == int((w > thr).sum())
+    assert 0 < n_live <= n_tiles <= N * S
+    # live samples sit in both entries of the scan's runs, first and last included
+    per_block = (w > thr).sum(1)[:1024 * 64].reshape(1024, 64).sum(1)
+    assert int(per_block[0]) > 0 and int(per_block[1]) > 0 and int(per_block[-1]) > 0 and int((w[1024 * 64:] > thr).sum()) > 0
