@@ -41,6 +41,27 @@ class Scene(C.Structure):
         ("density_dense", C.c_void_p), ("density_coarse_dense", C.c_void_p),
     ]
 
+    # The baked node grid of the appearance features travels in members the struct already has (include/egonerf_hip.h: app_f16 =
+    # EGO_APP_DENSE, app16.plane[0][0] = the grid, app16.res = its resolution); `app_dense` reads and writes that as one pointer.
+    @property
+    def app_dense(self):
+        """Address of the baked appearance-feature grid, or None when the struct does not select it."""
+        return self.app16.plane[0][0] if self.app_f16 == APP_DENSE else None
+
+    @app_dense.setter
+    def app_dense(self, address):
+        if address:
+            self.app16 = VmField()
+            self.app16.plane[0][0], self.app16.n_comp = address, self.app.n_comp
+            self.app16.res[:] = list(self.app.res)
+            self.app_f16 = APP_DENSE
+        elif self.app_f16 == APP_DENSE:
+            self.app16 = VmField()
+            self.app_f16 = APP_TABLES
+
+
+APP_TABLES, APP_HALF, APP_DENSE = 0, 1, 2   # EGO_APP_* (ego_scene.app_f16)
+
 
 def new_scene() -> "Scene":
     """A zero-initialised ego_scene with the opt-in fields that are not 'off' at zero set to off."""
@@ -160,6 +181,7 @@ PROTOTYPES = {
     "ego_packed_floats_compat": (C.c_int64, [SP]),
     "ego_pack_mlp_compat": (C.c_int, [SP, P, P]),
     "ego_bake_density_dense": (C.c_int, [C.POINTER(VmField), P, P]),
+    "ego_bake_app_dense": (C.c_int, [C.POINTER(VmField), P, P, I32, P, P]),
     "ego_march_density": (C.c_int, [SP, P, I64, I32, P, P, P, F32, I32, P, P, I32, P, P, P, P, P, P]),
     "ego_shade_kernel_info": (C.c_int, [I32, C.POINTER(C.c_int32), I32]),
     "ego_shade": (C.c_int, [SP, P, P, P, I64, I32, P, P, P, P]),

@@ -977,6 +977,68 @@ __device__ __forceinline__ void gather_basis_f16(const DevField& F, const VMTaps
   basis_step(f0, v2, keep, fe); basis_step(f1, v2 + 8, keep, fe); basis_step(f2, v2 + 16, keep, fe);
 }
 
+// ---- dense gather (ego_scene.app_f16 = EGO_APP_DENSE): the 27 features as the trilinear interpolation of the baked node grid ------------------------
+// A lane serves its OWN sample and lane half: per cell corner the half's 14 slots are three 16-byte quads and one 8-byte piece of the
+// node (quad 2 q + h of its 128 bytes, csrc/ego_dense.hip), so the two lanes of a sample read the same 64-byte line in every load
+// instruction.  The grid is chosen per lane by the sample's own flag: a wave that straddles the yin / yang border needs nothing special,
+// and a lane's result depends on its own sample only.  Interpolation along r, then theta, then phi (the dense march's order), fp32,
+// every weight in a register pair of its own (dense_weight).  The r pairs are reduced as they land: two pairs of loads in flight.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+struct DenseCorner {
+  f32x4 a, b, c;
+  f32x2 d;
+};
+__device__ __forceinline__ DenseCorner dense_corner(const char* __restrict__ G, uint32_t off) {
+  DenseCorner n;
+  n.a = *(const f32x4*)(G + off); n.b = *(const f32x4*)(G + off + 32); n.c = *(const f32x4*)(G + off + 64); n.d = *(const f32x2*)(G + off + 96);
+  return n;
+}
+// a weight is a register PAIR holding it twice, opaque to the compiler: a packed multiply then reads the pair as it stands and
+// broadcasts neither half (pinned scalars alone still came out as {w0, w1} pairs with a high-half broadcast in the
+// MODE_APP instance)
+__device__ __forceinline__ f32x2 dense_weight(float w) {
+  f32x2 ww = {w, w};
+  asm volatile("" : "+v"(ww));
+  return ww;
+}
+__device__ __forceinline__ DenseCorner dense_lerp(const DenseCorner& x, const DenseCorner& y, f32x2 w0, f32x2 w1) {
+  // fma(y, w1, x * w0), spelled out (the file is built with -ffp-contract=off): every instance rounds alike, which the bit equality
+  // of the plain, folded and compact forms rests on
+  const f32x4 w0q = __builtin_shufflevector(w0, w0, 0, 1, 0, 1), w1q = __builtin_shufflevector(w1, w1, 0, 1, 0, 1);
+  DenseCorner n;
+  n.a = __builtin_elementwise_fma(y.a, w1q, x.a * w0q); n.b = __builtin_elementwise_fma(y.b, w1q, x.b * w0q);
+  n.c = __builtin_elementwise_fma(y.c, w1q, x.c * w0q); n.d = __builtin_elementwise_fma(y.d, w1, x.d * w0);
+  return n;
+}
+
+__device__ __forceinline__ void gather_app_dense(const char* __restrict__ G, uint32_t grid_off, const int32_t res[3], const VMTaps& t, int h,
+                                                 f32x16& fe) {
+  const Lin1 &Rr = t.ax[0], &Tt = t.ax[1], &Pp = t.ax[2];
+  const uint32_t nr128 = (uint32_t)res[0] * 128u, gb = grid_off + 16u * (uint32_t)h;
+  const uint32_t row00 = gb + ((uint32_t)Pp.i0 * (uint32_t)res[1] + (uint32_t)Tt.i0) * nr128;
+  const uint32_t row01 = gb + ((uint32_t)Pp.i0 * (uint32_t)res[1] + (uint32_t)Tt.i1) * nr128;
+  const uint32_t row10 = gb + ((uint32_t)Pp.i1 * (uint32_t)res[1] + (uint32_t)Tt.i0) * nr128;
+  const uint32_t row11 = gb + ((uint32_t)Pp.i1 * (uint32_t)res[1] + (uint32_t)Tt.i1) * nr128;
+  const uint32_t c0 = (uint32_t)Rr.i0 * 128u, c1 = (uint32_t)Rr.i1 * 128u;
+  const f32x2 w6[6] = {dense_weight(Rr.w0), dense_weight(Rr.w1), dense_weight(Tt.w0), dense_weight(Tt.w1), dense_weight(Pp.w0), dense_weight(Pp.w1)};
+  DenseCorner p0 = dense_corner(G, row00 + c0), p1 = dense_corner(G, row00 + c1);
+  DenseCorner q0 = dense_corner(G, row01 + c0), q1 = dense_corner(G, row01 + c1);
+  __builtin_amdgcn_sched_barrier(0);
+  const DenseCorner v00 = dense_lerp(p0, p1, w6[0], w6[1]);
+  p0 = dense_corner(G, row10 + c0); p1 = dense_corner(G, row10 + c1);
+  __builtin_amdgcn_sched_barrier(0);
+  const DenseCorner v01 = dense_lerp(q0, q1, w6[0], w6[1]);
+  q0 = dense_corner(G, row11 + c0); q1 = dense_corner(G, row11 + c1);
+  const DenseCorner u0 = dense_lerp(v00, v01, w6[2], w6[3]);
+  __builtin_amdgcn_sched_barrier(0);
+  const DenseCorner v10 = dense_lerp(p0, p1, w6[0], w6[1]);
+  const DenseCorner v11 = dense_lerp(q0, q1, w6[0], w6[1]);
+  const DenseCorner u1 = dense_lerp(v10, v11, w6[2], w6[3]);
+  const DenseCorner d = dense_lerp(u0, u1, w6[4], w6[5]);
+  fe[0] = d.a.x; fe[1] = d.a.y; fe[2] = d.a.z; fe[3] = d.a.w; fe[4] = d.b.x; fe[5] = d.b.y; fe[6] = d.b.z; fe[7] = d.b.w;
+  fe[8] = d.c.x; fe[9] = d.c.y; fe[10] = d.c.z; fe[11] = d.c.w; fe[12] = d.d.x; fe[13] = d.d.y; fe[14] = 0.f; fe[15] = 0.f;
+}
+
 // PX: arithmetic of the MLP's correction terms: 0 = fp16 (f16x3), 1 = fp8 (f16f8), 2 = fp6 (f16f6)
 // FOLD: rows H / J in the epilogue (models/EgoNeRF.py:579-598): a wave owns whole rays (S a multiple of 32, a ray = S / 32 consecutive
 // tiles), keeps sum w rgb / sum w (lane half 0) and sum w z (lane half 1) per lane across the ray's tiles and finishes the pixel -
@@ -985,9 +1047,13 @@ __device__ __forceinline__ void gather_basis_f16(const DevField& F, const VMTaps
 // COMPACT: the tiles are cut from the live-sample list (ego_shade_live) instead of the flat [N][S] order: lane j of tile t shades sample
 // live[32 t + j], reads its coordinates at that index and its direction from ray live[..] / S, and writes its colour there.  Every lane's
 // result depends on its own sample only, so the colours are the bits the tile walk writes for the same samples.
-template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false, bool COMPACT = false>
+// DAPP: the features come from the baked node grid (gather_app_dense) instead of the tables and the basis; inference without dumps
+// and with fp32 tables only (MODE_SHADE in its three forms, and MODE_APP so that the features can be checked on their own).  Then A.F
+// describes the node grid, not the tables: F.base = the grid, F.poff[g][0] = the byte offset of grid g in it, F.res = its resolution.
+template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false, bool COMPACT = false, bool DAPP = false>
 __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   constexpr bool P8 = PX == 1, P6 = PX == 2;
+  static_assert(!DAPP || (MODE != MODE_MLP && !DUMP && !TAB16), "the dense gather replaces the fp32-table gather of inference only");
   static_assert(!FOLD || (MODE == MODE_SHADE && !DUMP), "compositing folds into the fused inference kernel only");
   static_assert(!COMPACT || (MODE == MODE_SHADE && !DUMP && !FOLD), "the live-sample list is an input of the two-launch inference shade only");
   static_assert(!PX || (!DUMP && MODE != MODE_APP), "the fp8 / fp6 correction arithmetic exists for the inference MLP only");
@@ -1023,7 +1089,8 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   const int j = lane & 31, h = lane >> 5;
   // wave priority follows the phase: high while gathering (latency-bound: get the loads out), low in the MLP phase, whose MFMAs
   // fill the matrix pipe anyway - 0.9 % faster than the static priority of k_shade (no priority / static: measured, removed)
-  const int32_t n_live = COMPACT ? *A.n_live : 0;
+  // (DAPP: the count is read as a scalar, so that no vector copy of it can become a loop invariant for the MLP phase to spill)
+  const int32_t n_live = COMPACT ? (DAPP ? __builtin_amdgcn_readfirstlane(*A.n_live) : *A.n_live) : 0;
   const int64_t n_tiles = ((COMPACT ? (int64_t)n_live : A.M) + 31) >> 5;
   const u32x4* W1 = (const u32x4*)(lds + OFF_W1);
   const u32x4* W2 = (const u32x4*)(lds + OFF_W2);
@@ -1064,7 +1131,10 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
     asm volatile("" : "+v"(lw));  // keeps the LDS weight reads inside the loop (see k_shade)
     if (MODE != MODE_MLP) __builtin_amdgcn_s_setprio(2);
     const int hw = lw >> 5;
-    const int64_t m_raw = tile * 32 + j;
+    // DAPP: with the load buffer gone the gather phase leaves registers free, and the compiler fills them with lane-derived loop
+    // invariants that the MLP phase then spills; taken from the opaque copy they are recomputed per tile (two VALU) instead
+    const int jt = DAPP ? (lw & 31) : j, ht = DAPP ? hw : h;
+    const int64_t m_raw = tile * 32 + jt;
     const bool valid = m_raw < (COMPACT ? (int64_t)n_live : A.M);
     // COMPACT: the list entry (a lane past the end repeats the last live sample and writes nothing)
     const int64_t m = COMPACT ? (int64_t)A.live[valid ? m_raw : n_live - 1] : valid ? m_raw : A.M - 1;
@@ -1088,7 +1158,9 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
         const int b = g ? 3 : 0;
         a_r = p[b]; a_th = p[b + 1]; a_ph = p[b + 2];
       } else {
-        const uint32_t ray = (uint32_t)m / (uint32_t)A.S;
+        int32_t s_div = A.S;
+        if constexpr (DAPP) asm volatile("" : "+s"(s_div));   // (the reciprocal behind the division is such an invariant too)
+        const uint32_t ray = (uint32_t)m / (uint32_t)s_div;
         const float* R = A.rays + (int64_t)ray * 6;
         vd0 = R[3]; vd1 = R[4]; vd2 = R[5];
         // normalised coordinates come from ego_march_density (no acos/atan2/LUT search here)
@@ -1098,7 +1170,14 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
       const bool any_yin = __ballot(g == 0) != 0ull, any_yang = __ballot(g != 0) != 0ull;
       const bool mixed = any_yin && any_yang;
       const int gu = any_yin ? 0 : 1;
-      const VMTaps taps = vm_setup(a_r, a_th, a_ph, A.F.res);
+      VMTaps taps;
+      if constexpr (DAPP) {   // ... and the same for the three axis scales (n - 1) / 2: the resolutions go through an opaque copy
+        int32_t rs[3] = {A.F.res[0], A.F.res[1], A.F.res[2]};
+        asm volatile("" : "+s"(rs[0]), "+s"(rs[1]), "+s"(rs[2]));
+        taps = vm_setup(a_r, a_th, a_ph, rs);
+      } else {
+        taps = vm_setup(a_r, a_th, a_ph, A.F.res);
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) fe[r] = 0.f;
       // per plane: two half-stages of 18 loads (12 products each); 3 basis k-steps of 8 products.  Loads of the
@@ -1107,7 +1186,9 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
       // lw / hw (opaque copies of lane / lane half) keep the per-table base pointers from being hoisted out of the tile
       // loop, where 24 64-bit loop invariants would spill.  Waves whose 32 samples all lie in one grid (the common case)
       // take the path without per-value masking; border-straddling waves run both weight sets masked.
-      if (TAB16) {
+      if (DAPP) {
+        gather_app_dense(A.F.base, g ? A.F.poff[1][0] : A.F.poff[0][0], A.F.res, taps, hw, fe);
+      } else if (TAB16) {
         if (!mixed) {
           gather_basis_f16<false>(A.F, taps, BASH, lw, g, hw, gu, true, fe);
         } else {
@@ -1143,7 +1224,7 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
         float* o = A.out + m * APP_DIM;
 #pragma unroll
         for (int r = 0; r < NSLOT; ++r)
-          if (2 * r + h < APP_DIM) o[2 * r + h] = fe[r];
+          if (2 * r + ht < APP_DIM) o[2 * r + ht] = fe[r];
       }
       continue;
     }
@@ -1161,7 +1242,7 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
       for (int q = 0; q < 4; ++q) __builtin_nontemporal_store(f32x4{fe[4 * q], fe[4 * q + 1], fe[4 * q + 2], fe[4 * q + 3]}, &((f32x4*)A.dump_fe)[(tile * 4 + q) * 64 + lane]);
     }
     float vw[8];
-    view_slots<EncHw>(vd0, vd1, vd2, h, vw);
+    view_slots<EncHw>(vd0, vd1, vd2, ht, vw);
 
     // ---- layer 1 (10 steps of 8 values per lane half) ----------------------------------------------------------
     f32x16 H[4];
@@ -1198,19 +1279,26 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
         o0 = fmaf(hv, w3[r].x, o0); o1 = fmaf(hv, w3[r].y, o1); o2 = fmaf(hv, w3[r].z, o2);
       }
     }
-    o0 += __shfl_xor(o0, 32, 64);
-    o1 += __shfl_xor(o1, 32, 64);
-    o2 += __shfl_xor(o2, 32, 64);
+    if constexpr (DAPP) {   // __shfl_xor(v, 32, 64) with the partner's index taken from the opaque lane copy (see jt / ht)
+      const int partner = (lw ^ 32) << 2;
+      o0 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o0)));
+      o1 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o1)));
+      o2 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o2)));
+    } else {
+      o0 += __shfl_xor(o0, 32, 64);
+      o1 += __shfl_xor(o1, 32, 64);
+      o2 += __shfl_xor(o2, 32, 64);
+    }
     if (FOLD) {
       // weights are >= 0 and a tile skipped above holds only zeros (the fold is used with shade_above = 0), so nothing is conditional
       const float* b3 = lds + OFF_B3;
       const float wgt = valid ? fold_w : 0.f;
-      const float x0 = h ? fold_z : sigmoidf(o0 + b3[0]);
+      const float x0 = ht ? fold_z : sigmoidf(o0 + b3[0]);
       c0 += wgt * x0;
       c1 += wgt * sigmoidf(o1 + b3[1]);
       c2 += wgt * sigmoidf(o2 + b3[2]);
       c3 += wgt;
-    } else if (valid && h == 0) {
+    } else if (valid && ht == 0) {
       const float* b3 = lds + OFF_B3;
       float* o = A.out + m * 3;
       o[0] = sigmoidf(o0 + b3[0]);
@@ -1269,14 +1357,14 @@ ShadeArgs shade_args(const ego_scene* sc, int64_t M, int32_t S) {   // (the tabl
 }
 
 // PX = 0 f16x3, 1 f16f8, 2 f16f6 where the MLP runs for inference (MLP, SHADE, SHADE + FOLD, SHADE + COMPACT), 0 elsewhere
-template <int MODE, bool DUMP, bool FOLD, bool COMPACT, bool TAB16>
+template <int MODE, bool DUMP, bool FOLD, bool COMPACT, bool TAB16, bool DAPP = false>
 void launch_shade_h(int32_t precision, const ShadeArgs& a, hipStream_t st) {
   const unsigned grid = shade_grid(a.M);
   if constexpr (MODE != MODE_APP && !DUMP) {
-    if (precision == EGO_PREC_F16F8) return k_shade_h<MODE, DUMP, TAB16, 1, FOLD, COMPACT><<<grid, 512, 0, st>>>(a);
-    if (precision == EGO_PREC_F16F6) return k_shade_h<MODE, DUMP, TAB16, 2, FOLD, COMPACT><<<grid, 512, 0, st>>>(a);
+    if (precision == EGO_PREC_F16F8) return k_shade_h<MODE, DUMP, TAB16, 1, FOLD, COMPACT, DAPP><<<grid, 512, 0, st>>>(a);
+    if (precision == EGO_PREC_F16F6) return k_shade_h<MODE, DUMP, TAB16, 2, FOLD, COMPACT, DAPP><<<grid, 512, 0, st>>>(a);
   }
-  k_shade_h<MODE, DUMP, TAB16, 0, FOLD, COMPACT><<<grid, 512, 0, st>>>(a);
+  k_shade_h<MODE, DUMP, TAB16, 0, FOLD, COMPACT, DAPP><<<grid, 512, 0, st>>>(a);
 }
 
 // The set of shade instances: the entry point fixes MODE / DUMP / FOLD / COMPACT, the scene's mlp_precision and app_f16 pick the rest.
@@ -1292,12 +1380,28 @@ int launch_shade(const ego_scene* sc, ShadeArgs& a, const char* who, const char*
       return ego_launch_status(label);
     }
     if constexpr (MODE != MODE_MLP) {
-      if (sc->app_f16) {
+      if (sc->app_f16 == EGO_APP_HALF) {
         if (int e = check_app16(sc, who)) return e;
         a.F = make_field(sc->app16);
         launch_shade_h<MODE, DUMP, FOLD, COMPACT, true>(sc->mlp_precision, a, st);
         return ego_launch_status(label);
       }
+    }
+  }
+  if constexpr (!DUMP && MODE != MODE_MLP) {
+    if (sc->app_f16 == EGO_APP_DENSE) {   // the baked node grid (app16.plane[0][0]) instead of tables and basis
+      const float* grid = sc->app16.plane[0][0];
+      if (!grid) return ego_fail(EGO_E_BADARG, "%s: app_f16 is EGO_APP_DENSE but app16.plane[0][0] (the node grid) is null", who);
+      if (sc->app16.n_comp != APP_C || sc->app16.res[0] != sc->app.res[0] || sc->app16.res[1] != sc->app.res[1] || sc->app16.res[2] != sc->app.res[2])
+        return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must be baked from 48 components at the resolution of `app`", who);
+      const uint64_t grid_bytes = (uint64_t)sc->app.res[0] * (uint64_t)sc->app.res[1] * (uint64_t)sc->app.res[2] * 128u;
+      if (((uintptr_t)grid & 15) != 0) return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must be 16-byte aligned", who);
+      if (2 * grid_bytes >= ((uint64_t)1 << 32))
+        return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must stay under 4 GB (32-bit byte offsets)", who);
+      a.F.base = (const char*)grid;   // (see k_shade_h, DAPP)
+      a.F.poff[0][0] = 0u; a.F.poff[1][0] = (uint32_t)grid_bytes;
+      launch_shade_h<MODE, DUMP, FOLD, COMPACT, false, true>(sc->mlp_precision, a, st);
+      return ego_launch_status(label);
     }
   }
   launch_shade_h<MODE, DUMP, FOLD, COMPACT, false>(sc->mlp_precision, a, st);
@@ -1308,7 +1412,7 @@ int launch_shade(const ego_scene* sc, ShadeArgs& a, const char* who, const char*
 
 // ego_render_forward's question (csrc/ego_render.hip): can shading and compositing run as one launch for this scene and sample count?
 bool ego_can_fold_composite(const ego_scene* sc, int32_t S) {
-  return sc && ego_shape_is_tuned(sc) && !sc->app_f16 && sc->mlp_precision != EGO_PREC_F32 && sc->weight_thres <= 0.f && S >= 32 && (S & 31) == 0;
+  return sc && ego_shape_is_tuned(sc) && sc->app_f16 != EGO_APP_HALF && sc->mlp_precision != EGO_PREC_F32 && sc->weight_thres <= 0.f && S >= 32 && (S & 31) == 0;
 }
 
 // ... and does it pay?  The folded kernel deals whole RAYS to its waves (a wave finishes its rays' pixels itself), the two-launch kernel

@@ -343,7 +343,7 @@ class YinYangAlphaGridMask(torch.nn.Module):
 class _SceneEntry:
     """EgoNeRF's one cached ego_scene struct, with everything the struct points to that nobody else keeps alive."""
 
-    def __init__(self, blobs=None, app16=None, dense=None):
+    def __init__(self, blobs=None, app16=None, dense=None, app_dense=None):
         self.key = None      # EgoNeRF._scene_key() the struct was built for; None: nothing cached
         self.struct = None
         self.holds = ()      # detached MLP / basis weights behind mlp_w, mlp_b, basis
@@ -353,6 +353,12 @@ class _SceneEntry:
         self.app16 = app16   # (appearance table versions, [12 half tables]) behind app16; outlives an invalidation
         # {"full" / "coarse": (table versions, baked node grid)} behind density_dense / density_coarse_dense; outlives an invalidation
         self.dense = dense
+        # (versions of the twelve appearance tables and both basis matrices, baked feature grid) behind app_dense; outlives an invalidation
+        self.app_dense = app_dense
+
+    def successor(self) -> "_SceneEntry":
+        """An empty entry that keeps what outlives an invalidation."""
+        return _SceneEntry(self.blobs, self.app16, self.dense, self.app_dense)
 
 
 class EgoNeRF(TensorBase):
@@ -388,6 +394,12 @@ class EgoNeRF(TensorBase):
         # field adds an eighth).  Part of the scene key.  EGO_DENSE_DENSITY=0|1 in the environment overrides the attribute; the grid is
         # baked only while it fits EGO_DENSE_DENSITY_MAX_MB (default 1024) and a quarter of the free device memory - see _fill_dense.
         self.dense_density = True
+        # ... and shades from the baked node grid of its 27 appearance features (csrc/ego_dense.hip): 8 taps of one 128-byte
+        # node per sample instead of 18 table taps and the basis product, for 2 x N_r N_theta N_phi x 128 B of device memory (3.41 GB at
+        # [150, 172, 516]).  Part of the scene key.  EGO_DENSE_APP=0|1 in the environment overrides the attribute; the grid is baked only
+        # for fp32 appearance tables and a split arithmetic, while it fits EGO_DENSE_APP_MAX_MB (default 4096), a quarter of the free
+        # device memory and 32-bit byte offsets - see _fill_app_dense.
+        self.dense_appearance = True
         self._coarse_epoch = 0   # counts update_coarse_sigma_grid() calls: the pooled tables are rewritten behind torch's version counters
         # opt-in skipping (EgoNeRF.forward itself evaluates every sample; TensorBase.forward's semantics, tensorBase.py:464-487,
         # pinned to the reference by tests/golden/skip_semantics.npz; see include/egonerf_hip.h):
@@ -627,10 +639,10 @@ class EgoNeRF(TensorBase):
         field_tables.fill_pointers(f, field_tables.tables(self, kind, coarse) if tensors is None else tensors)
 
     def invalidate_scene(self, moved: bool = False) -> None:
-        """The next scene() call builds the struct anew.  The per-mode packed blobs, the half tables and the baked density grids stay (an
+        """The next scene() call builds the struct anew.  The per-mode packed blobs, the half tables and the baked density / appearance grids stay (an
         earlier struct or a captured graph may point into them; reused while device, size and table versions stand) unless the whole
         model `moved` (Module._apply)."""
-        self._scene = _SceneEntry() if moved else _SceneEntry(self._scene.blobs, self._scene.app16, self._scene.dense)
+        self._scene = _SceneEntry() if moved else self._scene.successor()
 
     def packed_blob(self, training: bool = False) -> Optional[torch.Tensor]:
         """The packed MLP / basis image of a mode as of the last scene(training) call (None before the first)."""
@@ -647,6 +659,33 @@ class EgoNeRF(TensorBase):
         env = os.environ.get("EGO_DENSE_DENSITY", "")
         on = bool(self.dense_density) if env == "" else env != "0"
         return on and tuple(self.density_n_comp) == (16, 16, 16) and self.is_tuned_shape
+
+    def _app_dense_wanted(self) -> bool:
+        """The dense appearance route is asked for (attribute, EGO_DENSE_APP) and the model and its settings are ones it serves: the
+        tuned shape, fp32 appearance tables and a split arithmetic (the fp32-MFMA kernel and the half tables keep the factored gather)."""
+        env = os.environ.get("EGO_DENSE_APP", "")
+        on = bool(self.dense_appearance) if env == "" else env != "0"
+        return on and self.is_tuned_shape and self._app_table_dtype == "f32" and self._mlp_precision != "f32"
+
+    def _app_dense_versions(self) -> tuple:
+        """What the baked feature grid is a function of: the (address, version) pairs of the twelve appearance tables and of both
+        basis matrices."""
+        src = field_tables.tables(self, "app") + [self.basis_mat_yin.weight, self.basis_mat_yang.weight]
+        return tuple((t.data_ptr(), t._version) for t in src)
+
+    @staticmethod
+    def _app_dense_cap_bytes() -> float:
+        raw = os.environ.get("EGO_DENSE_APP_MAX_MB", "")
+        try:
+            return float(raw or 4096) * 2 ** 20
+        except ValueError:
+            raise ValueError(f"EGO_DENSE_APP_MAX_MB must be a number of megabytes, not {raw!r}") from None
+
+    @staticmethod
+    def _app_dense_fits(nbytes: int, cap: float, fresh: int, free: int) -> bool:
+        """The size gates of the dense appearance route: the grid within the cap and under the 4 GiB that 32-bit byte offsets address,
+        and what has to be allocated for it (`fresh`; 0 when a buffer of that size is held) within a quarter of the free device memory."""
+        return nbytes <= cap and nbytes < 2 ** 32 and (not fresh or fresh <= free // 4)
 
     def _dense_versions(self, coarse: bool) -> tuple:
         """What a baked node grid is a function of: the (address, version) pairs of the field's 12 tables.  The pooled tables are also
@@ -677,12 +716,15 @@ class EgoNeRF(TensorBase):
             has_coarse = self.coarse_sigma_plane_yin[0] is not None
             dense = (os.environ.get("EGO_DENSE_DENSITY_MAX_MB", ""), self._dense_versions(False),
                      self._dense_versions(True) if has_coarse else None)
+        app_dense = ()
+        if not training and self._app_dense_wanted():
+            app_dense = (os.environ.get("EGO_DENSE_APP_MAX_MB", ""), self._app_dense_versions())
         return (tuple(p.data_ptr() for p in self.parameters()), tuple((t.data_ptr(), t._version) for t in copied),
                 None if self.envmap is None else self.envmap.emission.data_ptr(), self.use_alpha_mask, id(self.alphaMask),
                 float(self.early_termination_eps), float(self.rayMarch_weight_thres) if self.use_weight_thres else None,
                 bool(self.skip_zero_weight_tiles), co.N_r, float(co.r0), float(co.far[0]), tuple(co.center.tolist()),
                 tuple(t.data_ptr() for t in self._luts(self.density_plane_yin[0].device)), float(self.distance_scale),
-                float(self.density_shift), self.fea2denseAct, self._mlp_precision, self._app_table_dtype, bool(training), dense)
+                float(self.density_shift), self.fea2denseAct, self._mlp_precision, self._app_table_dtype, bool(training), dense, app_dense)
 
     @_lib.device_guard
     def scene(self, training: bool = False) -> "_lib.Scene":
@@ -703,7 +745,9 @@ class EgoNeRF(TensorBase):
         a density table changed in place or the pooled tables were refreshed; a holder of an older struct, or a captured graph that
         embeds one, marches the field as last baked until scene() is called again (the bake rewrites the SAME buffers, so that call is
         all it takes).  The buffers stay allocated until the model moves or the grid changes size (_fill_dense), whatever struct is
-        cached meanwhile.  A training struct never carries them.  A holder that needs a frozen snapshot must copy the tables; re-allocation (another shape / device,
+        cached meanwhile.  A training struct never carries them.  The baked grid of the appearance features (`dense_appearance`: app_dense,
+        which the inference shade kernels then read INSTEAD of the appearance tables and the basis) follows the same rules, keyed by the twelve
+        appearance tables and both basis_mat weights (_fill_app_dense).  A holder that needs a frozen snapshot must copy the tables; re-allocation (another shape / device,
         tables assigned one by one) invalidates the cached struct and the next scene() call builds a new one.  One struct is cached
         (not one per mode), together with everything it points to that nobody else keeps alive (_SceneEntry)."""
         dev = self.density_plane_yin[0].device
@@ -719,7 +763,7 @@ class EgoNeRF(TensorBase):
         for kind in ("density", "app"):
             if not field_tables.is_compact(field_tables.tables(self, kind)):
                 field_tables.recarve(self, kind, keep_parameters=True)
-        entry = _SceneEntry(self._scene.blobs, self._scene.app16, self._scene.dense)
+        entry = self._scene.successor()
         sc = entry.struct = _lib.new_scene()
         entry.luts = self._luts(dev)
         self.coordinates.fill_scene(sc, dev)
@@ -735,6 +779,8 @@ class EgoNeRF(TensorBase):
             self._fill_app16(sc, entry)
         if not training and self._dense_wanted():
             self._fill_dense(sc, entry, dev)   # (otherwise the pointers stay NULL; grids baked earlier stay allocated, see _fill_dense)
+        if not training and self._app_dense_wanted():
+            self._fill_app_dense(sc, entry, dev)
         entry.mask = self.alphaMask
         if self.use_alpha_mask and self.alphaMask is not None:
             self.alphaMask.fill_scene(sc)
@@ -787,7 +833,7 @@ class EgoNeRF(TensorBase):
                 hv.copy_(t.detach())
             entry.app16 = (ver, halves)
         self._fill_field(sc.app16, "app", tensors=entry.app16[1])
-        sc.app_f16 = 1
+        sc.app_f16 = _lib.APP_HALF
 
     def _fill_dense(self, sc, entry, dev):
         """The baked node grids behind density_dense / density_coarse_dense (ego_bake_density_dense), decided once per scene build:
@@ -826,6 +872,47 @@ class EgoNeRF(TensorBase):
         sc.density_dense = dense["full"][1].data_ptr()
         if has_coarse:
             sc.density_coarse_dense = dense["coarse"][1].data_ptr()
+
+    def _fill_app_dense(self, sc, entry, dev):
+        """The baked node grid of the appearance features behind app_dense (ego_bake_app_dense), decided once per scene build by
+        _fill_dense's rules: baked while the grid fits EGO_DENSE_APP_MAX_MB (default 4096), 32-bit byte offsets and - where it has to
+        be allocated - a quarter of the free device memory; otherwise the pointer stays NULL and the shade gathers from the tables.
+        The grid is kept across rebuilds and baked again, IN PLACE, when an appearance table or a basis matrix changed; it stays allocated
+        until the model moves or the grid changes size, because an inference struct handed out earlier, or a captured graph, may still
+        point into it.  `last_app_bake_ms` records the time of the latest bake (None before the first)."""
+        res = [int(v) for v in self.gridSize.tolist()]
+        nbytes = 2 * 128 * res[0] * res[1] * res[2]
+        h = entry.app_dense
+        held = h is not None and h[1].device == dev and h[1].numel() * 4 == nbytes
+        fresh = 0 if held else nbytes
+        if not self._app_dense_fits(nbytes, self._app_dense_cap_bytes(), fresh, torch.cuda.mem_get_info(dev)[0] if fresh else 0):
+            return   # pointer stays NULL; what is held stays held
+        if not held:
+            h = (None, torch.empty(nbytes // 4, device=dev))
+        ver = self._app_dense_versions()
+        if h[0] != ver:
+            f = _lib.VmField()
+            self._fill_field(f, "app")
+            timed = not torch.cuda.is_current_stream_capturing()
+            if timed:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+            _call("ego_bake_app_dense", C.byref(f), sc.basis[0], sc.basis[1], int(self.app_dim), h[1].data_ptr(), _lib.stream_handle())
+            if timed:
+                t1.record()
+                self._app_bake_events = (t0, t1)
+            h = (ver, h[1])
+        entry.app_dense = h
+        sc.app_dense = h[1].data_ptr()
+
+    @property
+    def last_app_bake_ms(self) -> Optional[float]:
+        """Device time of the latest bake of the dense appearance grid in ms (waits for it), or None if none was timed."""
+        ev = getattr(self, "_app_bake_events", None)
+        if ev is None:
+            return None
+        ev[1].synchronize()
+        return float(ev[0].elapsed_time(ev[1]))
 
     # -- stage methods (reference public API) ----------------------------------------------------------------
     def _sched(self, n_samples: int, device) -> torch.Tensor:

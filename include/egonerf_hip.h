@@ -123,9 +123,21 @@ typedef struct ego_scene {
   /* Optional half-precision copy of the appearance tables (inference only): same shapes/layout as `app`, elements are
    * IEEE binary16 (the pointer type is nominal).  app_f16 != 0 makes ego_shade / ego_app_feature gather from it
    * (halves the bytes through the vector L1; interpolation and everything after stay fp32).  Measured effect on RGB in
-   * DESIGN.md. */
+   * DESIGN.md.
+   * app_f16 selects the source of the appearance features in inference: EGO_APP_TABLES (0) = the fp32 tables `app`; EGO_APP_HALF (1) =
+   * the half tables in app16, as above; EGO_APP_DENSE (2) = the baked node grid of the features (no struct member was added for it, so
+   * sizes and offsets stand and EGO_ABI_VERSION stays 17): app16.plane[0][0] then points to what ego_bake_app_dense wrote for `app` and
+   * `basis` (128 bytes per node, 16-byte aligned, both grids under 4 GB together; the pointer type is nominal), app16.res holds the
+   * resolution it was baked at, which must equal app.res, app16.n_comp is 48 and the other eleven pointers of app16 are not read.  The
+   * split-arithmetic inference kernels behind ego_shade (without dumps), ego_shade_composite, ego_shade_live and ego_app_feature then
+   * interpolate the 27 features from the grid (8 taps of one node each per sample) instead of gathering the 18 table taps and
+   * multiplying by the basis; EGO_PREC_F32 and every dumping (training) call keep the fp32 tables.  The grid is a SNAPSHOT of the tables
+   * and of both basis matrices, like `packed`: bake again after either changed. */
   ego_vm_field app16;
   int32_t app_f16;
+#define EGO_APP_TABLES 0
+#define EGO_APP_HALF 1
+#define EGO_APP_DENSE 2
   /* Radius LUT of the fine pass after resampling, when it differs from r_lut: with the plain exponential grid
    * (interval_th = False, coordinates.py:132-155) the first pass normalises r on the `downsample=2` grid (EgoNeRF.py:524) and
    * the fine pass on the full one (EgoNeRF.py:546).  NULL / 0: the fine pass uses r_lut. */
@@ -431,6 +443,19 @@ int ego_march_density(const ego_scene* sc, const float* rays, int64_t N, int32_t
  * line interpolate on one lattice along independent axes.  One thread per voxel; the sum over c runs in ascending order as one chain of
  * fused multiply-adds from 0 (acc = fma(plane_c, line_c, acc), float32), so a bake is a pure function of the tables. */
 int ego_bake_density_dense(const ego_vm_field* f, float* out, void* stream);
+
+/* The node grid behind ego_scene.app_f16 = EGO_APP_DENSE (csrc/ego_dense.hip; append-only addition, EGO_ABI_VERSION stays 17; no reference
+ * counterpart).  The appearance feature of EgoNeRF.compute_appfeature (models/EgoNeRF.py:349-413) is basis_g . concat_i(bilerp(plane_i)
+ * * lerp(line_i)); plane and line interpolate on one lattice along independent axes and the basis is linear, so it is the trilinear
+ * interpolation of F[g][phi][theta][r][27] = basis_g . concat_i(plane_i[node] * line_i[node]), zero padding included.
+ * f: the 48-component appearance field; basis_yin / basis_yang: the two [27][144] row-major basis matrices (ego_scene.basis); app_dim
+ * must be 27.  out (dev, 16-byte aligned, 2 * N_r * N_theta * N_phi * 128 bytes < 4 GB): [grid][N_phi][N_theta][N_r][8 quads][4] float32, r
+ * fastest.  A node's 128 bytes: quad 2 q + h holds slots 4 q .. 4 q + 3 of lane half h, and slot s of half h is feature 2 s + h (14 + 13
+ * features); i.e. feature f sits at float (2 ((f >> 1) >> 2) + (f & 1)) * 4 + ((f >> 1) & 3) of its node.  The five floats that hold no
+ * feature are exactly 0.  Arithmetic: the 144 products plane * line are exact in float64; each feature is one chain of 144 float64 fused
+ * multiply-adds acc = fma(basis[f][k], product_k, acc) from 0 in the order k = 48 i + c, rounded to float32 once.  Refused before any
+ * launch: n_comp != 48, app_dim != 27 (EGO_E_UNSUPPORTED); a grid of 4 GB or more, an out that is not 16-byte aligned (EGO_E_BADARG). */
+int ego_bake_app_dense(const ego_vm_field* f, const float* basis_yin, const float* basis_yang, int32_t app_dim, float* out, void* stream);
 
 /* Per-sample activations the training forward keeps for the backward pass (all dev).  Logical matrices x [M][160] (layer-1
  * inputs), h1, h2 [M][128] (post-ReLU hidden activations), v [M][144] (plane x line products); element kk of lane half h

@@ -119,6 +119,15 @@ def pair_changed_signatures(old: dict, new: dict) -> None:
         o = lone.get(_without_parameters(n))
         if o is not None:
             old[n] = old.pop(o)
+    # ... and a kernel template that gained trailing arguments which default to false / 0 (a new switch, off in every instance that
+    # existed before): `k<1, true, false>` is the successor of `k<1, true>`
+    lone = {_without_parameters(n): n for n in old if n not in new}
+    for n in [n for n in new if n not in old]:
+        head = _without_parameters(n)
+        while re.search(r", (false|0)>$", head) and head not in lone:
+            head = re.sub(r", (false|0)>$", ">", head)
+        if head in lone:
+            old[n] = old.pop(lone.pop(head))
 
 
 def main() -> int:

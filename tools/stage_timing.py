@@ -1,5 +1,7 @@
 """Times the phases of the shade kernel in isolation at the bench size (M = 4096 x 512 samples):
-gather+basis only (ego_app_feature), MLP only (ego_mlp_fea), and the fused kernel (ego_shade)."""
+gather+basis only (ego_app_feature), MLP only (ego_mlp_fea), and the fused kernel (ego_shade).
+The appearance front end is the scene's: the dense gather from the baked feature grid by default (the record says `app_dense`),
+the table gather + basis product with EGO_DENSE_APP=0 in the environment."""
 import sys, os, json
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,7 +40,7 @@ def timeit(fn, reps=10):
     torch.cuda.synchronize()
     return float(np.mean([ev[i].elapsed_time(ev[i + 1]) for i in range(reps)]))
 
-res = dict(precision=prec)
+res = dict(precision=prec, app_dense=bool(sc.app_dense), app_bake_ms=model.last_app_bake_ms)
 res["app_only_ms"] = timeit(lambda: _lib.check(lib.ego_app_feature(sc, c7.data_ptr(), M, feat.data_ptr(), st), "app"))
 res["mlp_only_ms"] = timeit(lambda: _lib.check(lib.ego_mlp_fea(sc, vd.data_ptr(), feat.data_ptr(), M, rgb.data_ptr(), st), "mlp"))
 res["shade_ms"] = timeit(lambda: _lib.check(lib.ego_shade(sc, rays.data_ptr(), z.data_ptr(), crd.data_ptr(), N, S, rgb.data_ptr(), None, None, st), "shade"))
