@@ -1,7 +1,9 @@
 // Training-step table ops of the EgoNeRF path that sit next to the render (train.py:245-330): the TV / L1 / ortho
-// regularisers with their gradients fused into the same pass, the ray-entropy loss, the distortion regulariser (per ray, through
-// alpha like the entropy), coarse-to-fine table resampling and a multi-tensor Adam.  All tables are channel-last ([H][W][C] fp32),
+// regularisers with their gradients fused into the same pass, the ray-entropy loss, the distortion regulariser and the depth term (per
+// ray, through alpha like the entropy), coarse-to-fine table resampling and a multi-tensor Adam.  All tables are channel-last ([H][W][C] fp32),
 // all kernels are HBM-bound streaming passes.
+#include <stddef.h>
+
 #include "ego_device.h"
 #include "ego_host.h"
 
@@ -195,6 +197,25 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// One 64-sample pass of the recurrence R_{i-1} = A_i R_i + B_i (A = 1 - alpha + 1e-10, B = G alpha; 1 and 0 beyond the ray's end), passes
+// taken from the ray's end: -> R_i of this lane's sample; cR carries R at the pass's last sample in and R in front of its first one out.
+__device__ __forceinline__ float recurrence_pass(float A, float B, float& cR, int lane) {
+  // lane i: the map R_i -> R_{i-1}; after the scan the composition of the maps of lanes i .. 63
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float Ao = __shfl_down(A, d, 64), Bo = __shfl_down(B, d, 64);
+    if (lane + d < 64) {
+      B = fmaf(A, Bo, B);
+      A *= Ao;
+    }
+  }
+  const float R_before = fmaf(A, cR, B);   // R_{i-1}
+  float R = __shfl_down(R_before, 1, 64);
+  if (lane == 63) R = cR;
+  cR = __shfl(R_before, 0, 64);
+  return R;
+}
+
 // One ray by one wave (all 64 lanes run every scan) -> the ray's term of the value; with g_row, the ray's gradient row is written.
 __device__ __forceinline__ double dist_ray(const float* __restrict__ a_row, const float* __restrict__ z_row, float* __restrict__ g_row, int64_t N,
                                            int S, int stride, const DistMap& map, int lane) {
@@ -239,20 +260,7 @@ __device__ __forceinline__ double dist_ray(const float* __restrict__ a_row, cons
     cGeW = __shfl(geW, 0, 64);
     cGeWM = __shfl(geWM, 0, 64);
     const float G = (float)G64;
-    // lane i: the map R_i -> R_{i-1}; after the scan the composition of the maps of lanes i .. 63
-    float A = s.f, B = G * s.a;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float Ao = __shfl_down(A, d, 64), Bo = __shfl_down(B, d, 64);
-      if (lane + d < 64) {
-        B = fmaf(A, Bo, B);
-        A *= Ao;
-      }
-    }
-    const float R_before = fmaf(A, cR, B);   // R_{i-1}
-    float R = __shfl_down(R_before, 1, 64);
-    if (lane == 63) R = cR;
-    cR = __shfl(R_before, 0, 64);
+    const float R = recurrence_pass(s.f, G * s.a, cR, lane);
     if (i < S) g_row[i] = T * (G - R) * (float)invN;
   }
   for (int c = S + lane; c < stride; c += 64) g_row[c] = 0.f;
@@ -273,6 +281,115 @@ __global__ __launch_bounds__(256) void k_ray_distortion(const float* __restrict_
   if (lane == 0) terms[wave] = term;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(value, (terms[0] + terms[1]) + (terms[2] + terms[3]));
+}
+
+// ---- Depth supervision (train.py:249-251, :275-283: a masked MSE between depth_map and a per-ray target, rays with target 0 left out) ----
+// The reference computes depth_map under no_grad (EgoNeRF.py:595-598), so its term has no gradient; this is the term that loop means.
+// The render's depth output stays non-differentiable: the loss enters through alpha, like the entropy and the distortion terms.  With
+// the render's weights w_i = alpha_i T_i, T_i = prod_{j<i} f_j, f_j = 1 - alpha_j + 1e-10, the mapped distances q_i = s(z_i) and the
+// mapped tail q_t = s(tail) (0 without one):
+//   D       = sum_i w_i q_i + (1 - sum_i w_i) q_t                   (both sums in float64; w q is exact there)
+//   G_i     = dD / dw_i = q_i - q_t
+//   R_{S-1} = 0, R_i = G_{i+1} alpha_{i+1} + f_{i+1} R_{i+1}        (the distortion kernel's recurrence: no division)
+//   dD / dalpha_i = T_i (G_i - R_i)
+// A ray is valid iff its target is finite and > 0; V = the number of valid rays, r = D - s(target):
+//   l2: loss = (1 / V) sum_valid r^2,  g_alpha_i = (2 r / V) dD / dalpha_i        l1: |r| and sign(r) (0 at r = 0) in their places
+// An invalid ray adds nothing and its gradient row is 0; with V = 0 the value and every gradient element are 0.
+//
+// Three launches, no host synchronisation: k_depth_count leaves V in the workspace; k_ray_depth_loss (one wave per ray, four rays per
+// block, 64 samples per pass like k_ray_distortion) writes pred = D, the ray's r^2 or |r| into the workspace and the gradient row:
+// the forward sweep keeps per-lane float64 partial sums over the passes and parks T_i in g_alpha[i], the reverse sweep runs the affine
+// scan for R and overwrites it; k_depth_reduce sums the rays' terms in a fixed order and divides by V.  r^2 reaches far^2, so the
+// distortion kernel's rounding to multiples of 2^-51 (sums below 4) does not carry over: the order is fixed instead, and value-only,
+// gradient-only, joint and repeated calls return the same bits.
+__device__ __forceinline__ float depth_map(float z, const DistMap& g) { return g.space == EGO_DIST_METRIC ? z : dist_map(z, g); }
+
+__device__ __forceinline__ bool depth_valid(float t) { return t > 0.f && t < INFINITY; }   // false for NaN
+
+struct DepthWorkspace {
+  unsigned long long valid;   // V
+  unsigned long long pad;
+  double term[1];             // [N]: r^2 or |r| of a valid ray, 0 of an invalid one
+};
+
+__global__ __launch_bounds__(1024) void k_depth_count(const float* __restrict__ target, int64_t N, DepthWorkspace* __restrict__ ws) {
+  __shared__ unsigned long long total;
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  unsigned long long c = 0;
+  for (int64_t i = threadIdx.x; i < N; i += 1024) c += depth_valid(target[i]) ? 1u : 0u;
+  atomicAdd(&total, c);   // integers: any order gives the same sum
+  __syncthreads();
+  if (threadIdx.x == 0) ws->valid = total;
+}
+
+__global__ __launch_bounds__(256) void k_ray_depth_loss(const float* __restrict__ alpha, int stride, const float* __restrict__ z,
+                                                        const float* __restrict__ target, const float* __restrict__ tail, int64_t N, int S,
+                                                        DistMap map, int kind, DepthWorkspace* __restrict__ ws, float* __restrict__ g_alpha,
+                                                        float* __restrict__ pred) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ray >= N) return;   // wave-uniform
+  const float* a_row = alpha + ray * stride;
+  const float* z_row = z + ray * S;
+  float* g_row = g_alpha ? g_alpha + ray * stride : nullptr;
+  const float q_t = tail ? depth_map(tail[ray], map) : 0.f;
+  const float tgt = target ? target[ray] : 0.f;
+  const bool valid = depth_valid(tgt);
+  const bool want_row = g_row && valid;   // an invalid ray's row is zeros: T need not be parked
+  const int passes = (S + 63) >> 6;
+
+  float cT = 1.f;   // carry: T at the pass's first sample
+  double sw = 0.0, swq = 0.0;   // this lane's share of sum w, sum w q
+  for (int p = 0; p < passes; ++p) {
+    const int i = p * 64 + lane;
+    const float a = i < S ? a_row[i] : 0.f;
+    const float f = __fadd_rn(__fsub_rn(1.f, a), 1e-10f);
+    const float q = i < S ? depth_map(z_row[i], map) : 0.f;
+    const float prod = wave_scan_mul(f, lane);
+    float before = __shfl_up(prod, 1, 64);
+    if (lane == 0) before = 1.f;
+    const float T = cT * before;
+    cT *= __shfl(prod, 63, 64);
+    const double w = (double)(a * T);
+    sw += w;
+    swq += w * (double)q;
+    if (want_row && i < S) g_row[i] = T;
+  }
+  const double D = wave_sum_f64(swq) + (1.0 - wave_sum_f64(sw)) * (double)q_t;
+  if (pred && lane == 0) pred[ray] = (float)D;
+  if (!ws) return;   // pred only
+
+  const double r = valid ? D - (double)depth_map(tgt, map) : 0.0;
+  if (lane == 0) ws->term[ray] = kind == EGO_DEPTH_L2 ? r * r : fabs(r);
+  if (!g_row) return;
+  // d loss / d D; V >= 1 where a ray is valid
+  const float scale = !valid ? 0.f : (float)((kind == EGO_DEPTH_L2 ? 2.0 * r : (double)((r > 0.0) - (r < 0.0))) / (double)ws->valid);
+  if (scale == 0.f) {   // invalid, or r = 0: exactly 0
+    for (int c = lane; c < stride; c += 64) g_row[c] = 0.f;
+    return;
+  }
+  float cR = 0.f;   // carry: R at the pass's last sample
+  for (int p = passes - 1; p >= 0; --p) {
+    const int i = p * 64 + lane;
+    const bool in = i < S;
+    const float a = in ? a_row[i] : 0.f;
+    const float f = __fadd_rn(__fsub_rn(1.f, a), 1e-10f);
+    const float G = in ? depth_map(z_row[i], map) - q_t : 0.f;
+    const float T = in ? g_row[i] : 0.f;
+    const float R = recurrence_pass(f, G * a, cR, lane);
+    if (in) g_row[i] = T * (G - R) * scale;
+  }
+  for (int c = S + lane; c < stride; c += 64) g_row[c] = 0.f;
+}
+
+// value += (1 / V) sum_rays term, the rays in a fixed order: thread t takes rays t, t + 256, ..., then block_sum_256's tree
+__global__ __launch_bounds__(256) void k_depth_reduce(const DepthWorkspace* __restrict__ ws, int64_t N, double* __restrict__ value) {
+  __shared__ double red[256];
+  double part = 0.0;
+  for (int64_t i = threadIdx.x; i < N; i += 256) part += ws->term[i];
+  const double tot = block_sum_256(part, red);
+  if (threadIdx.x == 0 && ws->valid > 0) *value += tot / (double)ws->valid;
 }
 
 // coordinates.py:27-39 / :226-266: bilinear (align_corners, zero padding) resample of a channel-last table at per-axis
@@ -400,6 +517,44 @@ int ego_ray_distortion(const float* alpha, int32_t alpha_stride, const float* z,
   const DistMap map{space, near_, (float)(1.0 / span)};
   k_ray_distortion<<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(alpha, alpha_stride, z, N, S, map, value, g_alpha);
   return ego_launch_status("k_ray_distortion");
+}
+
+int64_t ego_ray_depth_loss_workspace_bytes(int64_t N) { return N < 0 ? -1 : (int64_t)offsetof(DepthWorkspace, term) + N * (int64_t)sizeof(double); }
+
+int ego_ray_depth_loss(const float* alpha, int32_t alpha_stride, const float* z, const float* target, const float* tail, int64_t N, int32_t S,
+                       float near_, float far_, int32_t space, int32_t kind, void* workspace, double* value, float* g_alpha, float* pred,
+                       void* stream) {
+  EGO_TRACE("ego_ray_depth_loss");
+  EGO_REQUIRE(N >= 0 && (N + 3) / 4 <= INT32_MAX && S >= 2 && (alpha_stride == S || alpha_stride == S + 1),
+              "ray_depth_loss: bad size (S >= 2, alpha_stride = S or S + 1)");
+  EGO_REQUIRE(space == EGO_DIST_METRIC || space == EGO_DIST_LOG || space == EGO_DIST_DISPARITY,
+              "ray_depth_loss: unknown space (metric, log or disparity)");
+  EGO_REQUIRE(kind == EGO_DEPTH_L2 || kind == EGO_DEPTH_L1, "ray_depth_loss: unknown kind (l2 or l1)");
+  EGO_REQUIRE(space == EGO_DIST_METRIC || (far_ > near_ && far_ < INFINITY && near_ > 0.f),
+              "ray_depth_loss: the log and disparity spaces need finite 0 < near < far");
+  if (N == 0) return EGO_OK;
+  EGO_REQUIRE(alpha && z && (value || g_alpha || pred), "ray_depth_loss: null argument");
+  const bool loss = value || g_alpha;
+  EGO_REQUIRE(!loss || (target && workspace), "ray_depth_loss: a value or a gradient needs target and workspace (null)");
+  EGO_REQUIRE(((uintptr_t)workspace & 7) == 0, "ray_depth_loss: the workspace must be 8-byte aligned");
+  DistMap map{space, 1.f, 1.f};
+  if (space != EGO_DIST_METRIC) {
+    const double n = (double)near_, f = (double)far_;
+    map = DistMap{space, near_, (float)(1.0 / (space == EGO_DIST_LOG ? log(f / n) : 1.0 / n - 1.0 / f))};
+  }
+  DepthWorkspace* ws = loss ? (DepthWorkspace*)workspace : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (ws) {
+    k_depth_count<<<1, 1024, 0, st>>>(target, N, ws);
+    if (int e = ego_launch_status("k_depth_count")) return e;
+  }
+  k_ray_depth_loss<<<(unsigned)((N + 3) / 4), 256, 0, st>>>(alpha, alpha_stride, z, target, tail, N, S, map, kind, ws, g_alpha, pred);
+  if (int e = ego_launch_status("k_ray_depth_loss")) return e;
+  if (value) {
+    k_depth_reduce<<<1, 256, 0, st>>>(ws, N, value);
+    return ego_launch_status("k_depth_reduce");
+  }
+  return EGO_OK;
 }
 
 int ego_resample_table(const float* src, int32_t C, int32_t H, int32_t W, const float* xs, const float* ys, int32_t H2, int32_t W2,

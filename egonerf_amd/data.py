@@ -31,9 +31,15 @@ class RayBank:
     of the window's pixels, i.e. the rows of the per-image `all_rgbs` that belong to the rays (`all_rgbs` itself keeps every pixel
     of the image, as the reference's does).
 
+    depths (optional) [K,H,W] float32 or float16 (array or tensor): one depth target per pixel of the full images, in units of distance
+    along the normalised ray, 0 = no target (losses.depth_loss leaves such a ray out).  Kept on the device in its own dtype;
+    `gather_depth(idx)` returns the targets of ray indices as float32.  The reference defines no depth file format (its loaders never
+    fill all_depth, dataset_interface.py:41), so reading one is the caller's business.
+
     A bank on device="cpu" holds the host state only (shapes, window, struct): gather / sampling need the HIP device."""
 
-    def __init__(self, poses, images_u8, img_wh: Sequence[int], roi: Sequence[float] = (0, 1, 0, 1), normalize: bool = True, device="cuda"):
+    def __init__(self, poses, images_u8, img_wh: Sequence[int], roi: Sequence[float] = (0, 1, 0, 1), normalize: bool = True, device="cuda",
+                 depths=None):
         W, H = int(img_wh[0]), int(img_wh[1])
         poses = torch.as_tensor(np.asarray(poses) if not torch.is_tensor(poses) else poses).float()
         if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
@@ -53,6 +59,12 @@ class RayBank:
         self.device = torch.device(device)
         self.poses = poses[:, :3, :].contiguous().to(self.device)
         self.images = img.contiguous().to(self.device)
+        self.depths = None
+        if depths is not None:
+            d = depths if torch.is_tensor(depths) else torch.from_numpy(np.ascontiguousarray(depths))
+            if d.dtype not in (torch.float32, torch.float16) or tuple(d.shape) != (K, H, W):
+                raise ValueError(f"RayBank: depths must be float32 or float16 [K,H,W] = {(K, H, W)}, got {d.dtype} {tuple(d.shape)}")
+            self.depths = d.detach().contiguous().to(self.device)
         self.K, self.H, self.W = K, H, W
         self.r0, self.n_rows, self.c0, self.n_cols = r0, r1 - r0, c0, c1 - c0
         self.roi, self.normalize = list(roi), bool(normalize)
@@ -62,8 +74,9 @@ class RayBank:
 
     @property
     def nbytes(self) -> int:
-        """Bytes the bank holds (on its device): K * H * W * 4 for the images + K * 48 for the poses."""
-        return self.images.numel() * self.images.element_size() + self.poses.numel() * self.poses.element_size()
+        """Bytes the bank holds (on its device): K * H * W * 4 for the images + K * 48 for the poses (+ K * H * W * 4 or 2 for depths)."""
+        depth = 0 if self.depths is None else self.depths.numel() * self.depths.element_size()
+        return self.images.numel() * self.images.element_size() + self.poses.numel() * self.poses.element_size() + depth
 
     def __len__(self) -> int:
         return self.total
@@ -80,6 +93,25 @@ class RayBank:
         rgb = torch.empty(idx.shape[0], 3, device=self.device, dtype=torch.float32)
         ray_batch_gather(idx, rays, rgb, self)
         return rays, rgb
+
+    def gather_depth(self, idx: torch.Tensor) -> torch.Tensor:
+        """[B] float32: the depth targets of ray indices, bit-equal to indexing the `depths` array at the rays' pixels.  idx as in
+        `gather`; an index outside [0, total) gives NaN, which losses.depth_loss treats as "no target"."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        out = torch.empty(idx.shape[0], device=self.device, dtype=torch.float32)
+        self.gather_depth_into(idx, out)
+        return out
+
+    def gather_depth_into(self, idx: torch.Tensor, out: torch.Tensor) -> None:
+        """ego_ray_batch_gather_depth into a caller-owned buffer (idx [B] int64, out [B] float32, contiguous, on the bank's device): one
+        launch, no allocation - what GraphedTrainStep captures after the batch source's own launch."""
+        if self.depths is None:
+            raise ValueError("RayBank.gather_depth: this bank was built without depths")
+        _need_hip(idx, "RayBank.gather_depth")
+        if idx.dtype != torch.int64 or out.dtype != torch.float32 or idx.dim() != 1 or out.shape != idx.shape or not idx.is_contiguous() \
+                or not out.is_contiguous() or out.device != idx.device:
+            raise RuntimeError("RayBank.gather_depth_into: idx must be int64 [B] and out float32 [B], contiguous, on the bank's device")
+        _gather_depth(idx, out, self)
 
 
 def _need_hip(t: torch.Tensor, what: str) -> None:
@@ -105,6 +137,13 @@ def ray_batch_sample(idx: torch.Tensor, rays: Optional[torch.Tensor], rgb: Optio
 def _gather(idx, rays, rgb, bank):
     _lib.check(_lib.load().ego_ray_batch_gather(C.byref(bank.struct), idx.data_ptr(), idx.shape[0], _lib.ptr(rays), _lib.ptr(rgb),
                                                 _lib.stream_handle()), "ego_ray_batch_gather")
+
+
+@_lib.device_guard
+def _gather_depth(idx, out, bank):
+    _lib.check(_lib.load().ego_ray_batch_gather_depth(C.byref(bank.struct), bank.depths.data_ptr(), int(bank.depths.dtype == torch.float16),
+                                                      idx.data_ptr(), idx.shape[0], out.data_ptr(), _lib.stream_handle()),
+               "ego_ray_batch_gather_depth")
 
 
 @_lib.device_guard
@@ -188,13 +227,14 @@ class OmniBlenderDataset:
             raise ValueError(f"ray_bank: {path} is not an 8-bit RGB / RGBA image (array {a.dtype} {a.shape})")
         return a
 
-    def ray_bank(self, device=None) -> RayBank:
+    def ray_bank(self, device=None, depths=None) -> RayBank:
         """The training rays and colours as a device-resident `RayBank` (poses + uint8 images read from disk here): what
-        `all_rays[idx]` / `all_rgbs[idx]` return, without materialising either array."""
+        `all_rays[idx]` / `all_rgbs[idx]` return, without materialising either array.  `depths` ([K,h,w] float32 / float16, see RayBank)
+        is passed through: the reference defines no depth file format, so none is read here."""
         if self.is_stack:
             raise ValueError("ray_bank: the flat ray index space is that of is_stack=False")
         imgs = np.stack([self._load_image_u8(p) for p in self.image_paths], 0)
-        return RayBank(self.poses, imgs, self.img_wh, roi=self.roi, normalize=True, device=device or self.device)
+        return RayBank(self.poses, imgs, self.img_wh, roi=self.roi, normalize=True, device=device or self.device, depths=depths)
 
     def rays(self, idx: int, device=None) -> torch.Tensor:
         """[h*w, 6] rays of image `idx`: get_ray_directions_360 + normalisation + get_rays(roi) (dataset_omniblender.py:41-43,79),

@@ -6,10 +6,11 @@ the stored gradient (scaled by the incoming one) back in backward, so `total_los
     utils.py:175-183   ray_entropy_loss             -> ray_entropy_loss
     EgoNeRF.py:189-228 vector_comp_diffs, density_L1, TV_loss_density / TV_loss_app  (methods of model.EgoNeRF call in here)
     (not in the reference) Mip-NeRF 360's distortion regulariser                    -> distortion_loss
+    train.py:249-251   depth_loss (with the gradient the reference's lacks)          -> depth_loss, expected_depth
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -154,3 +155,100 @@ def distortion_loss(alpha: torch.Tensor, z: torch.Tensor, near_far: Sequence[flo
         raise RuntimeError("distortion_loss: z must be a float32 tensor on alpha's device")
     _require_cuda(alpha, "distortion_loss")
     return _RayDistortion.apply(alpha, z.detach().contiguous(), near, far, _DIST_SPACES[space])
+
+
+_DEPTH_SPACES = {"metric": _lib.DIST_METRIC, "log": _lib.DIST_LOG, "disparity": _lib.DIST_DISPARITY}
+_DEPTH_KINDS = {"l2": _lib.DEPTH_L2, "l1": _lib.DEPTH_L1}
+
+
+def _depth_workspace(n_rays: int, device) -> torch.Tensor:
+    """ego_ray_depth_loss's workspace (the valid-ray count and one float64 term per ray); the library states its size."""
+    return torch.empty(_lib.load().ego_ray_depth_loss_workspace_bytes(n_rays) // 8, dtype=torch.float64, device=device)
+
+
+class _RayDepth(torch.autograd.Function):
+    @staticmethod
+    @_lib.device_guard
+    def forward(ctx, alpha: torch.Tensor, z: torch.Tensor, target: torch.Tensor, tail, near: float, far: float, space: int, kind: int):
+        lib, st = _lib.load(), _lib.stream_handle()
+        a = alpha.detach()
+        if a.dtype != torch.float32 or not a.is_contiguous():
+            a = a.float().contiguous()
+        N, S = z.shape
+        value = torch.zeros(1, dtype=torch.float64, device=a.device)
+        g = torch.empty_like(a) if alpha.requires_grad else None
+        ws = _depth_workspace(N, a.device)
+        _lib.check(lib.ego_ray_depth_loss(a.data_ptr(), a.shape[1], z.data_ptr(), target.data_ptr(), _lib.ptr(tail), N, S, near, far, space, kind,
+                                          ws.data_ptr(), value.data_ptr(), _lib.ptr(g), None, st), "ego_ray_depth_loss")
+        ctx.g = g
+        return value.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g = ctx.g
+        ctx.g = None
+        return (None if g is None else g * g_out), None, None, None, None, None, None, None
+
+
+def _depth_args(what: str, alpha: torch.Tensor, z: torch.Tensor, per_ray: dict):
+    """The shape, dtype and device checks depth_loss and expected_depth share; -> the per-ray vectors, detached and contiguous."""
+    if alpha.dim() != 2 or z.dim() != 2 or alpha.shape[0] != z.shape[0] or alpha.shape[1] - z.shape[1] not in (0, 1) or z.shape[1] < 2:
+        raise RuntimeError(f"{what}: alpha {tuple(alpha.shape)} and z {tuple(z.shape)} must be [N, S] or [N, S + 1] and [N, S], S >= 2")
+    if z.dtype != torch.float32 or z.device != alpha.device:
+        raise RuntimeError(f"{what}: z must be a float32 tensor on alpha's device")
+    out = []
+    for name, t in per_ray.items():
+        if t is None:
+            out.append(None)
+            continue
+        if t.dim() != 1 or t.shape[0] != z.shape[0] or t.dtype != torch.float32 or t.device != alpha.device:
+            raise RuntimeError(f"{what}: {name} must be a float32 [N] tensor on alpha's device, N = {z.shape[0]}")
+        out.append(t.detach().contiguous())
+    _require_cuda(alpha, what)
+    return out
+
+
+def depth_loss(alpha: torch.Tensor, z: torch.Tensor, target: torch.Tensor, tail: Optional[torch.Tensor] = None, space: str = "metric",
+               near_far: Optional[Sequence[float]] = None, kind: str = "l2") -> torch.Tensor:
+    """The depth term of train.py:249-251 / :275-283 with its gradient (the reference computes depth_map under no_grad, so its own term
+    has none): the mean over the VALID rays of (D - s(target))^2 ("l2") or |D - s(target)| ("l1"), D = sum_i w_i s(z_i) +
+    (1 - sum_i w_i) s(tail) with the render's weights w; csrc/ego_reg.hip states the O(S) form.  A ray is valid iff its target is finite
+    and > 0 (0 = no target, as in the reference; NaN, inf and negative targets drop out too); with no valid ray the loss and the gradient
+    are 0.  `space`: "metric" (s = identity, the reference's term), "log" or "disparity" (distortion_loss's normalised maps; they need
+    `near_far`).  alpha [N, S] or [N, S + 1] as returned by EgoNeRF.forward, z [N, S] = `model.last_train_z` of the SAME render, target
+    [N] float32 in units of distance along the normalised ray.  `tail=None` puts the mass a ray does not absorb at 0;
+    `tail=rays[:, 5]` reproduces the render's own depth_map, which adds (1 - acc) * rays[..., -1].  alpha is the only differentiable
+    input; the render's `depth` output is not involved and stays non-differentiable."""
+    if space not in _DEPTH_SPACES:
+        raise ValueError(f"depth_loss: space must be one of {sorted(_DEPTH_SPACES)}, not {space!r}")
+    if kind not in _DEPTH_KINDS:
+        raise ValueError(f"depth_loss: kind must be one of {sorted(_DEPTH_KINDS)}, not {kind!r}")
+    near, far = 0.0, 0.0
+    if space != "metric":
+        if near_far is None:
+            raise ValueError(f"depth_loss: the {space!r} space needs near_far")
+        near, far = float(near_far[0]), float(near_far[1])
+        if not (0.0 < near < far < float("inf")):
+            raise ValueError(f"depth_loss: the {space!r} space needs finite 0 < near < far (near_far = {near}, {far})")
+    if target is None:
+        raise RuntimeError("depth_loss: target must be a float32 [N] tensor on alpha's device")
+    target, tail = _depth_args("depth_loss", alpha, z, dict(target=target, tail=tail))
+    return _RayDepth.apply(alpha, z.detach().contiguous(), target, tail, near, far, _DEPTH_SPACES[space], _DEPTH_KINDS[kind])
+
+
+@_lib.device_guard
+def _expected_depth(a, z, tail):
+    pred = torch.empty(z.shape[0], device=a.device)
+    _lib.check(_lib.load().ego_ray_depth_loss(a.data_ptr(), a.shape[1], z.data_ptr(), None, _lib.ptr(tail), z.shape[0], z.shape[1], 0.0, 0.0,
+                                              _lib.DIST_METRIC, _lib.DEPTH_L2, None, None, None, pred.data_ptr(), _lib.stream_handle()),
+               "ego_ray_depth_loss")
+    return pred
+
+
+def expected_depth(alpha: torch.Tensor, z: torch.Tensor, tail: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """D of depth_loss in the metric space, [N] float32, no target needed and no gradient: sum_i w_i z_i + (1 - sum_i w_i) tail."""
+    (tail,) = _depth_args("expected_depth", alpha, z, dict(tail=tail))
+    a = alpha.detach()
+    if a.dtype != torch.float32 or not a.is_contiguous():
+        a = a.float().contiguous()
+    return _expected_depth(a, z.detach().contiguous(), tail)

@@ -589,6 +589,18 @@ class TrainSchedule:
         w = float(w0) * torch.pow(torch.full_like(it, float(factor)), n)
         return torch.where(gate, w, torch.zeros_like(w)).float()
 
+    def stepped(self, w0: float, rate: float, step_size: float, end_iter: Optional[int] = None) -> torch.Tensor:
+        """The depth term's weight in the current iteration (float32 device scalar): `depth_lambda * depth_rate ** int(iteration /
+        depth_step_size)` (train.py:276), and 0 once `iteration > depth_end_iter` (train.py:279-281, where the reference zeroes the
+        term itself)."""
+        it = self.it
+        if not float(step_size) > 0.0:
+            raise ValueError("TrainSchedule.stepped: step_size must be > 0")
+        w = float(w0) * torch.pow(torch.full_like(it, float(rate)), torch.floor(it / float(step_size)))
+        if end_iter is not None:
+            w = torch.where(it > float(end_iter), torch.zeros_like(w), w)
+        return w.float()
+
     def iteration(self) -> int:
         return int(self.it.item())
 
@@ -625,10 +637,18 @@ class GraphedTrainStep:
     INSIDE the graph - the iteration starts with the source's one launch writing indices, rays and colours into the static buffers
     `self.idx` / `self.rays` / `self.target`, and the source's device counter is advanced next to `schedule.it` - so `rays` / `target`
     are omitted, `step()` takes no arguments and nothing crosses the host link per iteration.  `start_iteration` positions the source's
-    counter as well: iteration k of a resumed run draws `batch_source.indices_at(k)`."""
+    counter as well: iteration k of a resumed run draws `batch_source.indices_at(k)`.
+
+    Depth targets (losses.depth_loss): a `loss_fn` with a parameter NAMED `depth` receives the batch's targets as the keyword
+    `depth=self.depth`, a static float32 [B] buffer.  With a `batch_source` whose bank has depths (RayBank(depths=...)) the buffer is
+    filled inside the graph, by `bank.gather_depth_into(self.idx, self.depth)` right after the source's launch; with host-fed batches
+    the constructor takes an example `depth=` [B] and `step(rays, target, depth=...)` copies the iteration's targets in.  A loss_fn that
+    names `depth` without either source is refused at construction.  The weight of train.py:276 is `sched.stepped(depth_lambda,
+    depth_rate, depth_step_size, depth_end_iter)`; the term reads `model.last_train_z` like the distortion term:
+    `depth_loss(alpha, model.last_train_z, depth)` (tests/test_hip_depth_loss.py pins it against the eager loop)."""
 
     def __init__(self, model, optimizer, rays=None, target=None, render_kwargs=None, loss_fn=None, warmup=3, noise_fn=None, start_iteration=0,
-                 schedule_aware=None, batch_source=None):
+                 schedule_aware=None, batch_source=None, depth=None):
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs FusedAdam(capturable=True): the step count and lr schedule must live on the device")
         if render_kwargs is None:
@@ -642,6 +662,10 @@ class GraphedTrainStep:
             target = torch.empty(batch_source.batch, 3, device=dev0, dtype=torch.float32)
             self.idx = torch.empty(batch_source.batch, device=dev0, dtype=torch.int64)
             batch_source.seek(start_iteration)
+            if depth is not None:
+                raise ValueError("GraphedTrainStep: with a batch_source the depth targets come from its bank (RayBank(depths=...)); pass no depth")
+            if getattr(batch_source.bank, "depths", None) is not None:
+                depth = torch.empty(batch_source.batch, device=dev0, dtype=torch.float32)
         elif rays is None or target is None:
             raise ValueError("GraphedTrainStep needs an example batch (rays, target) or a batch_source")
         if rays is not None and rays.requires_grad:
@@ -657,6 +681,18 @@ class GraphedTrainStep:
             except (TypeError, ValueError):
                 schedule_aware = False
         self._loss_takes_schedule = bool(schedule_aware)
+        # the same opt-in by name for the depth targets
+        try:
+            import inspect
+            self._loss_takes_depth = "depth" in inspect.signature(self.loss_fn).parameters
+        except (TypeError, ValueError):
+            self._loss_takes_depth = False
+        if self._loss_takes_depth and depth is None:
+            raise ValueError("GraphedTrainStep: loss_fn names `depth` but there is no depth source: pass depth= with a host-fed batch, "
+                             "or a batch_source whose bank has depths")
+        if depth is not None and (depth.dim() != 1 or depth.shape[0] != rays.shape[0]):
+            raise ValueError(f"GraphedTrainStep: depth must be [B] = [{rays.shape[0]}], got {tuple(depth.shape)}")
+        self.depth = None if depth is None else depth.detach().to(rays.device).float().contiguous().clone()
         self.schedule = TrainSchedule(rays.device, start_iteration)
         # noise_fn(n_rays, n_samples, device) -> [n_rays, n_samples] in [0, 1): torch.rand by default; tests pin it
         self.noise_fn = noise_fn or (lambda n, m, dev: torch.rand(n, m, device=dev))
@@ -681,11 +717,14 @@ class GraphedTrainStep:
         kw = self.kw
         if self.source is not None:   # this iteration's batch, drawn from the source's device counter straight into the static inputs
             self.source.sample_into(self.idx, self.rays, self.target)
+            if self.depth is not None:
+                self.source.bank.gather_depth_into(self.idx, self.depth)
         # the is_train noise comes from the device generator (graph-safe: every replay draws new numbers)
         jitter = self.noise_fn(N, kw["n_coarse"], dev)
         u = self.noise_fn(N, kw["n_fine"], dev) if kw.get("resampling") else None
         rgb, _depth, _bg, _env, alpha = self.model(self.rays, is_train=True, jitter=jitter, u=u, **kw)
-        loss = self.loss_fn(rgb, self.target, alpha, self.schedule) if self._loss_takes_schedule else self.loss_fn(rgb, self.target, alpha)
+        extra = dict(depth=self.depth) if self._loss_takes_depth else {}
+        loss = self.loss_fn(rgb, self.target, alpha, self.schedule, **extra) if self._loss_takes_schedule else self.loss_fn(rgb, self.target, alpha, **extra)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         self.opt.step()
@@ -696,9 +735,9 @@ class GraphedTrainStep:
             self.source.counter.add_(1)
         return loss.detach()
 
-    def __call__(self, rays=None, target=None):
+    def __call__(self, rays=None, target=None, depth=None):
         if self.source is not None:
-            if rays is not None or target is not None:
+            if rays is not None or target is not None or depth is not None:
                 raise ValueError("this GraphedTrainStep draws its batches from its batch_source inside the graph: call step() without arguments")
         elif rays is None or target is None:
             raise ValueError("this GraphedTrainStep was built without a batch_source: call step(rays, target)")
@@ -707,6 +746,12 @@ class GraphedTrainStep:
                 raise NotImplementedError(_GRAPHED_RAY_GRADS)
             self.rays.copy_(rays, non_blocking=True)
             self.target.copy_(target, non_blocking=True)
+            if depth is not None:
+                if self.depth is None:
+                    raise ValueError("this GraphedTrainStep was built without depth targets: pass an example depth= to the constructor")
+                self.depth.copy_(depth, non_blocking=True)
+            elif self._loss_takes_depth:
+                raise ValueError("this GraphedTrainStep's loss_fn takes depth targets: call step(rays, target, depth=...)")
         self.graph.replay()
         self.iterations += 1
         # the replayed optimiser wrote the parameters through raw pointers: tell autograd and the model's packed-weight cache

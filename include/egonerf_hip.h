@@ -243,6 +243,14 @@ enum { EGO_BATCH_SIMPLE = 0, EGO_BATCH_THETA = 1 };
 int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, const int64_t* counter, const float* row_cdf, int64_t B,
                          int64_t* idx, float* rays, float* rgb, void* stream);
 
+/* Depth targets next to a bank (append-only addition, EGO_ABI_VERSION stays 17; ego_ray_bank itself does not change): depth [K][H][W] dev,
+ * float32 (is_half == 0) or float16 (is_half != 0), one value per pixel of the bank's full images, in units of distance along the
+ * normalised ray, 0 = no target.  out[i] (float32 [B] dev) = the depth of the pixel idx[i] names in the bank's index space (img, r0 + row,
+ * c0 + col), converted exactly.  As in ego_ray_batch_gather, a row whose index is outside [0, total) reads nothing and is filled with NaN
+ * (ego_ray_depth_loss then treats that ray as invalid).  The bank's images may be NULL.  B == 0 is a no-op. */
+int ego_ray_batch_gather_depth(const ego_ray_bank* bank, const void* depth, int32_t is_half, const int64_t* idx, int64_t B, float* out,
+                               void* stream);
+
 /* ---- camera paths (csrc/ego_camera.hip; append-only additions, EGO_ABI_VERSION stays 17: no existing symbol, struct or argument list
  * changed): the two ends of evaluation_path (renderer.py:199-255) and of the tail of evaluation (renderer.py:141-174) ---- */
 enum { EGO_CAM_ERP = 0, EGO_CAM_PINHOLE = 1, EGO_CAM_PINHOLE_BLENDER = 2 };
@@ -704,6 +712,33 @@ enum { EGO_DIST_LINEAR = 0 /* (z - near) / (far - near) */, EGO_DIST_LOG = 1 /* 
        EGO_DIST_DISPARITY = 2 /* (1 / near - 1 / max(z, near)) / (1 / near - 1 / far) */ };
 int ego_ray_distortion(const float* alpha, int32_t alpha_stride, const float* z, int64_t N, int32_t S, float near_, float far_, int32_t space,
                        double* value, float* g_alpha, void* stream);
+/* Depth supervision (train.py:249-251, :275-283: masked MSE between depth_map and a per-ray target; append-only addition, EGO_ABI_VERSION
+ * stays 17).  The reference computes depth_map under no_grad (EgoNeRF.py:595-598), so its term adds a number and no gradient; this is the
+ * term with its gradient, entering through alpha like the two terms above - the render's depth output stays non-differentiable.  With
+ * w_i = alpha_i T_i, T_i = prod_{j<i} (1 - alpha_j + 1e-10), q_i = s(z_i), q_t = s(tail) (0 when tail is NULL):
+ *   D = sum_i w_i q_i + (1 - sum_i w_i) q_t,    dD / dalpha_i = T_i (G_i - R_i),  G_i = q_i - q_t,
+ *   R_{S-1} = 0, R_i = G_{i+1} alpha_{i+1} + (1 - alpha_{i+1} + 1e-10) R_{i+1}        (no division: alpha = 1 is harmless)
+ * s = `space`: EGO_DIST_METRIC (identity: the reference's term; near_ / far_ unused), EGO_DIST_LOG or EGO_DIST_DISPARITY (the maps of
+ * ego_ray_distortion; they need finite 0 < near_ < far_).  A ray is valid iff its target is finite and > 0 (the reference's mask is != 0;
+ * NaN, inf and negative targets drop out as well); V = the number of valid rays, counted on the device; r = D - s(target):
+ *   EGO_DEPTH_L2: value += (1 / V) sum_valid r^2,  g_alpha_i = (2 r / V) dD / dalpha_i
+ *   EGO_DEPTH_L1: value += (1 / V) sum_valid |r|,  g_alpha_i = (sign(r) / V) dD / dalpha_i, 0 at r = 0
+ * An invalid ray's gradient row is exactly 0; with V = 0 nothing is added to value and every gradient element is exactly 0.
+ * alpha [N][alpha_stride], alpha_stride = S or S + 1 (an envmap's trailing ones column takes no part and gets the gradient 0), z [N][S],
+ * target [N], tail [N] or NULL: float32 dev, all constant but alpha.  tail = the rays' last component reproduces the render's own
+ * depth_map, which adds (1 - sum w) rays[..., -1] (EgoNeRF.py:597).  Outputs, each optional: `value`, a float64 device scalar zeroed by
+ * the caller; g_alpha [N][alpha_stride], every element WRITTEN, must not overlap alpha; pred [N] = D of every ray, valid or not.
+ * target may be NULL when only pred is asked for.  `workspace`: caller-owned, 8-byte aligned, ego_ray_depth_loss_workspace_bytes(N)
+ * = 16 + 8 N bytes (V and one float64 term per ray), needed with value or g_alpha, overwritten, no need to clear it.  Value and gradient
+ * are bit-reproducible, and value-only, gradient-only and joint calls return the same bits: every sum has a fixed order.  Refuses
+ * S < 2, another alpha_stride, an unknown space or kind, near_ / far_ outside a space's domain, and null arguments; N == 0 is a no-op.
+ * Up to three launches, no allocation, no synchronisation: it can be captured into a hipGraph. */
+enum { EGO_DIST_METRIC = 3 /* s(z) = z; ego_ray_depth_loss only */ };
+enum { EGO_DEPTH_L2 = 0, EGO_DEPTH_L1 = 1 };
+int64_t ego_ray_depth_loss_workspace_bytes(int64_t N);
+int ego_ray_depth_loss(const float* alpha, int32_t alpha_stride, const float* z, const float* target, const float* tail, int64_t N, int32_t S,
+                       float near_, float far_, int32_t space, int32_t kind, void* workspace, double* value, float* g_alpha, float* pred,
+                       void* stream);
 /* coordinates.py:27-39 and :226-266 (up_sampling_VM): bilinear, align_corners=True, zero-padded resample of a table at
  * per-axis normalised positions xs [W2], ys [H2] (device) -> dst [H2][W2][C]. */
 int ego_resample_table(const float* src, int32_t C, int32_t H, int32_t W, const float* xs, const float* ys, int32_t H2, int32_t W2,
