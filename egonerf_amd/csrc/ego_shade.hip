@@ -1041,7 +1041,7 @@ __device__ __forceinline__ void gather_app_dense(const char* __restrict__ G, uin
 
 // PX: arithmetic of the MLP's correction terms: 0 = fp16 (f16x3), 1 = fp8 (f16f8), 2 = fp6 (f16f6)
 // FOLD: rows H / J in the epilogue (models/EgoNeRF.py:579-598): a wave owns whole rays (S a multiple of 32, a ray = S / 32 consecutive
-// tiles), keeps sum w rgb / sum w (lane half 0) and sum w z (lane half 1) per lane across the ray's tiles and finishes the pixel -
+// tiles), keeps sum w r, w b, w (lane half 0) and sum w g, w z (lane half 1) per lane across the ray's tiles and finishes the pixel -
 // background, clamp, depth - itself; no per-sample colours are written and k_composite (12 us per 4096 x 512 launch: 25 MB of colours
 // written here, 42 MB read there) is not launched.
 // COMPACT: the tiles are cut from the live-sample list (ego_shade_live) instead of the flat [N][S] order: lane j of tile t shades sample
@@ -1053,6 +1053,11 @@ __device__ __forceinline__ void gather_app_dense(const char* __restrict__ G, uin
 template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false, bool COMPACT = false, bool DAPP = false>
 __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   constexpr bool P8 = PX == 1, P6 = PX == 2;
+  // RAY_VIEW: a folded wave's tiles are whole rays, so the dense instances encode the view direction once per ray and keep the lane
+  // half's eight view slots across its tiles; their tile loop holds no division m / S, no load of the direction and no encoding of it.
+  // The table instances have no registers for that (built: 6 / 19 VGPRs spilled in the f16x3 / f16f6 forms; with the direction as
+  // scalars and the encoding per tile, 7 of 1780 VALU per tile) and keep the per-tile form.
+  constexpr bool RAY_VIEW = FOLD && DAPP;
   static_assert(!DAPP || (MODE != MODE_MLP && !DUMP && !TAB16), "the dense gather replaces the fp32-table gather of inference only");
   static_assert(!FOLD || (MODE == MODE_SHADE && !DUMP), "compositing folds into the fused inference kernel only");
   static_assert(!COMPACT || (MODE == MODE_SHADE && !DUMP && !FOLD), "the live-sample list is an input of the two-launch inference shade only");
@@ -1106,15 +1111,24 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
   // mask in the prologue, or chunks dealt through an atomic counter) was built and measured: DESIGN.md 4.3.
   const int64_t n_wv = (int64_t)gridDim.x * 8;
   const int64_t tpr = FOLD ? (int64_t)(A.S >> 5) : 0;   // tiles per ray
-  const int64_t per_wave = FOLD ? ((A.M / A.S + n_wv - 1) / n_wv) * tpr : (n_tiles + n_wv - 1) / n_wv;
+  const int64_t rays_per_wave = FOLD ? (A.M / A.S + n_wv - 1) / n_wv : 0;
+  const int64_t per_wave = FOLD ? rays_per_wave * tpr : (n_tiles + n_wv - 1) / n_wv;
   const int64_t tile0 = ((int64_t)blockIdx.x * 8 + wave) * per_wave;
   const int64_t tile1 = tile0 + per_wave < n_tiles ? tile0 + per_wave : n_tiles;
   const int64_t seg_len = FOLD ? tpr : per_wave;   // FOLD: one ray per segment
-  for (int64_t seg0 = tile0; seg0 < tile1; seg0 += seg_len) {
+  int64_t fold_ray = ((int64_t)blockIdx.x * 8 + wave) * rays_per_wave;   // FOLD: the segment's ray, seg0 / tpr, counted instead of divided
+  for (int64_t seg0 = tile0; seg0 < tile1; seg0 += seg_len, ++fold_ray) {
   const int64_t seg1 = seg0 + seg_len < tile1 ? seg0 + seg_len : tile1;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;   // FOLD, lane half 0: sum w r, w g, w b, w; half 1: sum w z in c0
-  // the ray's d_z for the depth quirk: wave-uniform address, fetched (scalar) at the top of the ray instead of in its epilogue
-  const float fold_dz = FOLD ? A.rays[(seg0 / tpr) * 6 + 5] : 0.f;
+  float c0 = 0.f, c1 = 0.f, c2 = 0.f;   // FOLD, lane half 0: sum w r, w b, w; half 1: sum w g, w z
+  // What a ray's tiles share is fetched and made once, at the top of the ray (so also for a ray whose first tiles, or all of them,
+  // the tile mask skips), through a wave-uniform address: d_z for the depth quirk of the epilogue and, with RAY_VIEW, the lane half's
+  // eight view slots - by the function and on the floats that the other forms use per tile, so the bits are theirs.
+  float fold_dz = 0.f, fold_vw[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if constexpr (FOLD) {
+    const float* R = A.rays + fold_ray * 6;
+    fold_dz = R[5];
+    if constexpr (RAY_VIEW) view_slots<EncHw>(R[3], R[4], fold_dz, h, fold_vw);
+  }
   // the tile mask is read 64 tiles at a time (one byte per lane + ballot) and walked with find-first-set: a skipped tile costs no
   // memory round trip (a per-tile flag load sat on the critical path of every skipped tile)
   for (int64_t wbase = seg0; wbase < seg1; wbase += 64) {
@@ -1158,11 +1172,13 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
         const int b = g ? 3 : 0;
         a_r = p[b]; a_th = p[b + 1]; a_ph = p[b + 2];
       } else {
-        int32_t s_div = A.S;
-        if constexpr (DAPP) asm volatile("" : "+s"(s_div));   // (the reciprocal behind the division is such an invariant too)
-        const uint32_t ray = (uint32_t)m / (uint32_t)s_div;
-        const float* R = A.rays + (int64_t)ray * 6;
-        vd0 = R[3]; vd1 = R[4]; vd2 = R[5];
+        if constexpr (!RAY_VIEW) {   // (RAY_VIEW: the ray is the segment's, its view slots are in fold_vw)
+          int32_t s_div = A.S;
+          if constexpr (DAPP) asm volatile("" : "+s"(s_div));   // (the reciprocal behind the division is such an invariant too)
+          const uint32_t ray = (uint32_t)m / (uint32_t)s_div;
+          const float* R = A.rays + (int64_t)ray * 6;
+          vd0 = R[3]; vd1 = R[4]; vd2 = R[5];
+        }
         // normalised coordinates come from ego_march_density (no acos/atan2/LUT search here)
         const f32x4 cc = ((const f32x4*)A.coords)[m];
         a_r = cc.x; a_th = cc.y; a_ph = cc.z; g = cc.w != 0.f;
@@ -1242,7 +1258,12 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
       for (int q = 0; q < 4; ++q) __builtin_nontemporal_store(f32x4{fe[4 * q], fe[4 * q + 1], fe[4 * q + 2], fe[4 * q + 3]}, &((f32x4*)A.dump_fe)[(tile * 4 + q) * 64 + lane]);
     }
     float vw[8];
-    view_slots<EncHw>(vd0, vd1, vd2, ht, vw);
+    if constexpr (RAY_VIEW) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vw[e] = fold_vw[e];
+    } else {
+      view_slots<EncHw>(vd0, vd1, vd2, ht, vw);
+    }
 
     // ---- layer 1 (10 steps of 8 values per lane half) ----------------------------------------------------------
     f32x16 H[4];
@@ -1279,31 +1300,32 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
         o0 = fmaf(hv, w3[r].x, o0); o1 = fmaf(hv, w3[r].y, o1); o2 = fmaf(hv, w3[r].z, o2);
       }
     }
-    if constexpr (DAPP) {   // __shfl_xor(v, 32, 64) with the partner's index taken from the opaque lane copy (see jt / ht)
-      const int partner = (lw ^ 32) << 2;
-      o0 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o0)));
-      o1 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o1)));
-      o2 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o2)));
-    } else {
-      o0 += __shfl_xor(o0, 32, 64);
-      o1 += __shfl_xor(o1, 32, 64);
-      o2 += __shfl_xor(o2, 32, 64);
+    // A channel's logit is own + partner, in either lane of the pair.  Lane half 0 finishes red and blue, half 1 green: one exchange
+    // carries what the partner finishes (half 1's o0, half 0's o1), one o2; two sigmoids per lane instead of three.
+    float oa = ht ? o1 : o0;
+    {
+      const float give = ht ? o0 : o1;
+      if constexpr (DAPP) {   // __shfl_xor(v, 32, 64) with the partner's index taken from the opaque lane copy (see jt / ht)
+        const int partner = (lw ^ 32) << 2;
+        oa += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(give)));
+        o2 += __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(o2)));
+      } else {
+        oa += __shfl_xor(give, 32, 64);
+        o2 += __shfl_xor(o2, 32, 64);
+      }
     }
+    const float* b3 = lds + OFF_B3;
+    const float ca = sigmoidf(oa + (ht ? b3[1] : b3[0])), cb = sigmoidf(o2 + b3[2]);   // half 0: red, blue; half 1: green, (blue)
     if (FOLD) {
       // weights are >= 0 and a tile skipped above holds only zeros (the fold is used with shade_above = 0), so nothing is conditional
-      const float* b3 = lds + OFF_B3;
       const float wgt = valid ? fold_w : 0.f;
-      const float x0 = ht ? fold_z : sigmoidf(o0 + b3[0]);
-      c0 += wgt * x0;
-      c1 += wgt * sigmoidf(o1 + b3[1]);
-      c2 += wgt * sigmoidf(o2 + b3[2]);
-      c3 += wgt;
-    } else if (valid && ht == 0) {
-      const float* b3 = lds + OFF_B3;
+      c0 += wgt * ca;
+      c1 += wgt * (ht ? fold_z : cb);
+      c2 += wgt;
+    } else if (valid) {
       float* o = A.out + m * 3;
-      o[0] = sigmoidf(o0 + b3[0]);
-      o[1] = sigmoidf(o1 + b3[1]);
-      o[2] = sigmoidf(o2 + b3[2]);
+      if (ht == 0) { o[0] = ca; o[2] = cb; }
+      else o[1] = ca;
     }
   }
   }
@@ -1312,14 +1334,17 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
     // row_shr 1, 2, 4, 8 inside the 16-lane rows, then row_bcast:15 into rows 1 / 3: lane 31 holds half 0's sums, lane 63 half 1's
 #define EGO_SUM_STEP(v, ctrl, rmask) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rmask, 0xf, false))
 #define EGO_HALF_SUM(v) EGO_SUM_STEP(v, 0x111, 0xf); EGO_SUM_STEP(v, 0x112, 0xf); EGO_SUM_STEP(v, 0x114, 0xf); EGO_SUM_STEP(v, 0x118, 0xf); EGO_SUM_STEP(v, 0x142, 0xa)
-    EGO_HALF_SUM(c0); EGO_HALF_SUM(c1); EGO_HALF_SUM(c2); EGO_HALF_SUM(c3);
+    EGO_HALF_SUM(c0); EGO_HALF_SUM(c1); EGO_HALF_SUM(c2);
+    // (the tree is the same in both halves, so lane 63's green is the sum lane 31 would have formed of the same per-lane values)
+    const float green = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c0), 63));
+    const float dp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c1), 63));
 #undef EGO_HALF_SUM
 #undef EGO_SUM_STEP
-    const float dp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c0), 63));
     if (lane == 31) {
-      const int64_t ray = seg0 / tpr;
+      const int64_t ray = fold_ray;
       const float* R = A.rays + ray * 6;
-      float cr = c0, cg = c1, cb = c2;
+      float cr = c0, cg = green, cb = c1;
+      const float c3 = c2;
       if (A.envmap) {
         float e[3];
         envmap_lookup(A.envmap, A.envmap_h, R[3], R[4], R[5], e);
