@@ -125,6 +125,7 @@ TEXEL_ADAM_PROJECT, TEXEL_ADAM_ZERO_GRAD = 1, 2   # EGO_TEXEL_ADAM_*
 DIST_LINEAR, DIST_LOG, DIST_DISPARITY = 0, 1, 2   # EGO_DIST_*
 DIST_METRIC = 3   # EGO_DIST_METRIC (ego_ray_depth_loss only)
 DEPTH_L2, DEPTH_L1 = 0, 1   # EGO_DEPTH_*
+PHOTO_L2, PHOTO_L1, PHOTO_HUBER, PHOTO_CHARBONNIER = 0, 1, 2, 3   # EGO_PHOTO_*
 
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SP = C.POINTER(Scene)
@@ -148,6 +149,7 @@ PROTOTYPES = {
     "ego_ray_batch_gather": (C.c_int, [C.POINTER(RayBankStruct), P, I64, P, P, P]),
     "ego_ray_batch_sample": (C.c_int, [C.POINTER(RayBankStruct), I32, C.c_uint64, P, P, I64, P, P, P, P]),
     "ego_ray_batch_gather_depth": (C.c_int, [C.POINTER(RayBankStruct), P, I32, P, I64, P, P]),
+    "ego_ray_batch_gather_mask": (C.c_int, [C.POINTER(RayBankStruct), P, P, I64, P, P]),
     "ego_camera_rays": (C.c_int, [I32, I32, I32, F32, F32, F32, F32, I32, P, I64, I64, P, P]),
     "ego_finish_frame": (C.c_int, [P, P, I64, I64, I32, I32, F32, F32, P, I32, P, P, P]),
     "ego_camera_rays_ex": (C.c_int, [I32, I32, I32, F32, F32, F32, F32, I32, P, I64, I64, I32, F32, I32, P, P]),
@@ -228,6 +230,9 @@ PROTOTYPES = {
     "ego_ray_distortion": (C.c_int, [P, I32, P, I64, I32, F32, F32, I32, P, P, P]),
     "ego_ray_depth_loss_workspace_bytes": (I64, [I64]),
     "ego_ray_depth_loss": (C.c_int, [P, I32, P, P, P, I64, I32, F32, F32, I32, I32, P, P, P, P, P]),
+    "ego_photo_loss_workspace_bytes": (I64, [I64, I32]),
+    "ego_photo_loss": (C.c_int, [P, P, P, P, P, I64, I32, I32, F32, P, P, P, P, P]),
+    "ego_photo_fit": (C.c_int, [P, P, P, P, I64, I32, P, P, P]),
     "ego_resample_table": (C.c_int, [P, I32, I32, I32, P, P, I32, I32, P, P]),
     "ego_adam_step": (C.c_int, [C.POINTER(AdamTensor), I32, F32, F32, F32, I32, P]),
     "ego_adam_step_graph": (C.c_int, [C.POINTER(AdamTensor), I32, F32, F32, F32, C.c_double, P, P]),

@@ -144,6 +144,22 @@ __global__ __launch_bounds__(256) void k_ray_batch_gather_depth(BankArgs b, cons
   out[i] = is_half ? (float)((const _Float16*)depth)[px] : ((const float*)depth)[px];
 }
 
+// the mask weight of one row of all_rays: the pixel gather_row reads the colour of, from a [K][H][W] uint8 array, 255 -> 1
+__global__ __launch_bounds__(256) void k_ray_batch_gather_mask(BankArgs b, const uint8_t* __restrict__ mask, const int64_t* __restrict__ idx,
+                                                               int64_t B, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  const int64_t id = idx[i];
+  if (id < 0 || id >= b.total) {   // outside the caller's contract: touch no memory of the bank, mark the row
+    out[i] = __int_as_float(0x7fc00000);
+    return;
+  }
+  const int img = (int)(id / b.per_img);
+  const int64_t rem = id - (int64_t)img * b.per_img;
+  const int row = b.r0 + (int)(rem / b.n_cols), col = b.c0 + (int)(rem % b.n_cols);
+  out[i] = __fdiv_rn((float)mask[((int64_t)img * b.H + row) * b.W + col], 255.f);
+}
+
 // shared argument checks; `what` names the entry point in the message
 int check_bank(const ego_ray_bank* bank, bool need_images, const char* what, BankArgs* out) {
   if (!bank) return ego_fail(EGO_E_BADARG, "%s: null bank", what);
@@ -192,6 +208,17 @@ int ego_ray_batch_gather_depth(const ego_ray_bank* bank, const void* depth, int3
   EGO_REQUIRE(((uintptr_t)depth & (is_half ? 1 : 3)) == 0, "ray_batch_gather_depth: depth must be aligned to its element size");
   k_ray_batch_gather_depth<<<nblk(B, 256), 256, 0, (hipStream_t)stream>>>(b, depth, is_half, idx, B, out);
   return ego_launch_status("k_ray_batch_gather_depth");
+}
+
+int ego_ray_batch_gather_mask(const ego_ray_bank* bank, const uint8_t* mask, const int64_t* idx, int64_t B, float* out, void* stream) {
+  EGO_TRACE("ego_ray_batch_gather_mask");
+  BankArgs b;
+  if (const int e = check_bank(bank, false, "ray_batch_gather_mask", &b)) return e;
+  EGO_REQUIRE(B >= 0, "ray_batch_gather_mask: B < 0");
+  if (B == 0) return EGO_OK;
+  EGO_REQUIRE(mask && idx && out, "ray_batch_gather_mask: null mask, idx or out");
+  k_ray_batch_gather_mask<<<nblk(B, 256), 256, 0, (hipStream_t)stream>>>(b, mask, idx, B, out);
+  return ego_launch_status("k_ray_batch_gather_mask");
 }
 
 int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, const int64_t* counter, const float* row_cdf, int64_t B,

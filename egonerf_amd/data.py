@@ -36,10 +36,17 @@ class RayBank:
     `gather_depth(idx)` returns the targets of ray indices as float32.  The reference defines no depth file format (its loaders never
     fill all_depth, dataset_interface.py:41), so reading one is the caller's business.
 
+    masks (optional) [K,H,W] uint8 (0 = ignore the pixel, 255 = full weight) or bool (stored as 0 / 255), array or tensor: one value per
+    pixel of the full images - the photographer, the tripod at the nadir, the stitching seam (the Ricoh360 layout ships a mask.png next
+    to its images; dataset_egocentric_video.py drops it from the file list and never builds the all_masks it reads).  Kept on the
+    device as uint8; `gather_mask(idx)` returns mask / 255 of ray indices as float32, the `weight` of losses.photometric_loss.  The
+    samplers do not look at the masks: masked pixels are still drawn and carry weight 0, so a nadir mask wastes the masked share of a
+    batch, and the loss normalises by the sum of the weights it did get.
+
     A bank on device="cpu" holds the host state only (shapes, window, struct): gather / sampling need the HIP device."""
 
     def __init__(self, poses, images_u8, img_wh: Sequence[int], roi: Sequence[float] = (0, 1, 0, 1), normalize: bool = True, device="cuda",
-                 depths=None):
+                 depths=None, masks=None):
         W, H = int(img_wh[0]), int(img_wh[1])
         poses = torch.as_tensor(np.asarray(poses) if not torch.is_tensor(poses) else poses).float()
         if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
@@ -65,6 +72,13 @@ class RayBank:
             if d.dtype not in (torch.float32, torch.float16) or tuple(d.shape) != (K, H, W):
                 raise ValueError(f"RayBank: depths must be float32 or float16 [K,H,W] = {(K, H, W)}, got {d.dtype} {tuple(d.shape)}")
             self.depths = d.detach().contiguous().to(self.device)
+        self.masks = None
+        if masks is not None:
+            m = masks if torch.is_tensor(masks) else torch.from_numpy(np.ascontiguousarray(masks))
+            if m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != (K, H, W):
+                raise ValueError(f"RayBank: masks must be uint8 or bool [K,H,W] = {(K, H, W)}, got {m.dtype} {tuple(m.shape)}")
+            m = m.detach()
+            self.masks = (m.to(torch.uint8) * 255 if m.dtype == torch.bool else m).contiguous().to(self.device)
         self.K, self.H, self.W = K, H, W
         self.r0, self.n_rows, self.c0, self.n_cols = r0, r1 - r0, c0, c1 - c0
         self.roi, self.normalize = list(roi), bool(normalize)
@@ -74,9 +88,10 @@ class RayBank:
 
     @property
     def nbytes(self) -> int:
-        """Bytes the bank holds (on its device): K * H * W * 4 for the images + K * 48 for the poses (+ K * H * W * 4 or 2 for depths)."""
+        """Bytes the bank holds (on its device): K * H * W * 4 for the images + K * 48 for the poses (+ K * H * W * 4 or 2 for depths, + K * H * W for masks)."""
         depth = 0 if self.depths is None else self.depths.numel() * self.depths.element_size()
-        return self.images.numel() * self.images.element_size() + self.poses.numel() * self.poses.element_size() + depth
+        mask = 0 if self.masks is None else self.masks.numel()
+        return self.images.numel() * self.images.element_size() + self.poses.numel() * self.poses.element_size() + depth + mask
 
     def __len__(self) -> int:
         return self.total
@@ -113,6 +128,25 @@ class RayBank:
             raise RuntimeError("RayBank.gather_depth_into: idx must be int64 [B] and out float32 [B], contiguous, on the bank's device")
         _gather_depth(idx, out, self)
 
+    def gather_mask(self, idx: torch.Tensor) -> torch.Tensor:
+        """[B] float32: mask / 255 at the pixels of ray indices, bit-equal to indexing the `masks` array there and dividing.  idx as in
+        `gather`; an index outside [0, total) gives NaN, which losses.photometric_loss treats as an invalid ray."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        out = torch.empty(idx.shape[0], device=self.device, dtype=torch.float32)
+        self.gather_mask_into(idx, out)
+        return out
+
+    def gather_mask_into(self, idx: torch.Tensor, out: torch.Tensor) -> None:
+        """ego_ray_batch_gather_mask into a caller-owned buffer (idx [B] int64, out [B] float32, contiguous, on the bank's device): one
+        launch, no allocation - what GraphedTrainStep captures after the batch source's own launch."""
+        if self.masks is None:
+            raise ValueError("RayBank.gather_mask: this bank was built without masks")
+        _need_hip(idx, "RayBank.gather_mask")
+        if idx.dtype != torch.int64 or out.dtype != torch.float32 or idx.dim() != 1 or out.shape != idx.shape or not idx.is_contiguous() \
+                or not out.is_contiguous() or out.device != idx.device:
+            raise RuntimeError("RayBank.gather_mask_into: idx must be int64 [B] and out float32 [B], contiguous, on the bank's device")
+        _gather_mask(idx, out, self)
+
 
 def _need_hip(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
@@ -144,6 +178,12 @@ def _gather_depth(idx, out, bank):
     _lib.check(_lib.load().ego_ray_batch_gather_depth(C.byref(bank.struct), bank.depths.data_ptr(), int(bank.depths.dtype == torch.float16),
                                                       idx.data_ptr(), idx.shape[0], out.data_ptr(), _lib.stream_handle()),
                "ego_ray_batch_gather_depth")
+
+
+@_lib.device_guard
+def _gather_mask(idx, out, bank):
+    _lib.check(_lib.load().ego_ray_batch_gather_mask(C.byref(bank.struct), bank.masks.data_ptr(), idx.data_ptr(), idx.shape[0], out.data_ptr(),
+                                                     _lib.stream_handle()), "ego_ray_batch_gather_mask")
 
 
 @_lib.device_guard
@@ -227,14 +267,15 @@ class OmniBlenderDataset:
             raise ValueError(f"ray_bank: {path} is not an 8-bit RGB / RGBA image (array {a.dtype} {a.shape})")
         return a
 
-    def ray_bank(self, device=None, depths=None) -> RayBank:
+    def ray_bank(self, device=None, depths=None, masks=None) -> RayBank:
         """The training rays and colours as a device-resident `RayBank` (poses + uint8 images read from disk here): what
         `all_rays[idx]` / `all_rgbs[idx]` return, without materialising either array.  `depths` ([K,h,w] float32 / float16, see RayBank)
-        is passed through: the reference defines no depth file format, so none is read here."""
+        is passed through: the reference defines no depth file format, so none is read here.  `masks` ([K,h,w] uint8 / bool, see RayBank)
+        is passed through as well."""
         if self.is_stack:
             raise ValueError("ray_bank: the flat ray index space is that of is_stack=False")
         imgs = np.stack([self._load_image_u8(p) for p in self.image_paths], 0)
-        return RayBank(self.poses, imgs, self.img_wh, roi=self.roi, normalize=True, device=device or self.device, depths=depths)
+        return RayBank(self.poses, imgs, self.img_wh, roi=self.roi, normalize=True, device=device or self.device, depths=depths, masks=masks)
 
     def rays(self, idx: int, device=None) -> torch.Tensor:
         """[h*w, 6] rays of image `idx`: get_ray_directions_360 + normalisation + get_rays(roi) (dataset_omniblender.py:41-43,79),

@@ -7,6 +7,7 @@ the stored gradient (scaled by the incoming one) back in backward, so `total_los
     EgoNeRF.py:189-228 vector_comp_diffs, density_L1, TV_loss_density / TV_loss_app  (methods of model.EgoNeRF call in here)
     (not in the reference) Mip-NeRF 360's distortion regulariser                    -> distortion_loss
     train.py:249-251   depth_loss (with the gradient the reference's lacks)          -> depth_loss, expected_depth
+    train.py:261       the colour term, with weights, per-image exposure, robust kinds -> photometric_loss (csrc/ego_photo.hip)
 """
 from __future__ import annotations
 
@@ -252,3 +253,84 @@ def expected_depth(alpha: torch.Tensor, z: torch.Tensor, tail: Optional[torch.Te
     if a.dtype != torch.float32 or not a.is_contiguous():
         a = a.float().contiguous()
     return _expected_depth(a, z.detach().contiguous(), tail)
+
+
+_PHOTO_KINDS = {"l2": _lib.PHOTO_L2, "l1": _lib.PHOTO_L1, "huber": _lib.PHOTO_HUBER, "charbonnier": _lib.PHOTO_CHARBONNIER}
+_PHOTO_PARAM = {"huber": 0.1, "charbonnier": 1e-3}   # delta, epsilon: in units of colour, [0, 1]
+
+
+class _Photo(torch.autograd.Function):
+    @staticmethod
+    @_lib.device_guard
+    def forward(ctx, rgb: torch.Tensor, affine, target: torch.Tensor, weight, image, kind: int, param: float):
+        lib, st = _lib.load(), _lib.stream_handle()
+        c = rgb.detach()
+        if c.dtype != torch.float32 or not c.is_contiguous():
+            c = c.float().contiguous()
+        a = None if affine is None else affine.detach()
+        if a is not None and (a.dtype != torch.float32 or not a.is_contiguous()):
+            a = a.float().contiguous()
+        N, K = c.shape[0], (0 if a is None else a.shape[0])
+        value = torch.zeros(1, dtype=torch.float64, device=c.device)
+        g_rgb = torch.empty_like(c) if rgb.requires_grad else None
+        g_aff = torch.empty_like(a) if a is not None and affine.requires_grad else None
+        if image is not None and a is None:
+            K = 2 ** 31 - 1   # no table to stay inside: only negative indices are invalid
+        ws = torch.empty(lib.ego_photo_loss_workspace_bytes(N, K if g_aff is not None else 0) // 8, dtype=torch.float64, device=c.device)
+        _lib.check(lib.ego_photo_loss(c.data_ptr(), target.data_ptr(), _lib.ptr(weight), _lib.ptr(image), _lib.ptr(a), N, K, kind, param,
+                                      ws.data_ptr(), value.data_ptr(), _lib.ptr(g_rgb), _lib.ptr(g_aff), st), "ego_photo_loss")
+        if N == 0:   # the library's no-op writes nothing
+            g_aff = None if g_aff is None else torch.zeros_like(g_aff)
+        ctx.g = (g_rgb, g_aff)
+        return value.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g_rgb, g_aff = ctx.g
+        ctx.g = None
+        return (None if g_rgb is None else g_rgb * g_out), (None if g_aff is None else g_aff * g_out), None, None, None, None, None
+
+
+def _photo_args(what: str, rgb: torch.Tensor, target: torch.Tensor, weight, image, affine=None):
+    """The shape, dtype and device checks photometric_loss and exposure.fit_exposure share; -> (target, weight, image) detached,
+    contiguous, image as int32."""
+    if not torch.is_tensor(rgb) or rgb.dim() != 2 or rgb.shape[1] != 3 or not rgb.dtype.is_floating_point:
+        raise RuntimeError(f"{what}: rgb must be a floating-point [N, 3] tensor")
+    N = rgb.shape[0]
+    if not torch.is_tensor(target) or tuple(target.shape) != (N, 3) or target.dtype != torch.float32 or target.device != rgb.device:
+        raise RuntimeError(f"{what}: target must be a float32 [N, 3] tensor on rgb's device, N = {N}")
+    if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32
+                               or weight.device != rgb.device):
+        raise RuntimeError(f"{what}: weight must be a float32 [N] tensor on rgb's device, N = {N}")
+    if image is not None:
+        if not torch.is_tensor(image) or tuple(image.shape) != (N,) or image.dtype not in (torch.int32, torch.int64) or image.device != rgb.device:
+            raise RuntimeError(f"{what}: image must be an int32 or int64 [N] tensor on rgb's device, N = {N}")
+        image = image.detach().to(torch.int32).contiguous()
+    if affine is not None:
+        if not torch.is_tensor(affine) or affine.dim() != 3 or tuple(affine.shape[1:]) != (3, 2) or affine.shape[0] < 1 \
+                or affine.dtype != torch.float32 or affine.device != rgb.device:
+            raise RuntimeError(f"{what}: affine must be a float32 [K, 3, 2] tensor (gain, bias) on rgb's device, K >= 1")
+        if image is None:
+            raise ValueError(f"{what}: affine needs image (the image index of every ray)")
+    _require_cuda(rgb, what)
+    return target.detach().contiguous(), (None if weight is None else weight.detach().contiguous()), image
+
+
+def photometric_loss(rgb: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, image: Optional[torch.Tensor] = None,
+                     affine: Optional[torch.Tensor] = None, kind: str = "l2", param: Optional[float] = None) -> torch.Tensor:
+    """The colour term of train.py:261 for real captures (csrc/ego_photo.hip states the formula): (1 / 3W) sum_valid w_n sum_c rho(r_nc),
+    r = gain[image[n]] * rgb + bias[image[n]] - target, W = the sum of the valid rays' weights.  `kind`: "l2" (r^2), "l1" (|r|), "huber"
+    (r^2 / 2 up to |r| = param, linear beyond; param defaults to 0.1) or "charbonnier" (sqrt(r^2 + param^2) - param; 1e-3).  A ray is
+    valid iff its weight is finite and > 0, its target is finite and its image index lies inside `affine`; invalid rays add nothing and
+    get the gradient 0, and with no valid ray the loss and its gradients are 0.  With the defaults it is `torch.mean((rgb - target) ** 2)`
+    evaluated in float64.  rgb [N, 3]; target [N, 3] float32; weight [N] float32 (RayBank.gather_mask's output: 0 = ignore); image [N]
+    int32 / int64 (RayBank.image_of); affine [K, 3, 2] float32 (ExposureDeltas.affine()), which needs `image`.  Differentiable inputs: rgb
+    and affine.  Deterministic: the same inputs give the same bits."""
+    if kind not in _PHOTO_KINDS:
+        raise ValueError(f"photometric_loss: kind must be one of {sorted(_PHOTO_KINDS)}, not {kind!r}")
+    if param is None:
+        param = _PHOTO_PARAM.get(kind, 0.0)
+    elif kind in _PHOTO_PARAM and not (0.0 < float(param) < float("inf")):
+        raise ValueError(f"photometric_loss: {kind!r} needs a finite param > 0, not {param!r}")
+    target, weight, image = _photo_args("photometric_loss", rgb, target, weight, image, affine)
+    return _Photo.apply(rgb, affine, target, weight, image, _PHOTO_KINDS[kind], float(param))

@@ -26,9 +26,23 @@ def rgb_ssim(img0: torch.Tensor, img1: torch.Tensor, max_val, filter_size=11, fi
     return smap if return_map else float(total.item() / (Ho * Wo * 3))
 
 
-def psnr(img: torch.Tensor, gt: torch.Tensor) -> float:
-    """renderer.py:156-157."""
-    loss = torch.mean((img - gt) ** 2)
+def _pixel_mask(mask: torch.Tensor, img: torch.Tensor, what: str) -> torch.Tensor:
+    """[H, W] bool on img's device: the pixels with mask > 0"""
+    if not torch.is_tensor(mask) or tuple(mask.shape) != tuple(img.shape[:2]):
+        raise ValueError(f"{what}: mask must be a [H, W] = {tuple(img.shape[:2])} tensor")
+    m = mask.to(img.device) > 0
+    if not bool(m.any()):
+        raise ValueError(f"{what}: the mask leaves no pixel")
+    return m
+
+
+def psnr(img: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor = None) -> float:
+    """renderer.py:156-157.  With `mask` ([H, W], any dtype): the mean over the pixels with mask > 0 (exposure.align's protocol: the
+    photographer, the tripod and the seam are not scored)."""
+    if mask is None:
+        loss = torch.mean((img - gt) ** 2)
+    else:
+        loss = torch.mean(((img - gt) ** 2)[_pixel_mask(mask, img, "psnr")])
     return float(-10.0 * np.log(loss.item()) / np.log(10.0))
 
 
@@ -57,10 +71,15 @@ def ws_ssim(img0: torch.Tensor, img1: torch.Tensor, max_val=1.0, filter_size=11,
     return float(m.mean().item()), weighted_map_mean(m, w)
 
 
-def ws_psnr(img: torch.Tensor, gt: torch.Tensor, max_val=1.0) -> float:
+def ws_psnr(img: torch.Tensor, gt: torch.Tensor, max_val=1.0, mask: torch.Tensor = None) -> float:
     """Latitude-weighted PSNR of [H, W, 3] equirectangular images: 10 log10(max^2 / (sum_ij w_i (x - y)^2 / (3 W sum_i w_i))),
-    weights of extra/ws_ssim.py:12-14; reduces to renderer.py:156-157 for constant weights."""
+    weights of extra/ws_ssim.py:12-14; reduces to renderer.py:156-157 for constant weights.  With `mask` ([H, W], any dtype) both sums
+    run over the pixels with mask > 0 only: the weights are renormalised over them."""
     w = torch.as_tensor(ws_weights(img.shape[0]), dtype=torch.float64, device=img.device)
     d = img.to(torch.float64) - gt.to(img.device, torch.float64)
-    wmse = ((d * d).sum((1, 2)) * w).sum() / (w.sum() * img.shape[1] * img.shape[2])
+    if mask is None:
+        wmse = ((d * d).sum((1, 2)) * w).sum() / (w.sum() * img.shape[1] * img.shape[2])
+    else:
+        m = _pixel_mask(mask, img, "ws_psnr").to(torch.float64)
+        wmse = ((d * d).sum(2) * m * w[:, None]).sum() / ((m * w[:, None]).sum() * img.shape[2])
     return float(10.0 * np.log10(max_val ** 2 / wmse.item()))

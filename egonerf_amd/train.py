@@ -645,10 +645,20 @@ class GraphedTrainStep:
     the constructor takes an example `depth=` [B] and `step(rays, target, depth=...)` copies the iteration's targets in.  A loss_fn that
     names `depth` without either source is refused at construction.  The weight of train.py:276 is `sched.stepped(depth_lambda,
     depth_rate, depth_step_size, depth_end_iter)`; the term reads `model.last_train_z` like the distortion term:
-    `depth_loss(alpha, model.last_train_z, depth)` (tests/test_hip_depth_loss.py pins it against the eager loop)."""
+    `depth_loss(alpha, model.last_train_z, depth)` (tests/test_hip_depth_loss.py pins it against the eager loop).
+
+    Masks and exposure (losses.photometric_loss): the same opt-in by name.  A `loss_fn` with a parameter NAMED `weight` receives
+    `weight=self.weight`, a static float32 [B] buffer: with a `batch_source` whose bank has masks (RayBank(masks=...)) it is filled inside
+    the graph by `bank.gather_mask_into(self.idx, self.weight)`; host-fed, the constructor takes an example `weight=` [B] and
+    `step(rays, target, weight=...)` copies the iteration's in.  A parameter NAMED `image` receives `image=self.image`, a static int32
+    [B] buffer: with a `batch_source` it is `bank.image_of(self.idx)` written inside the graph; host-fed it comes through `image=` in the
+    same way.  Naming either without a source is refused at construction; a loss_fn that names neither runs exactly the calls it ran
+    before.  The parameters of an exposure.ExposureDeltas are an ordinary extra group of the FusedAdam the step drives:
+    `photometric_loss(rgb, gt, weight=weight, image=image, affine=deltas.affine())` (tests/test_hip_photo_loss.py pins it against the
+    eager loop)."""
 
     def __init__(self, model, optimizer, rays=None, target=None, render_kwargs=None, loss_fn=None, warmup=3, noise_fn=None, start_iteration=0,
-                 schedule_aware=None, batch_source=None, depth=None):
+                 schedule_aware=None, batch_source=None, depth=None, weight=None, image=None):
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs FusedAdam(capturable=True): the step count and lr schedule must live on the device")
         if render_kwargs is None:
@@ -666,6 +676,9 @@ class GraphedTrainStep:
                 raise ValueError("GraphedTrainStep: with a batch_source the depth targets come from its bank (RayBank(depths=...)); pass no depth")
             if getattr(batch_source.bank, "depths", None) is not None:
                 depth = torch.empty(batch_source.batch, device=dev0, dtype=torch.float32)
+            if weight is not None or image is not None:
+                raise ValueError("GraphedTrainStep: with a batch_source the weights come from its bank (RayBank(masks=...)) and the image "
+                                 "indices from its ray indices; pass no weight / image")
         elif rays is None or target is None:
             raise ValueError("GraphedTrainStep needs an example batch (rays, target) or a batch_source")
         if rays is not None and rays.requires_grad:
@@ -693,6 +706,40 @@ class GraphedTrainStep:
         if depth is not None and (depth.dim() != 1 or depth.shape[0] != rays.shape[0]):
             raise ValueError(f"GraphedTrainStep: depth must be [B] = [{rays.shape[0]}], got {tuple(depth.shape)}")
         self.depth = None if depth is None else depth.detach().to(rays.device).float().contiguous().clone()
+        # and for the per-ray weights and image indices of the photometric term; their buffers exist only when the loss_fn asks for them
+        try:
+            names = inspect.signature(self.loss_fn).parameters
+            self._loss_takes_weight, self._loss_takes_image = "weight" in names, "image" in names
+        except (TypeError, ValueError):
+            self._loss_takes_weight = self._loss_takes_image = False
+        B = rays.shape[0]
+        self.weight = self.image = None
+        if self._loss_takes_weight:
+            if batch_source is not None:
+                if getattr(batch_source.bank, "masks", None) is None:
+                    raise ValueError("GraphedTrainStep: loss_fn names `weight` but the batch_source's bank has no masks (RayBank(masks=...))")
+                self.weight = torch.empty(B, device=rays.device, dtype=torch.float32)
+            elif weight is None:
+                raise ValueError("GraphedTrainStep: loss_fn names `weight` but there is no weight source: pass weight= with a host-fed "
+                                 "batch, or a batch_source whose bank has masks")
+            else:
+                if weight.dim() != 1 or weight.shape[0] != B:
+                    raise ValueError(f"GraphedTrainStep: weight must be [B] = [{B}], got {tuple(weight.shape)}")
+                self.weight = weight.detach().to(rays.device).float().contiguous().clone()
+        elif weight is not None:
+            raise ValueError("GraphedTrainStep: weight= was given but loss_fn has no parameter named `weight`")
+        if self._loss_takes_image:
+            if batch_source is not None:
+                self.image = torch.empty(B, device=rays.device, dtype=torch.int32)
+            elif image is None:
+                raise ValueError("GraphedTrainStep: loss_fn names `image` but there is no image source: pass image= with a host-fed "
+                                 "batch, or a batch_source")
+            else:
+                if image.dim() != 1 or image.shape[0] != B or image.dtype not in (torch.int32, torch.int64):
+                    raise ValueError(f"GraphedTrainStep: image must be an int32 / int64 [B] = [{B}] tensor, got {image.dtype} {tuple(image.shape)}")
+                self.image = image.detach().to(rays.device, torch.int32).contiguous().clone()
+        elif image is not None:
+            raise ValueError("GraphedTrainStep: image= was given but loss_fn has no parameter named `image`")
         self.schedule = TrainSchedule(rays.device, start_iteration)
         # noise_fn(n_rays, n_samples, device) -> [n_rays, n_samples] in [0, 1): torch.rand by default; tests pin it
         self.noise_fn = noise_fn or (lambda n, m, dev: torch.rand(n, m, device=dev))
@@ -719,11 +766,19 @@ class GraphedTrainStep:
             self.source.sample_into(self.idx, self.rays, self.target)
             if self.depth is not None:
                 self.source.bank.gather_depth_into(self.idx, self.depth)
+            if self.weight is not None:
+                self.source.bank.gather_mask_into(self.idx, self.weight)
+            if self.image is not None:
+                self.image.copy_(self.source.bank.image_of(self.idx))
         # the is_train noise comes from the device generator (graph-safe: every replay draws new numbers)
         jitter = self.noise_fn(N, kw["n_coarse"], dev)
         u = self.noise_fn(N, kw["n_fine"], dev) if kw.get("resampling") else None
         rgb, _depth, _bg, _env, alpha = self.model(self.rays, is_train=True, jitter=jitter, u=u, **kw)
         extra = dict(depth=self.depth) if self._loss_takes_depth else {}
+        if self._loss_takes_weight:
+            extra["weight"] = self.weight
+        if self._loss_takes_image:
+            extra["image"] = self.image
         loss = self.loss_fn(rgb, self.target, alpha, self.schedule, **extra) if self._loss_takes_schedule else self.loss_fn(rgb, self.target, alpha, **extra)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -735,9 +790,9 @@ class GraphedTrainStep:
             self.source.counter.add_(1)
         return loss.detach()
 
-    def __call__(self, rays=None, target=None, depth=None):
+    def __call__(self, rays=None, target=None, depth=None, weight=None, image=None):
         if self.source is not None:
-            if rays is not None or target is not None or depth is not None:
+            if rays is not None or target is not None or depth is not None or weight is not None or image is not None:
                 raise ValueError("this GraphedTrainStep draws its batches from its batch_source inside the graph: call step() without arguments")
         elif rays is None or target is None:
             raise ValueError("this GraphedTrainStep was built without a batch_source: call step(rays, target)")
@@ -752,6 +807,13 @@ class GraphedTrainStep:
                 self.depth.copy_(depth, non_blocking=True)
             elif self._loss_takes_depth:
                 raise ValueError("this GraphedTrainStep's loss_fn takes depth targets: call step(rays, target, depth=...)")
+            for name, given, buf in (("weight", weight, self.weight), ("image", image, self.image)):
+                if given is not None:
+                    if buf is None:
+                        raise ValueError(f"this GraphedTrainStep's loss_fn takes no `{name}`: it was built without one")
+                    buf.copy_(given, non_blocking=True)
+                elif buf is not None:
+                    raise ValueError(f"this GraphedTrainStep's loss_fn takes `{name}`: call step(rays, target, {name}=...)")
         self.graph.replay()
         self.iterations += 1
         # the replayed optimiser wrote the parameters through raw pointers: tell autograd and the model's packed-weight cache

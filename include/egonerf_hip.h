@@ -250,6 +250,11 @@ int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, 
  * (ego_ray_depth_loss then treats that ray as invalid).  The bank's images may be NULL.  B == 0 is a no-op. */
 int ego_ray_batch_gather_depth(const ego_ray_bank* bank, const void* depth, int32_t is_half, const int64_t* idx, int64_t B, float* out,
                                void* stream);
+/* Per-pixel masks next to a bank (append-only addition, EGO_ABI_VERSION stays 17; ego_ray_bank itself does not change): mask [K][H][W]
+ * uint8 dev, one value per pixel of the bank's full images, 0 = ignore, 255 = full weight.  out[i] (float32 [B] dev) = mask / 255 of the
+ * pixel idx[i] names (one correctly rounded division).  A row whose index is outside [0, total) reads nothing and is filled with NaN
+ * (ego_photo_loss then treats that ray as invalid), as with depth.  The bank's images may be NULL.  B == 0 is a no-op.  One launch. */
+int ego_ray_batch_gather_mask(const ego_ray_bank* bank, const uint8_t* mask, const int64_t* idx, int64_t B, float* out, void* stream);
 
 /* ---- camera paths (csrc/ego_camera.hip; append-only additions, EGO_ABI_VERSION stays 17: no existing symbol, struct or argument list
  * changed): the two ends of evaluation_path (renderer.py:199-255) and of the tail of evaluation (renderer.py:141-174) ---- */
@@ -739,6 +744,42 @@ int64_t ego_ray_depth_loss_workspace_bytes(int64_t N);
 int ego_ray_depth_loss(const float* alpha, int32_t alpha_stride, const float* z, const float* target, const float* tail, int64_t N, int32_t S,
                        float near_, float far_, int32_t space, int32_t kind, void* workspace, double* value, float* g_alpha, float* pred,
                        void* stream);
+/* The photometric term for real captures (csrc/ego_photo.hip; append-only addition, EGO_ABI_VERSION stays 17): train.py:261's
+ * torch.mean((rgb_map - rgb_train) ** 2) with a per-image affine colour map, a per-ray weight and robust kinds.  With k = image[n]
+ * (0 without image), c'_nc = gain[k][c] rgb_nc + bias[k][c] (c' = rgb without affine) and r_nc = c'_nc - target_nc:
+ *   EGO_PHOTO_L2: rho = r^2      EGO_PHOTO_HUBER: rho = r^2 / 2 for |r| <= param, else param (|r| - param / 2)
+ *   EGO_PHOTO_L1: rho = |r|      EGO_PHOTO_CHARBONNIER: rho = sqrt(r^2 + param^2) - param
+ * A ray is valid iff its weight is finite and > 0 (weight NULL: 1), its three target channels are finite, and 0 <= image[n] < K when image
+ * is given.  A non-finite rgb of a valid ray is not hidden: it makes the value non-finite, as the MSE would.  W = sum_valid w_n, counted
+ * on the device:
+ *   value   += (1 / 3W) sum_valid w_n sum_c rho(r_nc)
+ *   g_rgb_nc = w_n rho'(r_nc) gain[k][c] / 3W, exactly 0 on an invalid ray; the L1 derivative is 0 at r = 0
+ *   g_affine[k][c] = (sum_{n in k, valid} w_n rho'(r_nc) rgb_nc / 3W, the same sum without rgb_nc): d value / d (gain, bias), exactly 0
+ *                    for an image no valid ray belongs to
+ * With W = 0 nothing is added to value and every gradient element is exactly 0.  Without weight, image and affine, EGO_PHOTO_L2 is the
+ * reference's MSE evaluated in float64.
+ * rgb [N][3], target [N][3], weight [N] or NULL: float32 dev; image [N] int32 dev or NULL; affine [K][3][2] float32 dev (gain, bias) or
+ * NULL (identity); all constant.  Outputs, each optional: `value`, a float64 device scalar zeroed by the caller; g_rgb [N][3] and g_affine
+ * [K][3][2] float32, every element WRITTEN.  `workspace`: caller-owned, 8-byte aligned, ego_photo_loss_workspace_bytes(N, K) bytes
+ * (K counts only when g_affine is asked for: pass 0 otherwise), overwritten, no need to clear it.  All arithmetic is float64; every sum has
+ * a fixed order (per-block partials joined in index order; per image, one block per slice of 2048 rays scanning the slice's image indices,
+ * the slices joined in slice order: N K index reads in all), no float atomics: repeated calls return the same bits, and so do value-only,
+ * gradient-only and joint calls.  Refuses, before any launch: an unknown kind, a param that is not
+ * finite and > 0 for HUBER / CHARBONNIER (unused otherwise), affine or g_affine without image, K < 1 with either, null rgb, target or
+ * workspace, no output asked for.  N == 0 is a no-op.  At most three launches, no allocation, no synchronisation: it can be captured
+ * into a hipGraph. */
+enum { EGO_PHOTO_L2 = 0, EGO_PHOTO_L1 = 1, EGO_PHOTO_HUBER = 2, EGO_PHOTO_CHARBONNIER = 3 };
+int64_t ego_photo_loss_workspace_bytes(int64_t N, int32_t K);
+int ego_photo_loss(const float* rgb, const float* target, const float* weight, const int32_t* image, const float* affine, int64_t N, int32_t K,
+                   int32_t kind, float param, void* workspace, double* value, float* g_rgb, float* g_affine, void* stream);
+/* The weighted least-squares affine colour map per image and channel, in closed form: for each (k, c), over the valid rays of image k
+ * (ego_photo_loss's rule; image NULL: one image, K must be 1), the (gain, bias) that minimise sum w (gain rgb + bias - target)^2, from the
+ * float64 moments W_k, sum w c, sum w t, sum w c^2, sum w c t (one block per image, ego_photo_loss's scan over the whole batch).  An image with
+ * W_k = 0 gets (1, 0).  A system is degenerate iff W sum w c^2 - (sum w c)^2 <= 1e-9 W sum w c^2 (all colours equal; a definition, not a
+ * tolerance) and gets gain 1, bias mean_w(t) - mean_w(c).  Writes affine [K][3][2] float32 dev and, optionally, Wk [K] float64 dev.
+ * Repeated calls return the same bits.  Refuses K < 1, image NULL with K != 1, null affine, null rgb or target with N > 0.  One launch. */
+int ego_photo_fit(const float* rgb, const float* target, const float* weight, const int32_t* image, int64_t N, int32_t K, float* affine,
+                  double* Wk, void* stream);
 /* coordinates.py:27-39 and :226-266 (up_sampling_VM): bilinear, align_corners=True, zero-padded resample of a table at
  * per-axis normalised positions xs [W2], ys [H2] (device) -> dst [H2][W2][C]. */
 int ego_resample_table(const float* src, int32_t C, int32_t H, int32_t W, const float* xs, const float* ys, int32_t H2, int32_t W2,
