@@ -148,6 +148,7 @@ PROTOTYPES = {
     "ego_erp_rays": (C.c_int, [I32, I32, I32, I32, C.POINTER(C.c_float), I32, P, P]),
     "ego_ray_batch_gather": (C.c_int, [C.POINTER(RayBankStruct), P, I64, P, P, P]),
     "ego_ray_batch_sample": (C.c_int, [C.POINTER(RayBankStruct), I32, C.c_uint64, P, P, I64, P, P, P, P]),
+    "ego_ray_batch_sample_patches": (C.c_int, [C.POINTER(RayBankStruct), C.c_uint64, P, I64, I32, I32, I32, I64, P, P, P, P]),
     "ego_ray_batch_gather_depth": (C.c_int, [C.POINTER(RayBankStruct), P, I32, P, I64, P, P]),
     "ego_ray_batch_gather_mask": (C.c_int, [C.POINTER(RayBankStruct), P, P, I64, P, P]),
     "ego_camera_rays": (C.c_int, [I32, I32, I32, F32, F32, F32, F32, I32, P, I64, I64, P, P]),
@@ -233,6 +234,8 @@ PROTOTYPES = {
     "ego_photo_loss_workspace_bytes": (I64, [I64, I32]),
     "ego_photo_loss": (C.c_int, [P, P, P, P, P, I64, I32, I32, F32, P, P, P, P, P]),
     "ego_photo_fit": (C.c_int, [P, P, P, P, I64, I32, P, P, P]),
+    "ego_patch_ssim_workspace_bytes": (I64, [I64, I32, I32]),
+    "ego_patch_ssim": (C.c_int, [P, P, P, I64, I32, I32, I32, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P]),
     "ego_resample_table": (C.c_int, [P, I32, I32, I32, P, P, I32, I32, P, P]),
     "ego_adam_step": (C.c_int, [C.POINTER(AdamTensor), I32, F32, F32, F32, I32, P]),
     "ego_adam_step_graph": (C.c_int, [C.POINTER(AdamTensor), I32, F32, F32, F32, C.c_double, P, P]),

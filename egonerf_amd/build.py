@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libegonerf_hip.so")
 SOURCES = ["ego_stages.hip", "ego_march.hip", "ego_resample.hip", "ego_runtime.hip", "ego_pack.hip", "ego_shade.hip", "ego_train.hip", "ego_render.hip", "ego_reg.hip", "ego_metrics.hip", "ego_wgrad.hip", "ego_generic.hip", "ego_generic_train.hip", "ego_generic_march.hip", "ego_selftest.hip", "ego_scatter_sorted.hip",
-           "ego_scatter_sort.hip", "ego_stage_grad.hip", "ego_compact.hip", "ego_batch.hip", "ego_camera.hip", "ego_msi.hip", "ego_ray_grad.hip", "ego_dense.hip", "ego_geometry.hip", "ego_mesh.hip", "ego_photo.hip"]
+           "ego_scatter_sort.hip", "ego_stage_grad.hip", "ego_compact.hip", "ego_batch.hip", "ego_camera.hip", "ego_msi.hip", "ego_ray_grad.hip", "ego_dense.hip", "ego_geometry.hip", "ego_mesh.hip", "ego_photo.hip", "ego_patch_loss.hip"]
 HEADERS = ["ego_device.h", "ego_host.h", "ego_tuned.h", "variants.h", "ego_generic.h", "ego_generic_dev.h", "ego_sorted_geom.h", "ego_vm_grad.h", "ego_march.h", "ego_density.h", os.path.join("..", "..", "include", "egonerf_hip.h")]
 
 
@@ -107,13 +107,15 @@ def shipped_isa_report(lib_path: str | None = None) -> dict:
 # ego_msi.hip dot products of that shape plus bilinear weights applied to four-channel texels; ego_ray_grad.hip holds the
 # interpolation-weight arithmetic itself, once more with the weights' derivatives next to them, and ego_geometry.hip the same arithmetic
 # again (ego_vm_grad.h), as does ego_mesh.hip (the point gradients, and the lattice field's density_lookup); ego_photo.hip holds
-# per-channel multiply-add triples (gain * rgb + bias over three channels) of the shape the vectoriser pairs.
+# per-channel multiply-add triples (gain * rgb + bias over three channels) of the shape the vectoriser pairs, and ego_patch_loss.hip the five
+# window moments and the three coefficient fields of the structural term: tap-weighted sums taken side by side, the same shape.
 EXTRA_FLAGS = {"ego_shade.hip": ["-fno-slp-vectorize"], "ego_pack.hip": ["-fno-slp-vectorize"], "ego_train.hip": ["-fno-slp-vectorize"],
                "ego_scatter_sorted.hip": ["-fno-slp-vectorize"], "ego_scatter_sort.hip": ["-fno-slp-vectorize"],
                "ego_stage_grad.hip": ["-fno-slp-vectorize"], "ego_batch.hip": ["-fno-slp-vectorize"],
                "ego_camera.hip": ["-fno-slp-vectorize"], "ego_msi.hip": ["-fno-slp-vectorize"],
                "ego_ray_grad.hip": ["-fno-slp-vectorize"], "ego_geometry.hip": ["-fno-slp-vectorize"],
-               "ego_mesh.hip": ["-fno-slp-vectorize"], "ego_photo.hip": ["-fno-slp-vectorize"]}
+               "ego_mesh.hip": ["-fno-slp-vectorize"], "ego_photo.hip": ["-fno-slp-vectorize"],
+               "ego_patch_loss.hip": ["-fno-slp-vectorize"]}
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC"]
 
 

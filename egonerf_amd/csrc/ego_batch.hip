@@ -127,6 +127,51 @@ __global__ __launch_bounds__(256) void k_ray_batch_sample(BankArgs b, int mode, 
   if (rays || rgb) gather_row(b, id, i, rays, rgb);
 }
 
+// key tweaks of the patch mode's two Philox streams (xor into the low key word): EGO_BATCH_THETA keys with the seed itself and the same
+// counter words, so the tweak is what keeps the three streams apart
+constexpr uint32_t kPatchKeyTweak = 0x50415443u, kPatchRandomKeyTweak = 0x52414E44u;   // "PATC", "RAND"
+
+struct PatchPlan {
+  int64_t n_patch_rows;      // P * ph * pw
+  int32_t ph, pw, stride;
+  int32_t row_origins;       // n_rows - (ph - 1) * stride
+  int32_t col_origins;       // n_cols when the panorama wraps, else n_cols - (pw - 1) * stride
+  int32_t wrap;
+};
+
+// rows [0, P ph pw): row p ph pw + a pw + b = pixel (row0_p + a stride, col0_p + b stride) of image img_p, the origin drawn once per patch
+// (every thread of a patch computes the same three integers); the rows behind them: independent uniform pixels
+__global__ __launch_bounds__(256) void k_ray_batch_sample_patches(BankArgs b, PatchPlan pl, uint32_t seed_lo, uint32_t seed_hi,
+                                                                  const int64_t* __restrict__ counter, int64_t B, int64_t* __restrict__ idx,
+                                                                  float* __restrict__ rays, float* __restrict__ rgb) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  const uint64_t c = (uint64_t)*counter;
+  int img, row, col;
+  if (i < pl.n_patch_rows) {
+    const int64_t per = (int64_t)pl.ph * pl.pw;
+    const uint64_t p = (uint64_t)(i / per);
+    const int64_t e = i - (int64_t)p * per;
+    const int pa = (int)(e / pl.pw), pb = (int)(e - (int64_t)pa * pl.pw);
+    uint32_t x[4] = {(uint32_t)p, (uint32_t)(p >> 32), (uint32_t)c, (uint32_t)(c >> 32)};
+    philox4x32_10(x, seed_lo ^ kPatchKeyTweak, seed_hi);
+    img = (int)(((uint64_t)x[0] * (uint32_t)b.K) >> 32);
+    row = (int)(((uint64_t)x[1] * (uint32_t)pl.row_origins) >> 32) + pa * pl.stride;
+    col = (int)(((uint64_t)x[2] * (uint32_t)pl.col_origins) >> 32) + pb * pl.stride;
+    if (pl.wrap) col %= b.n_cols;   // the panorama's seam: column n_cols is column 0
+  } else {
+    const uint64_t r = (uint64_t)(i - pl.n_patch_rows);
+    uint32_t x[4] = {(uint32_t)r, (uint32_t)(r >> 32), (uint32_t)c, (uint32_t)(c >> 32)};
+    philox4x32_10(x, seed_lo ^ kPatchRandomKeyTweak, seed_hi);
+    img = (int)(((uint64_t)x[0] * (uint32_t)b.K) >> 32);
+    col = (int)(((uint64_t)x[1] * (uint32_t)b.n_cols) >> 32);
+    row = (int)(((uint64_t)x[2] * (uint32_t)b.n_rows) >> 32);
+  }
+  const int64_t id = (int64_t)img * b.per_img + (int64_t)row * b.n_cols + col;
+  idx[i] = id;
+  if (rays || rgb) gather_row(b, id, i, rays, rgb);
+}
+
 // the depth target of one row of all_rays: the pixel gather_row reads the colour of, from a [K][H][W] float32 / float16 array
 __global__ __launch_bounds__(256) void k_ray_batch_gather_depth(BankArgs b, const void* __restrict__ depth, int is_half,
                                                                 const int64_t* __restrict__ idx, int64_t B, float* __restrict__ out) {
@@ -239,6 +284,33 @@ int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, 
   k_ray_batch_sample<<<nblk(B, 256), 256, 0, (hipStream_t)stream>>>(b, mode, (uint32_t)seed, (uint32_t)(seed >> 32), counter, row_cdf, B,
                                                                    per_epoch, half, idx, rays, rgb);
   return ego_launch_status("k_ray_batch_sample");
+}
+
+int ego_ray_batch_sample_patches(const ego_ray_bank* bank, uint64_t seed, const int64_t* counter, int64_t P, int32_t ph, int32_t pw,
+                                 int32_t stride, int64_t n_random, int64_t* idx, float* rays, float* rgb, void* stream) {
+  EGO_TRACE("ego_ray_batch_sample_patches");
+  BankArgs b;
+  if (const int e = check_bank(bank, rgb != nullptr, "ray_batch_sample_patches", &b)) return e;
+  EGO_REQUIRE(P >= 0 && n_random >= 0, "ray_batch_sample_patches: P < 0 or n_random < 0");
+  EGO_REQUIRE(ph >= 1 && pw >= 1 && stride >= 1, "ray_batch_sample_patches: ph, pw and stride must be >= 1");
+  const int64_t ext_rows = (int64_t)(ph - 1) * stride + 1, ext_cols = (int64_t)(pw - 1) * stride + 1;
+  if (ext_rows > b.n_rows || ext_cols > b.n_cols)
+    return ego_fail(EGO_E_BADARG, "ray_batch_sample_patches: a patch of %lld x %lld pixels ((ph - 1) stride + 1, (pw - 1) stride + 1) does not "
+                                  "fit the bank's window of %d x %d", (long long)ext_rows, (long long)ext_cols, b.n_rows, b.n_cols);
+  EGO_REQUIRE(P <= (((int64_t)1 << 62) - n_random) / ((int64_t)ph * pw), "ray_batch_sample_patches: P ph pw + n_random must stay below 2^62");
+  const int64_t n_patch_rows = P * ph * pw, B = n_patch_rows + n_random;
+  if (B == 0) return EGO_OK;
+  EGO_REQUIRE(counter && idx, "ray_batch_sample_patches: null counter or idx");
+  EGO_REQUIRE((B + 255) / 256 < ((int64_t)1 << 31), "ray_batch_sample_patches: B / 256 must stay below 2^31 blocks");
+  PatchPlan pl;
+  pl.n_patch_rows = n_patch_rows;
+  pl.ph = ph; pl.pw = pw; pl.stride = stride;
+  pl.wrap = b.c0 == 0 && b.n_cols == b.W;
+  pl.row_origins = (int32_t)(b.n_rows - (ext_rows - 1));
+  pl.col_origins = pl.wrap ? b.n_cols : (int32_t)(b.n_cols - (ext_cols - 1));
+  k_ray_batch_sample_patches<<<nblk(B, 256), 256, 0, (hipStream_t)stream>>>(b, pl, (uint32_t)seed, (uint32_t)(seed >> 32), counter, B, idx, rays,
+                                                                           rgb);
+  return ego_launch_status("k_ray_batch_sample_patches");
 }
 
 }  // extern "C"

@@ -47,6 +47,20 @@ inline int ego_launch_status(const char* kernel) {
   return EGO_OK;
 }
 
+// utils.py:117-121: the `filter_size` normalised Gaussian taps of rgb_ssim's window (ego_rgb_ssim and ego_patch_ssim both take theirs
+// from here); filt must hold filter_size doubles
+inline void ego_ssim_taps(int filter_size, double filter_sigma, double* filt) {
+  const int hw = filter_size / 2;
+  const double shift = (2 * hw - filter_size + 1) / 2.0;
+  double tot = 0.0;
+  for (int i = 0; i < filter_size; ++i) {
+    const double f = ((double)(i - hw) + shift) / filter_sigma;
+    filt[i] = exp(-0.5 * f * f);
+    tot += filt[i];
+  }
+  for (int i = 0; i < filter_size; ++i) filt[i] /= tot;
+}
+
 // compute units of the CURRENT device (what sizes a launch by wave slots: the march's split, the sorted walk's grid); queried once per
 // device; racing first calls store the same value
 inline int device_cus() {

@@ -95,16 +95,7 @@ int ego_rgb_ssim(const float* img0, const float* img1, int32_t H, int32_t W, dou
   EGO_REQUIRE(img0 && img1 && (sum || ssim_map), "rgb_ssim: null argument");
   SsimArgs a{};
   a.img0 = img0; a.img1 = img1; a.H = H; a.W = W; a.fs = filter_size; a.sum = sum; a.map = ssim_map;
-  // utils.py:117-121
-  const int hw = filter_size / 2;
-  const double shift = (2 * hw - filter_size + 1) / 2.0;
-  double tot = 0.0;
-  for (int i = 0; i < filter_size; ++i) {
-    const double f = ((double)(i - hw) + shift) / filter_sigma;
-    a.filt[i] = exp(-0.5 * f * f);
-    tot += a.filt[i];
-  }
-  for (int i = 0; i < filter_size; ++i) a.filt[i] /= tot;
+  ego_ssim_taps(filter_size, filter_sigma, a.filt);   // utils.py:117-121
   a.c1 = (k1 * max_val) * (k1 * max_val);
   a.c2 = (k2 * max_val) * (k2 * max_val);
   const int Ho = H - filter_size + 1, Wo = W - filter_size + 1;

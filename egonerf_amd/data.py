@@ -167,6 +167,61 @@ def ray_batch_sample(idx: torch.Tensor, rays: Optional[torch.Tensor], rgb: Optio
     _sample(idx, rays, rgb, bank, mode, seed, counter, row_cdf)
 
 
+def ray_batch_sample_patches(idx: torch.Tensor, rays: Optional[torch.Tensor], rgb: Optional[torch.Tensor], bank: RayBank, seed: int,
+                             counter: torch.Tensor, patches: int, patch: Sequence[int], stride: int, n_random: int) -> None:
+    """ego_ray_batch_sample_patches into caller-owned buffers: idx [patches * ph * pw + n_random] int64, rays / rgb float32 or None;
+    counter as in `ray_batch_sample`."""
+    _need_hip(idx, "patch batch sampling")
+    if idx.shape[0] != patches * patch[0] * patch[1] + n_random:
+        raise RuntimeError(f"patch batch sampling: idx holds {idx.shape[0]} rows, the batch {patches * patch[0] * patch[1] + n_random}")
+    _sample_patches(idx, rays, rgb, bank, seed, counter, patches, patch, stride, n_random)
+
+
+def check_patch_shape(what: str, bank: RayBank, patch, stride) -> tuple:
+    """(ph, pw, stride) as ints, refused unless each is >= 1 and the patch's extent fits the bank's window."""
+    if not (isinstance(patch, (tuple, list)) and len(patch) == 2):
+        raise ValueError(f"{what}: patch must be (ph, pw), not {patch!r}")
+    ph, pw, stride = int(patch[0]), int(patch[1]), int(stride)
+    if ph < 1 or pw < 1 or stride < 1:
+        raise ValueError(f"{what}: ph, pw and stride must be >= 1 (patch {ph} x {pw}, stride {stride})")
+    ext = ((ph - 1) * stride + 1, (pw - 1) * stride + 1)
+    if ext[0] > bank.n_rows or ext[1] > bank.n_cols:
+        raise ValueError(f"{what}: a patch of {ext[0]} x {ext[1]} pixels does not fit the bank's window of {bank.n_rows} x {bank.n_cols}")
+    return ph, pw, stride
+
+
+def patch_indices(bank: RayBank, img, row0, col0, patch: Sequence[int], stride: int = 1) -> torch.Tensor:
+    """The index block of patches with given origins, in DevicePatchSampler's layout: [P * ph * pw] int64 (on img's device), row
+    p ph pw + a pw + b = pixel (row0[p] + a stride, col0[p] + b stride) of image img[p] in the bank's index space.  img, row0, col0: [P]
+    integer tensors (or sequences), rows and columns counted inside the bank's window.  When the window spans the full width the columns
+    wrap (modulo n_cols) and col0 may be any column; otherwise the patch must fit.  Pure torch: works on any device."""
+    ph, pw, stride = check_patch_shape("patch_indices", bank, patch, stride)
+    img, row0, col0 = (torch.as_tensor(t, dtype=torch.int64) for t in (img, row0, col0))
+    if img.dim() != 1 or row0.shape != img.shape or col0.shape != img.shape:
+        raise ValueError("patch_indices: img, row0 and col0 must be [P] integer tensors of one length")
+    row0, col0 = row0.to(img.device), col0.to(img.device)
+    wrap = bank.c0 == 0 and bank.n_cols == bank.W
+    if img.numel():
+        last_col = bank.n_cols - 1 if wrap else bank.n_cols - ((pw - 1) * stride + 1)
+        if int(img.min()) < 0 or int(img.max()) >= bank.K or int(row0.min()) < 0 or int(row0.max()) > bank.n_rows - ((ph - 1) * stride + 1) \
+                or int(col0.min()) < 0 or int(col0.max()) > last_col:
+            raise ValueError("patch_indices: an origin lies outside the bank (image in [0, K), rows so that the patch fits, columns so "
+                             "that it fits or, on a full-width window, any column)")
+    rows = row0[:, None] + torch.arange(ph, device=img.device) * stride                 # [P, ph]
+    cols = col0[:, None] + torch.arange(pw, device=img.device) * stride                 # [P, pw]
+    if wrap:
+        cols = cols % bank.n_cols
+    idx = img[:, None, None] * (bank.n_rows * bank.n_cols) + rows[:, :, None] * bank.n_cols + cols[:, None, :]
+    return idx.reshape(-1)
+
+
+@_lib.device_guard
+def _sample_patches(idx, rays, rgb, bank, seed, counter, patches, patch, stride, n_random):
+    _lib.check(_lib.load().ego_ray_batch_sample_patches(C.byref(bank.struct), int(seed), counter.data_ptr(), int(patches), int(patch[0]),
+                                                        int(patch[1]), int(stride), int(n_random), idx.data_ptr(), _lib.ptr(rays),
+                                                        _lib.ptr(rgb), _lib.stream_handle()), "ego_ray_batch_sample_patches")
+
+
 @_lib.device_guard
 def _gather(idx, rays, rgb, bank):
     _lib.check(_lib.load().ego_ray_batch_gather(C.byref(bank.struct), idx.data_ptr(), idx.shape[0], _lib.ptr(rays), _lib.ptr(rgb),

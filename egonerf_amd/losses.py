@@ -8,6 +8,7 @@ the stored gradient (scaled by the incoming one) back in backward, so `total_los
     (not in the reference) Mip-NeRF 360's distortion regulariser                    -> distortion_loss
     train.py:249-251   depth_loss (with the gradient the reference's lacks)          -> depth_loss, expected_depth
     train.py:261       the colour term, with weights, per-image exposure, robust kinds -> photometric_loss (csrc/ego_photo.hip)
+    (not in the reference) 1 - mean SSIM over the windows of patch batches, with its gradient -> patch_ssim_loss (csrc/ego_patch_loss.hip)
 """
 from __future__ import annotations
 
@@ -334,3 +335,72 @@ def photometric_loss(rgb: torch.Tensor, target: torch.Tensor, weight: Optional[t
         raise ValueError(f"photometric_loss: {kind!r} needs a finite param > 0, not {param!r}")
     target, weight, image = _photo_args("photometric_loss", rgb, target, weight, image, affine)
     return _Photo.apply(rgb, affine, target, weight, image, _PHOTO_KINDS[kind], float(param))
+
+
+class _PatchSsim(torch.autograd.Function):
+    @staticmethod
+    @_lib.device_guard
+    def forward(ctx, rgb: torch.Tensor, target: torch.Tensor, weight, P: int, ph: int, pw: int, fs: int, sigma: float, max_val: float, k1: float,
+                k2: float):
+        lib, st = _lib.load(), _lib.stream_handle()
+        c = rgb.detach().contiguous()   # float32 [B, 3]: patch_ssim_loss has checked
+        value = torch.zeros(1, dtype=torch.float64, device=c.device)
+        n = P * ph * pw
+        g = None
+        if rgb.requires_grad:
+            g = torch.empty_like(c)
+            g[n:].zero_()   # the rows behind the patches take no part: exactly 0
+        ws = torch.empty(max(lib.ego_patch_ssim_workspace_bytes(P, ph, pw) // 8, 1), dtype=torch.float64, device=c.device)
+        _lib.check(lib.ego_patch_ssim(c.data_ptr(), target.data_ptr(), _lib.ptr(weight), P, ph, pw, fs, sigma, max_val, k1, k2, ws.data_ptr(),
+                                      value.data_ptr(), _lib.ptr(g), st), "ego_patch_ssim")
+        ctx.g = g
+        return value.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g = ctx.g
+        ctx.g = None
+        return (None if g is None else (g * g_out).to(g.dtype)), None, None, None, None, None, None, None, None, None, None
+
+
+def patch_ssim_loss(rgb: torch.Tensor, target: torch.Tensor, patch: Sequence[int], n_patches: Optional[int] = None,
+                    weight: Optional[torch.Tensor] = None, filter_size: int = 7, filter_sigma: float = 1.5, max_val: float = 1.0,
+                    k1: float = 0.01, k2: float = 0.03) -> torch.Tensor:
+    """The structural term on patch batches (not in the reference; csrc/ego_patch_loss.hip states the formulas): 1 - the mean SSIM over
+    the 'valid' Gaussian windows (metrics.rgb_ssim's taps, without its rounding guards) of `n_patches` patches of patch = (ph, pw) pixels,
+    a float64 device scalar.  rgb, target [B, 3]: the first n_patches * ph * pw rows are the patches, row p ph pw + a pw + b = pixel (a, b)
+    of patch p (sampler.DevicePatchSampler's layout, data.patch_indices'); n_patches=None takes all of B, which must then divide evenly.
+    Later rows are ignored and get exactly zero gradient.  weight [B] float32 (RayBank.gather_mask's output) is a gate: a window is valid
+    iff every pixel under it has a finite weight > 0 and a finite target; invalid windows add nothing, pixels under no valid window get
+    the gradient 0, and with no valid window the loss and its gradient are 0.  Envelope: 1 <= filter_size <= 15, filter_size <= ph, pw
+    <= 32.  rgb (float32) is the differentiable input; its gradient is float32.  As with the other terms here the gradient is computed in the
+    forward call and handed out once: a second backward through the same node (retain_graph) gets none.  Deterministic: the same inputs
+    give the same bits."""
+    what = "patch_ssim_loss"
+    if not (isinstance(patch, (tuple, list)) and len(patch) == 2):
+        raise ValueError(f"{what}: patch must be (ph, pw), not {patch!r}")
+    ph, pw, fs = int(patch[0]), int(patch[1]), int(filter_size)
+    if not 1 <= fs <= 15:
+        raise ValueError(f"{what}: filter_size must be 1..15, not {filter_size!r}")
+    if not (fs <= ph <= 32 and fs <= pw <= 32):
+        raise ValueError(f"{what}: a patch must cover the filter and be at most 32 x 32 (filter_size {fs}, patch {ph} x {pw})")
+    if not (0.0 < float(filter_sigma) < float("inf")):
+        raise ValueError(f"{what}: filter_sigma must be finite and > 0, not {filter_sigma!r}")
+    if not torch.is_tensor(rgb) or rgb.dim() != 2 or rgb.shape[1] != 3 or rgb.dtype != torch.float32:
+        raise RuntimeError(f"{what}: rgb must be a float32 [B, 3] tensor")
+    B = rgb.shape[0]
+    if not torch.is_tensor(target) or tuple(target.shape) != (B, 3) or target.dtype != torch.float32 or target.device != rgb.device:
+        raise RuntimeError(f"{what}: target must be a float32 [B, 3] tensor on rgb's device, B = {B}")
+    if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != (B,) or weight.dtype != torch.float32
+                               or weight.device != rgb.device):
+        raise RuntimeError(f"{what}: weight must be a float32 [B] tensor on rgb's device, B = {B}")
+    if n_patches is None:
+        if B % (ph * pw) != 0:
+            raise ValueError(f"{what}: {B} rows are not a whole number of {ph} x {pw} patches; pass n_patches")
+        n_patches = B // (ph * pw)
+    n_patches = int(n_patches)
+    if n_patches < 0 or n_patches * ph * pw > B:
+        raise ValueError(f"{what}: n_patches = {n_patches} patches of {ph} x {pw} do not fit {B} rows")
+    _require_cuda(rgb, what)
+    return _PatchSsim.apply(rgb, target.detach().contiguous(), None if weight is None else weight.detach().contiguous(), n_patches, ph, pw, fs,
+                            float(filter_sigma), float(max_val), float(k1), float(k2))

@@ -116,3 +116,30 @@ class DeviceThetaImportanceSampler(_DeviceSampler):
         cdf[-1] = 1.0
         self.cdf_host = cdf
         self.cdf = torch.from_numpy(cdf).to(bank.device)
+
+
+class DevicePatchSampler(_DeviceSampler):
+    """Batches with known neighbours (no reference counterpart: its samplers draw independent pixels): `patches` patches of ph x pw pixels
+    `stride` apart, then `n_random` independent uniform pixels, one launch (ego_ray_batch_sample_patches states the rule).  Row
+    p ph pw + a pw + b of the batch is pixel (row0_p + a stride, col0_p + b stride) of image img_p, so `rgb[:n_patch_rays]` reads as
+    [patches, ph, pw, 3] - the layout losses.patch_ssim_loss takes.  Image and origin are uniform; on a bank whose window spans the full
+    width a patch may straddle the panorama's seam (columns modulo n_cols).  The indices live in the bank's index space: `bank.gather`,
+    `gather_depth_into`, `gather_mask_into` and `image_of` work on them, and GraphedTrainStep(batch_source=...) takes the sampler as it
+    takes the other two."""
+
+    def __init__(self, bank, patches, patch=(8, 8), stride=1, n_random=0, seed=0):
+        from .data import check_patch_shape
+        self.patches, self.n_random = int(patches), int(n_random)
+        if self.patches < 0 or self.n_random < 0:
+            raise ValueError("DevicePatchSampler: patches and n_random must be >= 0")
+        self.ph, self.pw, self.stride = check_patch_shape("DevicePatchSampler", bank, patch, stride)
+        self.patch = (self.ph, self.pw)
+        self.n_patch_rays = self.patches * self.ph * self.pw
+        super().__init__(bank, self.n_patch_rays + self.n_random, seed)
+
+    def sample_into(self, idx, rays, rgb, counter=None):
+        """One launch: idx [batch] int64 and (unless None) rays [batch,6], rgb [batch,3] for iteration `counter` (default: the
+        sampler's own device counter, which is NOT advanced here)."""
+        from .data import ray_batch_sample_patches
+        ray_batch_sample_patches(idx, rays, rgb, self.bank, self.seed, self.counter if counter is None else counter, self.patches, self.patch,
+                                 self.stride, self.n_random)

@@ -243,6 +243,26 @@ enum { EGO_BATCH_SIMPLE = 0, EGO_BATCH_THETA = 1 };
 int ego_ray_batch_sample(const ego_ray_bank* bank, int32_t mode, uint64_t seed, const int64_t* counter, const float* row_cdf, int64_t B,
                          int64_t* idx, float* rays, float* rgb, void* stream);
 
+/* Patch batches (append-only addition, EGO_ABI_VERSION stays 17; no reference counterpart: its samplers draw independent pixels): one launch,
+ * like ego_ray_batch_sample, fills idx [B] (and rays [B][6] / rgb [B][3] where not NULL) with B = P ph pw + n_random rows for iteration
+ * *counter (int64 dev, read by the kernel).  Row p ph pw + a pw + b is pixel (row0_p + a stride, col0_p + b stride) of image img_p, counted
+ * inside the bank's window: a patch is contiguous and row-major, so rgb[0 .. P ph pw) reads as [P][ph][pw][3] (ego_patch_ssim's layout).  The
+ * trailing n_random rows are independent uniform pixels of the window.  idx uses the bank's index space, so ego_ray_batch_gather and the
+ * depth / mask gathers work on it unchanged.
+ * The rule, with c = *counter, hi(x, n) = (x * n) >> 32 (the high half of a 32 x 32-bit product, bias <= n / 2^32) and Philox4x32-10:
+ *   patch p:   x = Philox(counter words (p lo, p hi, c lo, c hi), key (seed lo ^ 0x50415443, seed hi));  img_p = hi(x0, K),
+ *              row0_p = hi(x1, n_rows - (ph - 1) stride), col0_p = hi(x2, C).  When the window spans the full width (c0 == 0 and n_cols == W)
+ *              the panorama wraps: C = n_cols and the columns are (col0_p + b stride) mod n_cols, so a patch may straddle the seam;
+ *              otherwise C = n_cols - (pw - 1) stride, the origins whose patch fits.
+ *   random r:  x = Philox(counter words (r lo, r hi, c lo, c hi), key (seed lo ^ 0x52414E44, seed hi));  image hi(x0, K), column hi(x1, n_cols),
+ *              row hi(x2, n_rows): EGO_BATCH_THETA's image and column draw with the row uniform too.
+ * The key tweaks keep both streams apart from EGO_BATCH_THETA's, which keys the same counter words with the seed itself.  Every draw is a pure
+ * function of (seed, *counter, p) or (seed, *counter, r).  Refuses, before any launch: P < 0 or n_random < 0; ph, pw or stride < 1; a patch
+ * extent (ph - 1) stride + 1 > n_rows or (pw - 1) stride + 1 > n_cols (with or without the wrap); null counter or idx with B > 0.  B == 0 is
+ * a no-op. */
+int ego_ray_batch_sample_patches(const ego_ray_bank* bank, uint64_t seed, const int64_t* counter, int64_t P, int32_t ph, int32_t pw,
+                                 int32_t stride, int64_t n_random, int64_t* idx, float* rays, float* rgb, void* stream);
+
 /* Depth targets next to a bank (append-only addition, EGO_ABI_VERSION stays 17; ego_ray_bank itself does not change): depth [K][H][W] dev,
  * float32 (is_half == 0) or float16 (is_half != 0), one value per pixel of the bank's full images, in units of distance along the
  * normalised ray, 0 = no target.  out[i] (float32 [B] dev) = the depth of the pixel idx[i] names in the bank's index space (img, r0 + row,
@@ -780,6 +800,32 @@ int ego_photo_loss(const float* rgb, const float* target, const float* weight, c
  * Repeated calls return the same bits.  Refuses K < 1, image NULL with K != 1, null affine, null rgb or target with N > 0.  One launch. */
 int ego_photo_fit(const float* rgb, const float* target, const float* weight, const int32_t* image, int64_t N, int32_t K, float* affine,
                   double* Wk, void* stream);
+/* The structural term on patch batches (csrc/ego_patch_loss.hip; append-only addition, EGO_ABI_VERSION stays 17).  No reference counterpart:
+ * its rgb_ssim (utils.py:104-152) is a metric on whole images without a gradient.  rgb, target [>= P ph pw][3] float32 dev hold P patches of
+ * ph x pw pixels, row p ph pw + a pw + b = pixel (a, b) of patch p (ego_ray_batch_sample_patches' layout); weight [>= P ph pw] float32 dev
+ * or NULL (1); rows behind the patches are not read.  With g = the normalised Gaussian taps of ego_rgb_ssim (utils.py:117-121), per patch,
+ * channel and window origin (i, j), 0 <= i <= ph - fs, 0 <= j <= pw - fs, the window moments with weights g_a g_b over x = rgb, y = target:
+ *   mux, muy, Exx, Eyy, Exy;  sxx = Exx - mux^2, syy = Eyy - muy^2, sxy = Exy - mux muy;  C1 = (k1 max_val)^2, C2 = (k2 max_val)^2
+ *   A1 = 2 mux muy + C1, B1 = mux^2 + muy^2 + C1, A2 = 2 sxy + C2, B2 = sxx + syy + C2, S = A1 A2 / (B1 B2)
+ * all sums and products float64 over the float32 inputs; the metric's rounding guards (its clamps of sxx, syy, sxy and its float32 squares)
+ * are deliberately absent, so the term is smooth.  A window is valid iff every pixel under it has a finite weight > 0 and three finite target
+ * channels (the weight is a gate, not a soft weight); a non-finite rgb under a valid window is not hidden.  M = the number of valid
+ * (patch, window) pairs, counted on the device:
+ *   *value = 1 - (1 / 3M) sum_valid S   (WRITTEN, not accumulated; 0 when M = 0)
+ *   g_rgb[pixel] = -(1 / 3M) sum over the valid windows covering it of g_a g_b (dmu + 2 x dS/dExx + y dS/dExy),  dS/dExx = -S / B2,
+ *   dS/dExy = 2 A1 / (B1 B2),  dmu = (A2 / B2)(2 muy B1 - 2 mux A1) / B1^2 + 2 mux S / B2 - 2 muy A1 / (B1 B2)
+ * g_rgb [>= P ph pw][3] float32 dev: every element of its first P ph pw rows is WRITTEN, exactly 0 for a pixel under no valid window and
+ * everywhere when M = 0; rows behind are not touched.  value (float64 dev) and g_rgb are each optional.  `workspace`: caller-owned, 8-byte
+ * aligned, ego_patch_ssim_workspace_bytes(P, ph, pw) bytes (-1 for P < 0 or ph, pw outside 1..32; it does not know filter_size, which
+ * ego_patch_ssim checks itself), overwritten, no need to clear it.  One block
+ * per patch stages x and y in LDS, takes the moments separably (rows, then columns) and forms the gradient as the transposed separable filter
+ * of the three coefficient fields in a fixed tap order; per-patch sums and counts are joined in index order, no atomics: value-only,
+ * gradient-only, joint and repeated calls return the same bits.  Envelope: 1 <= filter_size <= 15, filter_size <= ph, pw <= 32.  Refuses,
+ * before any launch: a shape outside the envelope, P < 0, a filter_sigma that is not finite and > 0, null rgb, target or workspace, no output
+ * asked for.  P == 0 is a no-op.  At most three launches, no allocation, no synchronisation: it can be captured into a hipGraph. */
+int64_t ego_patch_ssim_workspace_bytes(int64_t P, int32_t ph, int32_t pw);
+int ego_patch_ssim(const float* rgb, const float* target, const float* weight, int64_t P, int32_t ph, int32_t pw, int32_t filter_size,
+                   double filter_sigma, double max_val, double k1, double k2, void* workspace, double* value, float* g_rgb, void* stream);
 /* coordinates.py:27-39 and :226-266 (up_sampling_VM): bilinear, align_corners=True, zero-padded resample of a table at
  * per-axis normalised positions xs [W2], ys [H2] (device) -> dst [H2][W2][C]. */
 int ego_resample_table(const float* src, int32_t C, int32_t H, int32_t W, const float* xs, const float* ys, int32_t H2, int32_t W2,
