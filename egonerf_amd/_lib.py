@@ -196,6 +196,7 @@ PROTOTYPES = {
     "ego_shade_composite": (C.c_int, [SP, P, P, P, P, P, I64, I32, P, P, P, P, P, P]),
     "ego_render_forward_folds": (C.c_int32, [SP, I64, I32]),
     "ego_render_forward_compacts": (C.c_int32, [SP, I64, I32]),
+    "ego_render_forward_marches": (C.c_int32, [SP, I64, I32]),
     "ego_train_packed_floats": (I64, []),
     "ego_pack_train": (C.c_int, [SP, P, P]),
     "ego_train_layout": (C.c_int, [I32, C.POINTER(C.c_int32), I32]),

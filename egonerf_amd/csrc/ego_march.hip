@@ -4,18 +4,20 @@
 //
 // k_march_density is a loop over a ray's 64-sample passes whose steps are named functions, in this file or shared with k_march_generic
 // (ego_march.h) and k_raw2alpha (ego_device.h):
-//   lut_hints            workgroup prologue: the radius LUT into LDS and the closed forms of its knots (LutHints, normalize_r_fast)
+//   lut_hints            workgroup prologue: the radius LUT into LDS and the closed forms of its knots (LutHints, normalize_r_fast)   [ego_march.h]
 //   march_distances      phase A: z and the interval to the neighbour                                            [ego_march.h]
-//   store_stopped        a pass behind exactly zero transmittance: distances and zero weights only
+//   store_stopped        a pass behind exactly zero transmittance: distances and zero weights only                [ego_march.h]
 //   march_coords         phase A: point, yin-yang coordinates, normalisation                                     [ego_march.h]
 //   sample_occupied      the occupancy mask's decision for the sample
 //   density_factored /   phase B, the density feature: 18 table taps through the wave's LDS slab, or 8 corners of the baked node
-//   density_dense        grid; one `if constexpr` chooses
+//   density_dense        grid; one `if constexpr` chooses                                                   [density_dense: ego_march.h]
 //   transmittance_step   phase C: alpha, in-pass exclusive product, pass total                                   [ego_device.h]
-//   march_store_sample   z, coordinates, sigma, alpha
-//   march_emit           weights and tile flags, from the transmittance in front of the pass
+//   march_store_sample   z, coordinates, sigma, alpha                                                             [ego_march.h]
+//   march_emit           weights and tile flags, from the transmittance in front of the pass                      [ego_march.h]
 //   Park                 a deferred segment's passes waiting in LDS for that transmittance (NSPLIT > 1)
 //   march_store_tail     the column of ones and the background weight                                            [ego_march.h]
+// The pieces marked [ego_march.h] are also those of the march that runs inside the folded dense shade kernel (march_wave_rays there;
+// k_shade_h with MARCH, csrc/ego_shade.hip).
 #include <stdlib.h>
 #include "ego_device.h"
 #include "ego_host.h"
@@ -42,94 +44,6 @@
 // per pass = 64 us at 16 waves per CU) and VALU issue, which overlap only partly.  Three waves per SIMD (167 VGPRs): at four the
 // two 24-register load buffers spill (92 B of scratch per lane, 31 MB per launch through L2: 124 us).  DESIGN.md 4.4.
 // =============================================================================================
-struct LutHints {   // derived per workgroup from the LUT itself (so any monotone LUT works: the estimate is only a starting point)
-  float r0;         // first knot spacing (lut[1] - lut[0])
-  float lin_end;    // last knot of the arithmetic run
-  float inv_l2r;    // 1 / log2(ratio) of the exponential tail
-  float shift;      // tail knots: shift + r0' * ratio^k
-  float inv_r0;
-  float tail_k0;    // index offset of the tail estimate
-};
-
-// Workgroup prologue (every thread calls it; three workgroup barriers): copies the radius LUT into `lut` and derives the hints from it.
-__device__ __forceinline__ LutHints lut_hints(const DevCoords& c, float* lut) {
-  __shared__ int s_nlin;
-  __shared__ LutHints s_hints;
-  for (int i = threadIdx.x; i < c.n_lut; i += blockDim.x) lut[i] = c.r_lut[i];
-  if (threadIdx.x == 0) s_nlin = c.n_lut - 1;
-  __syncthreads();
-  // arithmetic run = the leading intervals equal to lut[1] - lut[0] up to float32 rounding of k * r0 (the reference replaces
-  // every shell thinner than r0 by a step of r0): the first interval that is not ends it
-  const float r0 = lut[1] - lut[0];
-  int first_other = c.n_lut - 1;
-  for (int i = threadIdx.x; i + 1 < c.n_lut; i += blockDim.x)
-    if (!(fabsf((lut[i + 1] - lut[i]) - r0) <= r0 * 1e-3f)) first_other = min(first_other, i);
-  if (first_other < c.n_lut - 1) atomicMin(&s_nlin, first_other);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int n = c.n_lut, nl = s_nlin;
-    LutHints H;
-    H.r0 = r0; H.inv_r0 = 1.f / r0; H.lin_end = lut[nl];
-    // tail: lut[k] = shift + a * ratio^k: ratio from the last three knots, shift from the last two
-    float ratio = 2.f, sh = 0.f;
-    if (n - nl >= 4) {
-      const float a = lut[n - 3], b = lut[n - 2], cc = lut[n - 1];
-      ratio = (cc - b) / (b - a);
-      sh = b - (cc - b) / (ratio - 1.f);
-    }
-    H.shift = sh;
-    H.inv_l2r = 1.f / __log2f(fmaxf(ratio, 1.0000001f));
-    // kf = log2(r - shift) * inv_l2r + tail_k0 must give kf = k for r = lut[k]: calibrate on the last knot
-    H.tail_k0 = (float)(n - 1) - __log2f(fmaxf(lut[n - 1] - sh, 1e-30f)) * H.inv_l2r;
-    if (n - nl < 4) { H.lin_end = 3.0e38f; }   // (almost) all linear: never take the tail form
-    s_hints = H;
-  }
-  __syncthreads();
-  // wave-uniform: keep the six values in SGPRs (read from LDS they would occupy six VGPRs for the whole kernel)
-  const auto sf = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-  LutHints H;
-  H.r0 = sf(s_hints.r0); H.lin_end = sf(s_hints.lin_end); H.inv_l2r = sf(s_hints.inv_l2r); H.shift = sf(s_hints.shift);
-  H.inv_r0 = sf(s_hints.inv_r0); H.tail_k0 = sf(s_hints.tail_k0);
-  return H;
-}
-
-// searchsorted(lut, r, right) clamped to [1, n - 1] (coordinates.py:125-127) without the 10-step dependent search: estimate the
-// knot from the closed forms, read the four knots around it, accept if they bracket r, else search.  Bit-identical to normalize_r.
-__device__ __forceinline__ float normalize_r_fast(float r, const float* lut, int n_lut, int n_r, const LutHints& H) {
-  float kf;
-  if (r < H.lin_end) kf = r * H.inv_r0;
-  else kf = fmaf(__log2f(fmaxf(r - H.shift, 1e-30f)), H.inv_l2r, H.tail_k0);
-  kf = fminf(fmaxf(kf, 0.f), (float)(n_lut - 1));
-  const int c0 = (int)kf + 1;                      // estimate of lo = #{i : lut[i] <= r}
-  // knots c0 - 2 .. c0 + 1; virtual knots below index 0 are <= r, beyond the end are > r
-  int lo = c0 - 2;
-  bool ok = r == r;
-#pragma unroll
-  for (int d = -2; d <= 1; ++d) {
-    const int j = c0 + d;
-    const bool in = (unsigned)j < (unsigned)n_lut;
-    const float v = lut[in ? j : 0];
-    const bool le = in ? (v <= r) : (j < 0);
-    lo += le ? 1 : 0;
-    if (d == -2) ok = ok && le;                    // the window's first knot must not exceed r
-    if (d == 1) ok = ok && (!le || j >= n_lut - 1);  // and its last one must (unless it is the LUT's end)
-  }
-  if (!ok) {   // rare: estimate off by more than a knot (or NaN): the reference's search
-    int l = 0, h = n_lut;
-    while (l < h) {
-      const int mid = (l + h) >> 1;
-      if (!(lut[mid] > r)) l = mid + 1; else h = mid;
-    }
-    lo = l;
-  }
-  const int k_out = lo < 1 ? 1 : (lo > n_lut - 1 ? n_lut - 1 : lo);
-  const int k_in = k_out - 1;
-  const float g0 = lut[k_in], g1 = lut[k_out];
-  const float frac = __fdiv_rn(__fsub_rn(r, g0), __fsub_rn(g1, g0));
-  const float v = __fdiv_rn(__fadd_rn((float)k_in, frac), (float)n_r);
-  return __fsub_rn(__fmul_rn(v, 2.0f), 1.0f);
-}
-
 // NSPLIT (1, 2): a ray's passes are dealt to NSPLIT waves of the workgroup (segments of consecutive passes).  One wave per ray
 // leaves the launch quantised by wave slots: 3 waves per SIMD = 3 072 slots, so 4 096 rays take a full round and a third of one, 106 us
 // where 3 072 rays take 76 and the sustained rate (19.6 us per 1 024 rays) would give 80 (tools/march_timing.py sweep).  Shorter waves
@@ -171,49 +85,6 @@ struct Park {
   __device__ __forceinline__ float carry_in_front() const { return carry[-1]; }  // behind a workgroup barrier after the predecessor's publish
 };
 
-// ---- phase C behind the transmittance step: lane = sample.  (k_march_generic holds the same rules in one block of its own: through these
-// two functions it measured slower, csrc/ego_generic_march.hip.)
-// what does not depend on the transmittance in front of the sample
-__device__ __forceinline__ void march_store_sample(const MarchArgs& A, int64_t ray, const MarchSample& m, float sg, float a) {
-  if (!m.ok) return;
-  const int64_t o = ray * A.S + m.s;
-  if (A.z_out) A.z_out[o] = m.z;
-  if (A.coords_out) ((f32x4*)A.coords_out)[o] = f32x4{m.a_r, m.a_th, m.a_ph, m.yang ? 1.f : 0.f};
-  if (A.sigma_out) A.sigma_out[o] = sg;
-  if (A.alpha) A.alpha[ray * A.alpha_stride + m.s] = a;
-}
-
-// weights and tile flags of the pass at s0 from (alpha, in-pass exclusive product) and the transmittance `carry` in front of the pass
-__device__ __forceinline__ void march_emit(const MarchArgs& A, int64_t ray, int s0, int lane, float carry, float a, float exc) {
-  const int S = A.S, s = min(s0 + lane, S - 1);
-  const bool ok = (s0 + lane) < S;
-  const float T = carry * exc;
-  const float wgt = (A.term_eps > 0.f && T < A.term_eps) ? 0.f : a * T;  // early termination (opt-in)
-  if (A.tile_active) {
-    // 32-sample shade tiles are cut from the flat [N*S] order: lanes 0-31 / 32-63 of this pass are (parts of) tiles
-    // a tile is shaded iff it holds a sample whose colour is read: weight > shade_above (0, or rayMarch_weight_thres)
-    const unsigned long long nz = __ballot(ok && wgt > A.shade_above);
-    const int64_t o = ray * S + s;
-    if ((S & 31) == 0) {
-      // whole tiles per pass half: written unconditionally (0 or 1), so the caller need not clear the flags first
-      if (ok && (lane & 31) == 0) A.tile_active[o >> 5] = (nz >> (lane & 32) & 0xffffffffull) != 0ull ? 1 : 0;
-    } else if (ok && (nz >> (lane & 32) & 0xffffffffull) != 0ull && ((lane & 31) == 0 || (o & 31) == 0)) {
-      A.tile_active[o >> 5] = 1;  // tiles straddle rays: flags are pre-zeroed by the caller and only set here
-    }
-  }
-  if (ok && A.weight) A.weight[ray * S + s] = wgt;
-}
-
-// A pass that lies behind exactly zero transmittance (see may_stop in the kernel): its distances, zero weights, cleared whole tiles
-__device__ __forceinline__ void store_stopped(const MarchArgs& A, int64_t ray, const MarchSample& m, int lane) {
-  if (!m.ok) return;
-  const int64_t o = ray * A.S + m.s;
-  if (A.z_out) A.z_out[o] = m.z;
-  if (A.coords_out) ((f32x4*)A.coords_out)[o] = f32x4{0.f, 0.f, 0.f, 0.f};  // never shaded (tile flags stay 0); defined values anyway
-  if (A.weight) A.weight[o] = 0.f;
-  if (A.tile_active && (A.S & 31) == 0 && (lane & 31) == 0) A.tile_active[o >> 5] = 0;
-}
-
 // occupancy mask (opt-in): unoccupied samples keep sigma = 0.  Dense form: the field's own taps `t`, which phase B needs anyway, serve
 // the mask too where it has the field's resolution (the factored form sets its taps up behind the decision and passes none)
 template <bool OCC, bool DENSE>
@@ -224,49 +95,6 @@ __device__ __forceinline__ bool sample_occupied(const DevOcc& occ, const DevFiel
     if (same_res) return occ_occupied_taps(occ, m.yang, t.ax[0], t.ax[1], t.ax[2]);
   }
   return occ_occupied(occ, m.yang, m.a_r, m.a_th, m.a_ph);
-}
-
-// DENSE (inference scenes that carry ego_scene.density_dense, csrc/ego_dense.hip): phase B reads the baked node grid instead of the
-// 18 table taps.  Per plane i the factored feature dot_i = sum_c bilerp(plane_i,c) * lerp(line_i,c) is the trilinear interpolation of
-// G_i[phi][theta][r] = sum_c plane_i,c[node] * line_i,c[node] - plane and line interpolate on one lattice along independent axes, and an
-// out-of-range tap has weight 0 in either form - so with lane = sample a pass needs 8 loads of 16 B per lane, one per cell corner
-// carrying (G_0, G_1, G_2, 0), and no LDS hand-over: no stage / fres slabs, no wave barriers, far fewer registers (WPE waves per SIMD
-// instead of 3).  Everything around the density feature is the same text for both forms.
-//
-// ---- phase B, dense form: lane = sample.  The eight corners of the sample's cell as base + 32-bit byte offset, all eight loads
-// issued before the first use; interpolation along r, then theta, then phi, with lin_setup's weights (out-of-range taps: clamped
-// index, weight 0); relu per plane, planes summed in order.
-template <bool OCC>
-__device__ __forceinline__ float density_dense(const char* __restrict__ dense, uint32_t dense_grid_bytes, const int32_t res[3], int yang,
-                                               const VMTaps& t, bool occupied) {
-#pragma clang fp contract(fast)
-  const Lin1 &Rr = t.ax[0], &Tt = t.ax[1], &Pp = t.ax[2];
-  const uint32_t nr16 = (uint32_t)res[0] * 16u, gb = yang != 0 ? dense_grid_bytes : 0u;
-  const uint32_t row00 = gb + ((uint32_t)Pp.i0 * (uint32_t)res[1] + (uint32_t)Tt.i0) * nr16;
-  const uint32_t row01 = gb + ((uint32_t)Pp.i0 * (uint32_t)res[1] + (uint32_t)Tt.i1) * nr16;
-  const uint32_t row10 = gb + ((uint32_t)Pp.i1 * (uint32_t)res[1] + (uint32_t)Tt.i0) * nr16;
-  const uint32_t row11 = gb + ((uint32_t)Pp.i1 * (uint32_t)res[1] + (uint32_t)Tt.i1) * nr16;
-  const uint32_t c0 = (uint32_t)Rr.i0 * 16u, c1 = (uint32_t)Rr.i1 * 16u;
-  const f32x4 g000 = *(const f32x4*)(dense + (row00 + c0)), g001 = *(const f32x4*)(dense + (row00 + c1));
-  const f32x4 g010 = *(const f32x4*)(dense + (row01 + c0)), g011 = *(const f32x4*)(dense + (row01 + c1));
-  const f32x4 g100 = *(const f32x4*)(dense + (row10 + c0)), g101 = *(const f32x4*)(dense + (row10 + c1));
-  const f32x4 g110 = *(const f32x4*)(dense + (row11 + c0)), g111 = *(const f32x4*)(dense + (row11 + c1));
-  // every weight in a register of its own (see `issue` in density_factored: a packed multiply must broadcast the LOW half of its operand pair)
-  float w6[6] = {Rr.w0, Rr.w1, Tt.w0, Tt.w1, Pp.w0, Pp.w1};
-#pragma unroll
-  for (int k = 0; k < 6; ++k) asm volatile("" : "+v"(w6[k]));
-  const f32x4 v00 = g000 * w6[0] + g001 * w6[1], v01 = g010 * w6[0] + g011 * w6[1];
-  const f32x4 v10 = g100 * w6[0] + g101 * w6[1], v11 = g110 * w6[0] + g111 * w6[1];
-  const f32x4 u0 = v00 * w6[2] + v01 * w6[3], u1 = v10 * w6[2] + v11 * w6[3];
-  const f32x4 d = u0 * w6[4] + u1 * w6[5];
-  const float f = (fmaxf(d.x, 0.f) + fmaxf(d.y, 0.f)) + fmaxf(d.z, 0.f);   // relu per plane (EgoNeRF.py:340,346)
-  return OCC && !occupied ? 0.f : f;                                       // sample masked out: sigma stays 0 (feature unused)
-}
-
-__device__ __forceinline__ void wave_handover() {   // what the wave's lanes wrote to its LDS slab is what its lanes read behind this
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---- phase B, factored form, with the tail of phase A that only it needs (the set-up hand-over); owns the LDS slabs of the
@@ -488,13 +316,11 @@ static void launch_march(const MarchArgs& a, int nsplit, hipStream_t st) {
   }
 }
 
-extern "C" {
-
-int ego_march_density(const ego_scene* sc, const float* rays, int64_t N, int32_t S, const float* z_in,
-                      const float* r_sched, const float* jitter, float near_, int32_t coarse, float* z_out,
-                      float* alpha, int32_t alpha_stride, float* weight, float* bg_weight, float* coords_out, float* sigma_out,
-                      uint8_t* tile_active, void* stream) {
-  EGO_TRACE("ego_march_density");
+// ego_march_density's checks and its argument block without its launch (ego_march.h): the march that runs inside the shade kernel
+// (csrc/ego_shade.hip, MARCH) is described by the same block
+int ego_march_fill_args(const ego_scene* sc, const float* rays, int64_t N, int32_t S, const float* z_in, const float* r_sched, const float* jitter,
+                        float near_, int32_t coarse, float* z_out, float* alpha, int32_t alpha_stride, float* weight, float* bg_weight,
+                        float* coords_out, float* sigma_out, uint8_t* tile_active, MarchArgs* out, bool* tuned) {
   EGO_REQUIRE(sc && rays && N >= 0 && S >= 2, "march_density: null argument or S < 2");
   if (alpha_stride == 0) alpha_stride = S;
   EGO_REQUIRE(alpha_stride >= S && alpha_stride <= S + 64, "march_density: alpha_stride must be in [S, S+64]");
@@ -502,20 +328,38 @@ int ego_march_density(const ego_scene* sc, const float* rays, int64_t N, int32_t
   EGO_REQUIRE(sc->r_lut && sc->n_r_lut >= 2 && sc->n_r_lut <= 1024, "march_density: r_lut missing or > 1024 entries");
   const ego_vm_field& f = (coarse & 1) ? sc->density_coarse : sc->density;
   if (int e = check_field(f, "march_density")) return e;
-  if (N == 0) return EGO_OK;
+  *tuned = f.n_comp == 16;
+  *out = MarchArgs{};
+  if (N == 0) return EGO_OK;   // an empty call asks nothing of the baked grid
   MarchArgs a = march_args(*sc, f, coarse);
   a.rays = rays; a.z_in = z_in; a.r_sched = r_sched; a.jitter = jitter; a.near_ = near_;
   a.z_out = z_out; a.alpha = alpha; a.weight = weight; a.bg = bg_weight; a.coords_out = coords_out; a.sigma_out = sigma_out;
   a.tile_active = tile_active;
   a.N = N; a.S = S; a.alpha_stride = alpha_stride;
-  if (f.n_comp != 16) return ego_generic_march(a, stream);   // any other component count: the compatibility kernel (csrc/ego_generic_march.hip)
   // the dense form (k_march_density, DENSE): the scene carries the baked node grid of the field this call marches
-  if (a.dense) {
+  if (*tuned && a.dense) {
     const uint64_t grid_bytes = (uint64_t)f.res[0] * (uint64_t)f.res[1] * (uint64_t)f.res[2] * 16u;
     EGO_REQUIRE(((uintptr_t)a.dense & 15) == 0, "march_density: the dense density grid must be 16-byte aligned");
     EGO_REQUIRE(2 * grid_bytes < ((uint64_t)1 << 32), "march_density: the dense density grid must stay under 4 GB (32-bit byte offsets)");
     a.dense_grid_bytes = (uint32_t)grid_bytes;
   }
+  *out = a;
+  return EGO_OK;
+}
+
+extern "C" {
+
+int ego_march_density(const ego_scene* sc, const float* rays, int64_t N, int32_t S, const float* z_in,
+                      const float* r_sched, const float* jitter, float near_, int32_t coarse, float* z_out,
+                      float* alpha, int32_t alpha_stride, float* weight, float* bg_weight, float* coords_out, float* sigma_out,
+                      uint8_t* tile_active, void* stream) {
+  EGO_TRACE("ego_march_density");
+  MarchArgs a;
+  bool tuned = false;
+  if (int e = ego_march_fill_args(sc, rays, N, S, z_in, r_sched, jitter, near_, coarse, z_out, alpha, alpha_stride, weight, bg_weight, coords_out,
+                                  sigma_out, tile_active, &a, &tuned)) return e;
+  if (N == 0) return EGO_OK;
+  if (!tuned) return ego_generic_march(a, stream);   // any other component count: the compatibility kernel (csrc/ego_generic_march.hip)
   launch_march(a, march_nsplit(N, (S + 63) / 64, a.dense ? MARCH_DENSE_WAVES : MARCH_WAVES), (hipStream_t)stream);
   return ego_launch_status("k_march_density");
 }

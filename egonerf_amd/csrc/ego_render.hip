@@ -2,6 +2,7 @@
 // sequence of launches on the caller's stream, no host synchronisation, no allocation.
 #include "ego_host.h"
 #include "ego_generic.h"
+#include "ego_march.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -86,6 +87,14 @@ int32_t ego_render_forward_compacts(const ego_scene* sc, int64_t N, int32_t S) {
   return (f && f[0] == '1') || sc->occ || sc->weight_thres > 0.f ? 1 : 0;
 }
 
+int32_t ego_render_forward_marches(const ego_scene* sc, int64_t N, int32_t S) {
+  const char* f = getenv("EGO_RENDER_MARCH");   // read per call, as EGO_MARCH_SPLIT is: a test flips it inside one process
+  if (f && f[0] == '0') return 0;
+  if (!sc || N < 1 || S < 32 || N * (int64_t)S >= (1ll << 31)) return 0;
+  if (ego_render_forward_compacts(sc, N, S) || !ego_render_forward_folds(sc, N, S)) return 0;
+  return ego_can_march_in_shade(sc, S) ? 1 : 0;
+}
+
 int ego_render_forward(const ego_scene* sc, const ego_render_args* a, const float* rays, int64_t N, void* workspace,
                        float* rgb_map, float* depth, float* alpha, float* bg_map, float* env_map, void* stream) {
   EGO_TRACE("ego_render_forward");
@@ -119,6 +128,15 @@ int ego_render_forward(const ego_scene* sc, const ego_render_args* a, const floa
     if ((e = ego_march_density(sc, rays, N, S, ws + p.zf, nullptr, nullptr, a->near_, 2 /* fine pass: full tables, fine LUT */, nullptr, alpha, astride, ws + p.w,
                                ws + p.bg, ws + p.crd, nullptr, act, stream))) return e;
     z = ws + p.zf;
+  } else if (!a->marched && ego_render_forward_marches(sc, N, S)) {
+    // one launch: the folded dense shade kernel's waves march their rays themselves, into the same workspace slots, ahead of their tiles.
+    // Not with a `marched` event: it is promised behind the march and AHEAD of the shade (the caller starts copies on it that are to
+    // run under the shade phase), and one launch has no such point.
+    MarchArgs m;
+    bool tuned = false;
+    if ((e = ego_march_fill_args(sc, rays, N, S, zc_in, zc_in ? nullptr : a->r_sched, zc_in ? nullptr : a->jitter, a->near_, 0,
+                                 zc_in ? nullptr : ws + p.zc, alpha, astride, ws + p.w, ws + p.bg, ws + p.crd, nullptr, act, &m, &tuned))) return e;
+    return ego_march_shade_composite(sc, m, rgb_map, depth, bg_map, env_map, stream);
   } else {
     if ((e = ego_march_density(sc, rays, N, S, zc_in, zc_in ? nullptr : a->r_sched, zc_in ? nullptr : a->jitter, a->near_, 0,
                                zc_in ? nullptr : ws + p.zc, alpha, astride, ws + p.w, ws + p.bg, ws + p.crd, nullptr, act, stream))) return e;

@@ -10,6 +10,7 @@
 #include "ego_tuned.h"
 #include "variants.h"
 #include "ego_generic.h"
+#include "ego_march.h"
 
 namespace {
 
@@ -1050,9 +1051,28 @@ __device__ __forceinline__ void gather_app_dense(const char* __restrict__ G, uin
 // DAPP: the features come from the baked node grid (gather_app_dense) instead of the tables and the basis; inference without dumps
 // and with fp32 tables only (MODE_SHADE in its three forms, and MODE_APP so that the features can be checked on their own).  Then A.F
 // describes the node grid, not the tables: F.base = the grid, F.poff[g][0] = the byte offset of grid g in it, F.res = its resolution.
-template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false, bool COMPACT = false, bool DAPP = false>
-__global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
+// MARCH (the three FOLD + DAPP instances; ego_render_forward's one-launch eval render): ahead of its first tile a wave marches the rays
+// it is about to shade - march_wave_rays (ego_march.h), k_march_density's dense one-wave form on MARCH passes side by side - into the
+// workspace slots that kernel fills, and the tile loop reads them through A.z / A.comp_w / A.coords as it reads that kernel's output.
+// The march's argument block is a kernel parameter of its own that only a marching instance has (MB: a grown ShadeArgs moves literals
+// in every instance); it is read through an opaque address inside the march, so that nothing of it can become an invariant of the tile
+// loop.  That address is `kernel-argument segment + sizeof(ShadeArgs)`: it is the code-object ABI's layout (explicit arguments first, in
+// declaration order, each at its natural alignment), so `mb` must stay the SECOND AND LAST explicit parameter, and a MarchBlock whose
+// alignment sizeof(ShadeArgs) is no multiple of does not compile (static_assert below).
+// A wave's tiles read what other lanes of the SAME wave stored: vmcnt(0) and a wavefront-scope release / acquire pair stand between; the
+// stores and the tile loop's loads go through the CU's one write-through vector L1, which is coherent between the CU's waves (a sibling
+// wave may have pulled in a line of tile flags before this wave stored its own).  The tile loop must read these buffers with vector loads.
+struct MarchBlock {
+  MarchArgs a;
+  int32_t rays_per_wave;   // the folded deal: wave w of the grid owns rays [w * rays_per_wave, (w + 1) * rays_per_wave) below N
+};
+
+template <int MODE, bool DUMP = false, bool TAB16 = false, int PX = 0, bool FOLD = false, bool COMPACT = false, bool DAPP = false, int MARCH = 0,
+          class... MB>
+__global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A, MB... mb) {
   constexpr bool P8 = PX == 1, P6 = PX == 2;
+  static_assert(!MARCH || (FOLD && DAPP), "the in-wave march exists for the folded dense instances only");
+  static_assert(sizeof...(MB) == (MARCH ? 1 : 0), "a marching instance takes the march's argument block, the others nothing");
   // RAY_VIEW: a folded wave's tiles are whole rays, so the dense instances encode the view direction once per ray and keep the lane
   // half's eight view slots across its tiles; their tile loop holds no division m / S, no load of the direction and no encoding of it.
   // The table instances have no registers for that (built: 6 / 19 VGPRs spilled in the f16x3 / f16f6 forms; with the direction as
@@ -1079,6 +1099,23 @@ __global__ __launch_bounds__(512) void k_shade_h(ShadeArgs A) {
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)from, (__attribute__((address_space(3))) void*)(lds + c * 256), 16, 0, 0);
     }
     for (int i = NCH * 64 + threadIdx.x; i < NQ; i += 512) ((f32x4*)lds)[i] = src[i];
+    if constexpr (MARCH) {
+      // LUT and hints once per workgroup, in LDS next to the image, behind barriers of their own; then the wave's rays.  (The first
+      // global load of either waits for the wave's share of the image, 19 KB: vmcnt retires in order.)
+      static_assert(sizeof(ShadeArgs) % alignof(MarchBlock) == 0, "the march block follows ShadeArgs in the kernel-argument segment");
+      static_assert(sizeof...(MB) == 1 && (std::is_same<MB, MarchBlock>::value && ...), "the march block is the kernel's second and last explicit parameter");
+      uint64_t ka = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(ShadeArgs);
+      asm volatile("" : "+s"(ka));
+      const MarchBlock* mblock = (const MarchBlock*)(const __attribute__((address_space(4))) MarchBlock*)ka;
+      __shared__ float march_lut[LUT_MAX];
+      const MarchArgs& MA = mblock->a;
+      const LutHints H = lut_hints(MA.c, march_lut);
+      const int64_t ray0 = ((int64_t)blockIdx.x * 8 + wv_u) * mblock->rays_per_wave;
+      const int64_t ray1 = ray0 + mblock->rays_per_wave < MA.N ? ray0 + mblock->rays_per_wave : MA.N;
+      march_wave_rays<MARCH>(MA, march_lut, H, ray0, ray1, threadIdx.x & 63);
+      __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the march's stores have reached L2 ...
+      wave_handover();                      // ... and no load of the tile loop is issued ahead of that
+    }
   }
   bool need_sync = MODE != MODE_APP;   // wave-uniform: the barrier that publishes the LDS image is still ahead
   {
@@ -1382,6 +1419,15 @@ ShadeArgs shade_args(const ego_scene* sc, int64_t M, int32_t S) {   // (the tabl
 }
 
 // PX = 0 f16x3, 1 f16f8, 2 f16f6 where the MLP runs for inference (MLP, SHADE, SHADE + FOLD, SHADE + COMPACT), 0 elsewhere
+// the marching form of the folded dense kernel (MARCH passes of a ray side by side); `mb` travels behind `a`
+constexpr int MARCH_P = 2;
+void launch_shade_march(int32_t precision, const ShadeArgs& a, const MarchBlock& mb, hipStream_t st) {
+  const unsigned grid = shade_grid(a.M);
+  if (precision == EGO_PREC_F16F8) return k_shade_h<MODE_SHADE, false, false, 1, true, false, true, MARCH_P, MarchBlock><<<grid, 512, 0, st>>>(a, mb);
+  if (precision == EGO_PREC_F16F6) return k_shade_h<MODE_SHADE, false, false, 2, true, false, true, MARCH_P, MarchBlock><<<grid, 512, 0, st>>>(a, mb);
+  k_shade_h<MODE_SHADE, false, false, 0, true, false, true, MARCH_P, MarchBlock><<<grid, 512, 0, st>>>(a, mb);
+}
+
 template <int MODE, bool DUMP, bool FOLD, bool COMPACT, bool TAB16, bool DAPP = false>
 void launch_shade_h(int32_t precision, const ShadeArgs& a, hipStream_t st) {
   const unsigned grid = shade_grid(a.M);
@@ -1390,6 +1436,21 @@ void launch_shade_h(int32_t precision, const ShadeArgs& a, hipStream_t st) {
     if (precision == EGO_PREC_F16F6) return k_shade_h<MODE, DUMP, TAB16, 2, FOLD, COMPACT, DAPP><<<grid, 512, 0, st>>>(a);
   }
   k_shade_h<MODE, DUMP, TAB16, 0, FOLD, COMPACT, DAPP><<<grid, 512, 0, st>>>(a);
+}
+
+// the baked node grid (app_f16 = EGO_APP_DENSE: app16.plane[0][0]) as the field of a DAPP instance (see k_shade_h)
+int dense_app_field(const ego_scene* sc, const char* who, DevField& F) {
+  const float* grid = sc->app16.plane[0][0];
+  if (!grid) return ego_fail(EGO_E_BADARG, "%s: app_f16 is EGO_APP_DENSE but app16.plane[0][0] (the node grid) is null", who);
+  if (sc->app16.n_comp != APP_C || sc->app16.res[0] != sc->app.res[0] || sc->app16.res[1] != sc->app.res[1] || sc->app16.res[2] != sc->app.res[2])
+    return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must be baked from 48 components at the resolution of `app`", who);
+  const uint64_t grid_bytes = (uint64_t)sc->app.res[0] * (uint64_t)sc->app.res[1] * (uint64_t)sc->app.res[2] * 128u;
+  if (((uintptr_t)grid & 15) != 0) return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must be 16-byte aligned", who);
+  if (2 * grid_bytes >= ((uint64_t)1 << 32))
+    return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must stay under 4 GB (32-bit byte offsets)", who);
+  F.base = (const char*)grid;   // (see k_shade_h, DAPP)
+  F.poff[0][0] = 0u; F.poff[1][0] = (uint32_t)grid_bytes;
+  return EGO_OK;
 }
 
 // The set of shade instances: the entry point fixes MODE / DUMP / FOLD / COMPACT, the scene's mlp_precision and app_f16 pick the rest.
@@ -1415,16 +1476,7 @@ int launch_shade(const ego_scene* sc, ShadeArgs& a, const char* who, const char*
   }
   if constexpr (!DUMP && MODE != MODE_MLP) {
     if (sc->app_f16 == EGO_APP_DENSE) {   // the baked node grid (app16.plane[0][0]) instead of tables and basis
-      const float* grid = sc->app16.plane[0][0];
-      if (!grid) return ego_fail(EGO_E_BADARG, "%s: app_f16 is EGO_APP_DENSE but app16.plane[0][0] (the node grid) is null", who);
-      if (sc->app16.n_comp != APP_C || sc->app16.res[0] != sc->app.res[0] || sc->app16.res[1] != sc->app.res[1] || sc->app16.res[2] != sc->app.res[2])
-        return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must be baked from 48 components at the resolution of `app`", who);
-      const uint64_t grid_bytes = (uint64_t)sc->app.res[0] * (uint64_t)sc->app.res[1] * (uint64_t)sc->app.res[2] * 128u;
-      if (((uintptr_t)grid & 15) != 0) return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must be 16-byte aligned", who);
-      if (2 * grid_bytes >= ((uint64_t)1 << 32))
-        return ego_fail(EGO_E_BADARG, "%s: the dense appearance grid must stay under 4 GB (32-bit byte offsets)", who);
-      a.F.base = (const char*)grid;   // (see k_shade_h, DAPP)
-      a.F.poff[0][0] = 0u; a.F.poff[1][0] = (uint32_t)grid_bytes;
+      if (int e = dense_app_field(sc, who, a.F)) return e;
       launch_shade_h<MODE, DUMP, FOLD, COMPACT, false, true>(sc->mlp_precision, a, st);
       return ego_launch_status(label);
     }
@@ -1561,3 +1613,36 @@ extern "C" int ego_shade_composite(const ego_scene* sc, const float* rays, const
   a.rgb_map = rgb_map; a.depth = depth; a.bg_map = bg_map; a.env_map = env_map;
   return launch_shade<MODE_SHADE, false, true>(sc, a, "shade_composite", "k_shade<SHADE, composite>", stream);
 }
+
+// ego_render_forward's one-launch eval render: ego_march_density + ego_shade_composite as the marching form of the folded dense kernel.
+// `m` is the march's argument block (ego_march_fill_args); the tile loop reads the workspace slots it names.
+bool ego_can_march_in_shade(const ego_scene* sc, int32_t S) {
+  return ego_can_fold_composite(sc, S) && sc->app_f16 == EGO_APP_DENSE && sc->density_dense && sc->density.n_comp == 16 &&
+         sc->density.res[0] == sc->app.res[0] && sc->density.res[1] == sc->app.res[1] && sc->density.res[2] == sc->app.res[2] &&
+         !sc->occ && !(sc->term_eps > 0.f) && sc->r_lut && sc->n_r_lut >= 2 && sc->n_r_lut <= LUT_MAX;
+}
+
+int ego_march_shade_composite(const ego_scene* sc, const MarchArgs& m, float* rgb_map, float* depth, float* bg_map, float* env_map, void* stream) {
+  EGO_TRACE("ego_march_shade_composite");
+  const int64_t N = m.N;
+  const int32_t S = m.S;
+  EGO_REQUIRE(rgb_map && m.dense && m.weight && m.coords_out && (m.z_in || m.z_out) && !m.occ.vol && !m.sigma_out && !(m.term_eps > 0.f) &&
+              N >= 0 && S >= 32 && (S & 31) == 0 && N * (int64_t)S < (1ll << 31), "march_shade_composite: needs the dense march without mask or early termination, S a multiple of 32, N*S < 2^31");
+  if (!ego_can_march_in_shade(sc, S)) return ego_fail(EGO_E_UNSUPPORTED, "march_shade_composite: the folded dense shade with both baked grids at one resolution only");
+  if (int e = check_shade_config(sc, "march_shade_composite", true, true)) return e;
+  EGO_REQUIRE(!sc->envmap || m.bg, "march_shade_composite: envmap needs bg_weight");
+  if (N == 0) return EGO_OK;
+  ShadeArgs a = shade_args(sc, N * (int64_t)S, S);
+  a.rays = m.rays; a.z = m.z_out ? m.z_out : m.z_in; a.coords = m.coords_out; a.tile_active = m.tile_active;
+  a.comp_w = m.weight; a.comp_bg = m.bg; a.envmap = sc->envmap; a.envmap_h = sc->envmap_h;
+  a.rgb_map = rgb_map; a.depth = depth; a.bg_map = bg_map; a.env_map = env_map;
+  a.F = make_field(sc->app);
+  if (int e = dense_app_field(sc, "march_shade_composite", a.F)) return e;
+  MarchBlock mb;
+  mb.a = m;
+  const int64_t n_wv = (int64_t)shade_grid(a.M) * 8;
+  mb.rays_per_wave = (int32_t)((N + n_wv - 1) / n_wv);
+  launch_shade_march(sc->mlp_precision, a, mb, (hipStream_t)stream);
+  return ego_launch_status("k_shade<SHADE, composite, march>");
+}
+

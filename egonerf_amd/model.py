@@ -1076,7 +1076,8 @@ class EgoNeRF(TensorBase):
         `volume_renderer(keep_alpha=False)` passes) returns None for the per-sample alpha, which also lets the ray march stop
         evaluating a ray once its transmittance is exactly 0 (the remaining weights are exactly 0 either way).  `marched_event` (a created
         torch.cuda.Event; volume_renderer's host hand-over passes it): recorded on the current stream behind the call's last march, ahead
-        of its shade kernel (ego_render_args.marched) - or at the end of a call that takes another path."""
+        of its shade kernel (ego_render_args.marched) - or at the end of a call that takes another path.  A call that passes it keeps
+        march and shade two launches where it would otherwise render in one (ego_render_forward_marches)."""
         self._last_render = self._last_shaded = None   # set again by a call that runs ego_render_forward
         _require_cuda(rays_chunk, "EgoNeRF.forward")
         if rays_chunk.dim() != 2 or rays_chunk.shape[1] < 6:

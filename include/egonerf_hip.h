@@ -548,6 +548,16 @@ int ego_shade_composite(const ego_scene* sc, const float* rays, const float* z, 
  * whenever the scene qualifies.  No device work. */
 int32_t ego_render_forward_folds(const ego_scene* sc, int64_t N, int32_t S);
 
+/* 1 iff ego_render_forward renders N rays x S samples of this scene in ONE launch: the folded dense shade kernel whose waves march the
+ * rays they are about to shade themselves, ahead of their tiles, into the workspace slots ego_march_density fills (same bits; coords
+ * behind an exactly opaque prefix are zeros, as in the one-wave march).  Taken without resampling when ego_render_forward_folds holds,
+ * the scene carries both baked grids (density_dense and the dense appearance grid) at one resolution, 16 density components, no mask,
+ * no term_eps, weight_thres <= 0 (with weight_thres = 0, the exact skip of all-zero tiles, the kernel writes and reads the tile flags
+ * itself), and the compact path is not taken.  The answer is for a call WITHOUT ego_render_args.marched: a call that passes that event
+ * keeps the march a launch of its own, so that the event stays behind the march and ahead of the shade.  Environment:
+ * EGO_RENDER_MARCH=0 keeps the two launches (read per call).  No device work. */
+int32_t ego_render_forward_marches(const ego_scene* sc, int64_t N, int32_t S);
+
 /* 1 iff ego_render_forward shades only the LIVE samples of N rays x S samples of this scene - weight > max(weight_thres, 0), the
  * app_mask of TensorBase.forward (models/tensorBase.py:480-487), which runs the appearance lookup and the MLP on coords_sampled[app_mask]
  * only - instead of the 32-sample tiles of the flat [N][S] order that hold one: it builds the list of those samples (ray-major, no
@@ -1019,7 +1029,8 @@ typedef struct ego_render_args {
   void* marched;         /* v17: hipEvent_t or NULL.  Recorded on `stream` behind the LAST march launch, ahead of the shade: lets a caller
                           * start copies of the PREVIOUS call's outputs under this call's shade kernel (bound by instruction issue) instead
                           * of under its march (bound by the latency of its gathers: next to the runtime's copy kernel it took 260 us
-                          * instead of 97, tools/handover_timeline.sh) */
+                          * instead of 97, tools/handover_timeline.sh).  A call that passes it never takes the one-launch render
+                          * (ego_render_forward_marches), which has no point between march and shade */
 } ego_render_args;
 
 /* Whole EgoNeRF.forward for N rays.  S_out = n_coarse (no resampling) | n_coarse+n_fine | n_fine.
